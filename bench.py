@@ -2,6 +2,7 @@
 """bench.py -- audio-sec/s of the EncoderDecoderASR hot path on MI355X (BASELINE.json metric).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   # + the timed region's token ids as DIR/*.npy
     python bench.py --gpus 8 --steps 20 --warmup 5      # spawns 8 ranks itself (torch.distributed.run, RCCL)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   # same thing
 
@@ -83,6 +84,30 @@ def make_job(n_utts, seed=1234, lo=5.0, hi=30.0):
     pool = (0.1 * torch.randn(pool_len + int(hi * SR) + 1, generator=g) * 32768.0).round().clamp(-32768, 32767).to(torch.int16)
     utts = [pool[(i * 104729) % pool_len:][:n_i] for i, n_i in enumerate(n)]
     return utts, [n_i / SR for n_i in n]
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(path, hyps, seed=0):
+    """--dump-outputs: what the timed region returned -- one token-id list per utterance, in job order -- as
+    `path`/token_ids.npy (float32, one row per utterance, padded with -1), token_counts.npy (float32) and utterance_index.npy
+    (float64, the job index of each row).  When the ids would pass DUMP_BYTES_MAX, the rows are a fixed seeded sample."""
+    import numpy as np
+
+    width = max((len(h) for h in hyps), default=0)
+    idx = torch.arange(len(hyps))
+    rows = (DUMP_BYTES_MAX - 4096) // (4 * width + 4 + 8)  # (4096: the three .npy headers)
+    if len(hyps) > rows:
+        idx = torch.randperm(len(hyps), generator=torch.Generator().manual_seed(seed))[:rows].sort().values
+    idx = idx.tolist()
+    ids = np.full((len(idx), width), -1.0, dtype=np.float32)
+    for r, i in enumerate(idx):
+        ids[r, :len(hyps[i])] = [int(v) for v in hyps[i]]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "token_ids.npy"), ids)
+    np.save(os.path.join(path, "token_counts.npy"), np.array([len(hyps[i]) for i in idx], dtype=np.float32))
+    np.save(os.path.join(path, "utterance_index.npy"), np.array(idx, dtype=np.float64))
 
 
 def frames_after_frontend(n_samples):
@@ -224,13 +249,13 @@ def cpu_baseline_subprocess(timeouts=(("4x10s", 420), ("2shortest", 200))):
     return {**fail, "sample": "; ".join(notes)}
 
 
-REFERENCE_ROOT = os.environ.get("SBK_BENCH_REFERENCE", "/root/reference")  # (this container only: the GPU box has no reference tree -> kind "port")
+REFERENCE_ROOT = os.environ.get("SBK_BENCH_REFERENCE", "")  # opt-in: a checkout of the reference (unset: the oracle port, kind "port")
 
 
 def _reference_runner(sd, steps, n_samples):
     """The reference's OWN modules (speechbrain.lobes.features.Fbank, ConvolutionFrontEnd, TransformerASR,
-    S2STransformerBeamSearcher + CTCScorer) with the same weights, when /root/reference is present."""
-    if not os.path.isdir(os.path.join(REFERENCE_ROOT, "speechbrain")):
+    S2STransformerBeamSearcher + CTCScorer) with the same weights, when SBK_BENCH_REFERENCE names a checkout of the reference."""
+    if not REFERENCE_ROOT or not os.path.isdir(os.path.join(REFERENCE_ROOT, "speechbrain")):
         return None
     for pth in (REFERENCE_ROOT, os.path.join(ROOT, "oracle", "ref_stubs")):
         if pth not in sys.path:
@@ -258,7 +283,7 @@ def _reference_runner(sd, steps, n_samples):
 
 
 def cpu_baseline(kind="4x10s", budget_s=240.0):
-    """The CPU leg: the reference's own modules when /root/reference exists (kind "reference"), else the oracle port of
+    """The CPU leg: the reference's own modules when SBK_BENCH_REFERENCE names them (kind "reference"), else the oracle port of
     the reference's CPU path (kind "port": no KV cache, Python-loop CTC scorer -- the reference's algorithm restated).
     One cheap warm-up (a 1-second batch: thread pools, oneDNN primitives), then best of 3 timed runs of the sample (fewer
     only when `budget_s` runs out).  With the 4 x 10 s sample it also decodes 12 x 10 s ONCE with the output heads x8 --
@@ -297,7 +322,7 @@ def cpu_baseline(kind="4x10s", budget_s=240.0):
            "kind": "reference" if ref_run is not None else "port",
            "sample": f"{what}: {seconds:.1f} audio-s, padded to {wav.shape[1] / SR:.2f} s, "
                      f"Conformer-L beam 10 + CTC 0.4, {steps} decode steps, "
-                     + ("the reference's own modules from /root/reference" if ref_run is not None else "oracle/sb_oracle.py")
+                     + ("the reference's own modules from SBK_BENCH_REFERENCE" if ref_run is not None else "oracle/sb_oracle.py")
                      + f" (torch-CPU fp32); 1-second warm-up batch + best of {len(times)} ({', '.join(f'{t:.1f}' for t in times)} s)",
            "tokens": [list(map(int, h)) for h in hyps]}
     if kind == "4x10s":  # the parity sample: 12 x 10 s, peaked heads, the oracle once
@@ -562,6 +587,9 @@ def main():
                          "of the timed region itself -- per kernel class the time its launches took with the other workers' "
                          "kernels co-resident, and the mean number of kernels in flight (sum of those times / wall clock); "
                          "rocprofv3 serialises the launch path of several threads and cannot show this regime (DESIGN.md section 6)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed region, write the token ids it returned to DIR/*.npy (dump_outputs): the inputs are "
+                         "seeded, so two builds run with the same arguments can be compared output for output")
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args()
 
@@ -892,6 +920,8 @@ def main():
             "per_rank": {"wall_s": info["per_rank_wall_s"], "audio_s": info["per_rank_audio_s"], "batches": info["per_rank_batches"]},
             **({"concurrent_kernels": info["concurrent_kernels"]} if "concurrent_kernels" in info else {}),
         }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, hyps)
 
     # ---- secondary legs (N = 1), EACH IN A PROCESS OF ITS OWN (the legs used to share the parent's caching-allocator
     # pools -- one per worker stream -- and the third leg measured 8.3 K where the same leg alone gives 11-12 K): the same

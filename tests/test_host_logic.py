@@ -244,6 +244,26 @@ def test_bench_roofline_entry_prices_each_kernel_against_its_own_peak():
     assert e["bound"] == "hbm" and e["unit"] == "GB/s" and abs(e["achieved"] - 1000.0) < 1e-6 and e["peak"] == 8000.0
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the timed region's token-id lists as float32 rows padded with -1, their lengths and job
+    indices; above the size cap a seeded sample of the rows, the same one on every call."""
+    import bench
+
+    hyps = [[5, 6, 7], [8], [9, 10]]
+    bench.dump_outputs(str(tmp_path / "all"), hyps)
+    ids, n, idx = (np.load(tmp_path / "all" / f"{k}.npy") for k in ("token_ids", "token_counts", "utterance_index"))
+    assert ids.dtype == np.float32 and n.dtype == np.float32 and idx.dtype == np.float64
+    assert ids.tolist() == [[5, 6, 7], [8, -1, -1], [9, 10, -1]] and n.tolist() == [3, 1, 2] and idx.tolist() == [0, 1, 2]
+    hyps = [[i, i + 1] for i in range(1000)]
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 4096 + 100 * 20)  # room for 100 rows: two ids, a count, an index
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), hyps)
+    ids, idx = np.load(tmp_path / "a" / "token_ids.npy"), np.load(tmp_path / "a" / "utterance_index.npy")
+    assert ids.shape == (100, 2) and len(set(idx.tolist())) == 100 and list(idx) == sorted(idx)
+    assert ids[:, 0].tolist() == idx.tolist() and idx.tolist() != list(range(100))
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "utterance_index.npy"))
+
+
 def test_bench_traffic_rows_of_this_rounds_kernels_only(tmp_path):
     """bench.pmc_traffic: the `traffic` field of the roofline object is the PMC figure of THIS round's kernel as shipped or null --
     a row of an earlier round, and a row counted before a later change of the kernel's schedule ("superseded"), are quoted in
