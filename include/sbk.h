@@ -365,6 +365,39 @@ int sbk_rope_attention_bf16(const float* qkv, const float* cosines, const float*
 int sbk_glu_dwconv_f32(const float* h, const float* w, const float* bias, float* y, int B, int T, int d, int ksize,
                        int chunk_size, sbk_stream_t stream);
 
+/* ---- CTC decoding (csrc/ctc_decode.hip; additive entries, ABI 11 unchanged) ---------------------------------------------
+ * ctc_greedy_decode (decoders/ctc.py:335-380): x [B,T,V] (log-)probabilities, rel_len [B] relative lengths (device; NULL =
+ * 1.0).  Utterance b uses its first int(round(fp32(rel_len[b] * T))) frames (round half to even, as torch.round); per frame
+ * the arg-max as torch.max picks it (the first of equal maxima, NaN above everything); repeats collapse, then `blank`
+ * (0 <= blank < V) is dropped.  tokens [B,T] int32: the first count[b] entries of row b are the result. */
+int sbk_ctc_greedy_decode_f32(const float* x, const float* rel_len, int32_t* tokens, int32_t* count, int B, int T, int V,
+                              int blank, sbk_stream_t stream);
+
+/* CTCBeamSearcher without a language model (decoders/ctc.py:782-935,1070-1153,1203-1220,1298-1487): one workgroup per
+ * utterance, every frame in one launch, the beam in LDS.
+ *   x [B,T,V] log-probabilities; rel_len [B] (device; NULL = 1.0): utterance b decodes int(fp32(T * rel_len[b])) frames
+ *   (truncation, as decode_beams does).
+ *   token_table [Vl][8] int32 (device), Vl = len(vocab_list) <= V (columns >= Vl are never expanded):
+ *     {kind (0 regular, 1 the blank, 2 a word boundary: the space token, or a SentencePiece piece that starts with the
+ *     boundary mark), string id (tokens with equal strings share one), n = length in characters of the token's text (a
+ *     boundary piece without its mark; 0 for the space token), h1, b1^n, h2, b2^n, 0} where h_i = sum_k (c_k + 1) * b_i^(n-1-k)
+ *     mod 2^31-1 over the text's code points c_k and (b1, b2) = cfg->char_base1/2.
+ *   workspace: sbk_ctc_beam_search_workspace_bytes(B, T, V, beam_size, topk) bytes, 16-byte aligned (backpointer records).
+ *   out_tokens [B,topk,T] int32: for hypothesis k (best first, the reference's final order) the token expanded at every frame
+ *   along its path, -1 at skipped / padded frames -- the host rebuilds `text` and `text_frames` from it; out_score [B,topk]
+ *   the hypothesis' score; out_count [B] the number of hypotheses (<= topk).
+ * beam_size 1..256 (larger beams are refused); topk 1..beam_size; V <= 65535. */
+typedef struct sbk_ctc_beam_config {
+  int32_t blank, beam_size, topk, prune_history;
+  float beam_prune_logp, token_prune_min_logp;
+  float log_blank_skip_threshold; /* a frame is skipped when x[blank] > this */
+  uint32_t char_base1, char_base2, space_code; /* hash bases (< 2^31-1) and the code of " " (ord(' ') + 1) */
+} sbk_ctc_beam_config;
+size_t sbk_ctc_beam_search_workspace_bytes(int B, int T, int V, int beam, int topk);
+int sbk_ctc_beam_search_f32(const float* x, const float* rel_len, const int32_t* token_table, int Vl,
+                            const sbk_ctc_beam_config* cfg, void* workspace, size_t workspace_bytes, int32_t* out_tokens,
+                            float* out_score, int32_t* out_count, int B, int T, int V, sbk_stream_t stream);
+
 /* log_softmax(x / temperature) * weight over the last dimension, x [rows,V] (seq2seq.py:1933). */
 int sbk_log_softmax_f32(const float* x, float* out, int rows, int V, float temperature, float weight,
                         sbk_stream_t stream);

@@ -70,6 +70,103 @@ class EncoderDecoderASR(Pretrained):
         return self.transcribe_batch(wavs, wav_lens)
 
 
+class EncoderASR(Pretrained):
+    """inference/ASR.py:176-386: an encoder ending in a CTC head (``ctc_lin`` + log-softmax) and a CTC decoding function.
+
+    ``hparams['decoding_function']`` is either a ``functools.partial`` (greedy: ``ctc_greedy_decode`` with its blank) or a
+    ``CTCBaseSearcher`` subclass, instantiated here with ``hparams['test_beam_search']`` and the tokenizer's vocabulary
+    (``CTCTextEncoder.ind2lab`` or SentencePiece pieces).  Both run on the device (decoders/ctc.py).  The encoder's
+    ``torch.nn.LogSoftmax`` children are replaced by ``NativeLogSoftmax`` (sbk_log_softmax_f32)."""
+
+    HPARAMS_NEEDED = ["tokenizer", "decoding_function"]
+    MODULES_NEEDED = ["encoder"]
+
+    def __init__(self, *args, **kwargs):
+        from speechbrain_amd.nnet.activations import NativeLogSoftmax
+
+        super().__init__(*args, **kwargs)
+        self.tokenizer = self.hparams.tokenizer
+        NativeLogSoftmax.replace_in(self.mods.encoder)
+        self.set_decoding_function()
+
+    def set_decoding_function(self):
+        import functools
+
+        from speechbrain_amd.dataio.encoder import CTCTextEncoder
+        from speechbrain_amd.decoders.ctc import CTCBaseSearcher
+
+        fn = self.hparams.decoding_function
+        if isinstance(fn, functools.partial):
+            self.decoding_function = fn
+            return
+        if not (isinstance(fn, type) and issubclass(fn, CTCBaseSearcher)):
+            raise ValueError("The decoding function must be an instance of speechbrain.decoders.CTCBaseSearcher")
+        if isinstance(self.tokenizer, CTCTextEncoder):
+            ind2lab = self.tokenizer.ind2lab
+            vocab_list = [ind2lab[x] for x in range(len(ind2lab))]
+        elif type(self.tokenizer).__name__ == "SentencePieceProcessor":
+            vocab_list = [self.tokenizer.id_to_piece(i) for i in range(self.tokenizer.vocab_size())]
+        else:
+            raise ValueError("The tokenizer must be sentencepiece or CTCTextEncoder")
+        opts = dict(getattr(self.hparams, "test_beam_search", None) or {})
+        if "kenlm_model_path" in opts:
+            raise NotImplementedError("CTC beam search with a kenlm n-gram model is not implemented")
+        self.decoding_function = fn(**opts, vocab_list=vocab_list)
+
+    def transcribe_file(self, path, **kwargs):
+        waveform = self.load_audio(path, **kwargs)
+        predicted_words, _ = self.transcribe_batch(waveform.unsqueeze(0), torch.tensor([1.0]))
+        return str(predicted_words[0])
+
+    def encode_batch(self, wavs, wav_lens):
+        """The log-probabilities of the CTC head [B,T,V].  As in EncoderDecoderASR.encode_batch, only the Transformer
+        encoder runs under the interface's precision (fp32 = the parity path): the children of the encoder container
+        that are an ``EncoderWrapper`` / ``TransformerASR``; the feature front-end, the CNN and the CTC head stay fp32.
+        (An encoder that is not a container runs under the precision as a whole.)"""
+        from speechbrain_amd import native
+        from speechbrain_amd.lobes.models.transformer.TransformerASR import EncoderWrapper, TransformerASR
+        from speechbrain_amd.nnet.containers import LengthsCapableSequential, Sequential
+
+        wavs = wavs.float()
+        wavs, wav_lens = wavs.to(self.device), wav_lens.to(self.device)
+        enc = self.mods.encoder
+        if self.eval_precision == "fp32" or not isinstance(enc, Sequential):
+            with native.precision_scope(self.eval_precision):
+                return enc(wavs, wav_lens)
+        x = wavs
+        for name, layer in enc.items():  # LengthsCapableSequential.forward / Sequential.forward, child by child
+            p = self.eval_precision if isinstance(layer, (EncoderWrapper, TransformerASR)) else "fp32"
+            with native.precision_scope(p):
+                if isinstance(enc, LengthsCapableSequential) and name in enc.length_layers:
+                    x = layer(x, lengths=wav_lens)
+                else:
+                    x = layer(x)
+            if isinstance(x, tuple):
+                x = x[0]
+        return x
+
+    def transcribe_batch(self, wavs, wav_lens):
+        import functools
+
+        from speechbrain_amd.dataio.encoder import CTCTextEncoder
+
+        with torch.no_grad():
+            wav_lens = wav_lens.to(self.device)
+            encoder_out = self.encode_batch(wavs, wav_lens)
+            predictions = self.decoding_function(encoder_out, wav_lens)
+            if isinstance(self.hparams.decoding_function, functools.partial):
+                if isinstance(self.tokenizer, CTCTextEncoder):
+                    predicted_words = ["".join(self.tokenizer.decode_ndim(seq)) for seq in predictions]
+                else:
+                    predicted_words = [self.tokenizer.decode_ids(seq) for seq in predictions]
+            else:
+                predicted_words = [hyp[0].text for hyp in predictions]
+        return predicted_words, predictions
+
+    def forward(self, wavs, wav_lens):
+        return self.encode_batch(wavs, wav_lens)
+
+
 @_dataclass
 class ASRWhisperSegment:
     """inference/ASR.py:391-428: one chunk of a long-form Whisper transcription."""

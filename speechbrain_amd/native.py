@@ -70,6 +70,12 @@ class SearchConfig(ctypes.Structure):  # sbk_search_config
                 ("ctc_w3", c_void_p)]
 
 
+class CTCBeamConfig(ctypes.Structure):  # sbk_ctc_beam_config
+    _fields_ = [("blank", c_int32), ("beam_size", c_int32), ("topk", c_int32), ("prune_history", c_int32),
+                ("beam_prune_logp", c_float), ("token_prune_min_logp", c_float), ("log_blank_skip_threshold", c_float),
+                ("char_base1", ctypes.c_uint32), ("char_base2", ctypes.c_uint32), ("space_code", ctypes.c_uint32)]
+
+
 def _declare(lib):
     p, i, f = c_void_p, c_int, c_float
     sig = {
@@ -136,6 +142,9 @@ def _declare(lib):
         "sbk_glu_dwconv_f32": ([p, p, p, p, i, i, i, i, i, p], c_int),
         "sbk_layernorm_f32": ([p, p, p, p, i, i, f, i, p], c_int),
         "sbk_log_softmax_f32": ([p, p, i, i, f, f, p], c_int),
+        "sbk_ctc_greedy_decode_f32": ([p, p, p, p, i, i, i, i, p], c_int),
+        "sbk_ctc_beam_search_workspace_bytes": ([i, i, i, i, i], ctypes.c_size_t),
+        "sbk_ctc_beam_search_f32": ([p, p, p, i, POINTER(CTCBeamConfig), p, ctypes.c_size_t, p, p, p, i, i, i, p], c_int),
         "sbk_beam_search_workspace_bytes": ([POINTER(DecoderWeights), POINTER(SearchConfig), i, i], ctypes.c_size_t),
         "sbk_beam_search_f32": ([POINTER(DecoderWeights), POINTER(SearchConfig), p, p, p, p, p, ctypes.c_size_t, p, p,
                                  p, p, p, p, p, POINTER(c_int32), i, i, p], c_int),
@@ -1511,6 +1520,45 @@ def log_softmax(x, temperature=1.0, weight=1.0):
     _chk(lib.sbk_log_softmax_f32(_p(x2), _p(out), x2.shape[0], V, float(temperature), float(weight), _stream(x2)),
          "sbk_log_softmax_f32")
     return out
+
+
+# ------------------------------------------------------------------ CTC decoding (csrc/ctc_decode.hip)
+def ctc_greedy_decode(x, rel_len, blank):
+    """x [B,T,V] fp32 -> (tokens [B,T] int32, count [B] int32): row b's first count[b] entries are its collapsed,
+    blank-free arg-max path over int(round(rel_len[b] * T)) frames (rel_len None = every frame)."""
+    lib = load()
+    _f32(x)
+    B, T, V = x.shape
+    x = x.contiguous()
+    rel = None if rel_len is None else rel_len.to(device=x.device, dtype=torch.float32).contiguous()
+    _dev_ok(x, rel)
+    tokens = torch.empty(B, T, dtype=torch.int32, device=x.device)
+    count = torch.empty(B, dtype=torch.int32, device=x.device)
+    _chk(lib.sbk_ctc_greedy_decode_f32(_p(x), _p(rel), _p(tokens), _p(count), B, T, V, int(blank), _stream(x)),
+         "sbk_ctc_greedy_decode_f32")
+    return tokens, count
+
+
+def ctc_beam_search(x, rel_len, table, n_vocab, cfg):
+    """CTCBeamSearcher without an LM on the device.  x [B,T,V] fp32 log-probabilities, table [n_vocab,8] int32 (the token
+    table of include/sbk.h), cfg a CTCBeamConfig -> (paths [B,topk,T] int32, scores [B,topk], count [B])."""
+    lib = load()
+    _f32(x)
+    B, T, V = x.shape
+    x = x.contiguous()
+    rel = None if rel_len is None else rel_len.to(device=x.device, dtype=torch.float32).contiguous()
+    table = table.to(device=x.device, dtype=torch.int32).contiguous()
+    _dev_ok(x, rel, table)
+    nbytes = lib.sbk_ctc_beam_search_workspace_bytes(B, T, V, cfg.beam_size, cfg.topk)
+    ws = torch.empty(max(nbytes, 1) + 16, dtype=torch.uint8, device=x.device)
+    off = (-ws.data_ptr()) % 16
+    paths = torch.empty(B, max(cfg.topk, 1), T, dtype=torch.int32, device=x.device)
+    scores = torch.empty(B, max(cfg.topk, 1), dtype=torch.float32, device=x.device)
+    count = torch.empty(B, dtype=torch.int32, device=x.device)
+    _chk(lib.sbk_ctc_beam_search_f32(_p(x), _p(rel), _p(table), int(n_vocab), ctypes.byref(cfg),
+                                     c_void_p(ws.data_ptr() + off), nbytes, _p(paths), _p(scores), _p(count), B, T, V,
+                                     _stream(x)), "sbk_ctc_beam_search_f32")
+    return paths, scores, count
 
 
 # ------------------------------------------------------------------ HIP-event profiler
