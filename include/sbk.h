@@ -398,6 +398,54 @@ int sbk_ctc_beam_search_f32(const float* x, const float* rel_len, const int32_t*
                             const sbk_ctc_beam_config* cfg, void* workspace, size_t workspace_bytes, int32_t* out_tokens,
                             float* out_score, int32_t* out_count, int B, int T, int V, sbk_stream_t stream);
 
+/* ---- transducer greedy decoding (csrc/transducer.hip; additive entries, ABI 11 unchanged) -------------------------------
+ * TransducerBeamSearcher.transducer_greedy_decode (decoders/transducer.py:156-291) for the prediction network (PN)
+ * [Embedding, LSTM (1..SBK_TRANSDUCER_MAX_LAYERS unidirectional layers, torch gate order i, f, g, o), Linear proj_dec], the
+ * joint Transducer_joint(joint="sum") -- act(tn[t] + out_PN) -- and one classifier Linear, then log-softmax.
+ * Weights are fp32 device memory, row-major in torch's layouts; H = hidden, J = joint dim, V = classifier outputs (tokens),
+ * G = 4H.
+ *   emb_ih   [n_emb, G]  the Embedding folded into layer 0's input weights: row k = E[k] . W_ih_l0^T (for the one-hot table
+ *                        of consider_as_one_hot=True that row is a column of W_ih_l0, the blank's row is zero)
+ *   w_ih[l]  [G, H]      weight_ih_l<l> of layers l >= 1 (w_ih[0] is unused)
+ *   w_hh[l]  [G, H]      weight_hh_l<l>;  b_ih[l], b_hh[l] [G] (NULL = no bias)
+ *   proj     [J, H]      proj_dec's weight;  proj_b [J] or NULL
+ *   out      [V, J]      the classifier's weight;  out_b [V] or NULL
+ * One workgroup per utterance runs every frame of tn [B,T,J] (no lengths: padded frames are decoded too, as the reference
+ * does).  At each frame the joint is evaluated and its arg-max (torch.max: the first of equal maxima, NaN above all) taken;
+ * a non-blank token is appended, its log-probability added to score[b], the PN advanced by it and the same frame evaluated
+ * again, at most max_symbols_per_step + 1 times per frame.
+ *   state: out_pn [B,J], h [L,B,H], c [L,B,H] -- read on entry unless start_from_blank (then the PN's output for the blank
+ *          token from a zero state), and overwritten with the final state (so that streaming can continue).
+ *   tokens [B, T*(max_symbols_per_step+1)] int32: the first count[b] entries of row b; score [B] the summed log-probabilities.
+ *   frame_block: frames whose joint is evaluated together against the current out_PN (0 = default); the result does not
+ *   depend on it (every logit has one summation order).  act: SBK_ACT_GELU (exact erf), SBK_ACT_LEAKY_RELU (slope 0.01),
+ *   SBK_ACT_TANH or SBK_ACT_RELU.  Needs V <= n_emb (an emitted token is the PN's next input). */
+#define SBK_TRANSDUCER_MAX_LAYERS 4
+enum { SBK_ACT_TANH = 5 }; /* (the transducer joint only) */
+typedef struct sbk_transducer_weights {
+  const float* emb_ih;
+  const float* w_ih[SBK_TRANSDUCER_MAX_LAYERS];
+  const float* w_hh[SBK_TRANSDUCER_MAX_LAYERS];
+  const float* b_ih[SBK_TRANSDUCER_MAX_LAYERS];
+  const float* b_hh[SBK_TRANSDUCER_MAX_LAYERS];
+  const float* proj;
+  const float* proj_b;
+  const float* out;
+  const float* out_b;
+  int32_t n_layers, hidden, joint, vocab, n_emb;
+} sbk_transducer_weights;
+typedef struct sbk_transducer_config {
+  int32_t blank, max_symbols_per_step, start_from_blank, frame_block, act;
+} sbk_transducer_config;
+/* One unidirectional LSTM layer over whole sequences (torch.nn.LSTM, gate order i, f, g, o), the step code of the transducer
+ * search: xp [B,T,4H] = x . W_ih^T (the input part, without bias; e.g. from sbk_gemm_nt_f32), w_hh [4H,H] = weight_hh,
+ * b_ih / b_hh [4H] (NULL = none); h / c [B,H] the initial state, overwritten with the final one; out [B,T,H]. */
+int sbk_lstm_f32(const float* xp, const float* w_hh, const float* b_ih, const float* b_hh, float* h, float* c, float* out,
+                 int B, int T, int H, sbk_stream_t stream);
+int sbk_transducer_greedy_f32(const sbk_transducer_weights* W, const sbk_transducer_config* cfg, const float* tn,
+                              float* out_pn, float* h, float* c, int32_t* tokens, int32_t* count, float* score, int B, int T,
+                              sbk_stream_t stream);
+
 /* log_softmax(x / temperature) * weight over the last dimension, x [rows,V] (seq2seq.py:1933). */
 int sbk_log_softmax_f32(const float* x, float* out, int rows, int V, float temperature, float weight,
                         sbk_stream_t stream);

@@ -18,6 +18,8 @@ _MODULES = [
     "decoders.scorer", "decoders.utils", "inference", "inference.ASR", "inference.interfaces", "utils",
     "utils.data_utils", "utils.parameter_transfer", "utils.metric_stats", "utils.edit_distance",
     "utils.dynamic_chunk_training", "utils.filter_analysis", "dataio", "dataio.encoder", "decoders.ctc",
+    "decoders.transducer", "nnet.RNN", "nnet.transducer", "nnet.transducer.transducer_joint", "tokenizers",
+    "tokenizers.SentencePiece",
 ]
 
 

@@ -3,6 +3,7 @@
 // of an utterance in ONE launch with its beam in LDS.  The semantics reproduced here are listed in DESIGN.md section 5.
 #include <math.h>
 
+#include "argmax.h"
 #include "common.h"
 
 namespace sbk {
@@ -17,14 +18,6 @@ __device__ __forceinline__ uint32_t hmul(uint32_t a, uint32_t b) { return (uint3
 __device__ __forceinline__ uint32_t hadd(uint32_t a, uint32_t b) {
   const uint32_t s = a + b;  // (a, b < 2^31: no wrap)
   return s >= kHashMod ? s - kHashMod : s;
-}
-
-// "x better than y" under torch.max / numpy.argmax: the larger value, NaN above everything, the first index on ties
-__device__ __forceinline__ bool arg_better(float v, int i, float w, int j) {
-  const bool vn = isnan(v), wn = isnan(w);
-  if (vn != wn) return vn;
-  if (!vn && v != w) return v > w;
-  return i < j;
 }
 
 // ---------------------------------------------------------------------------------------------------------- greedy

@@ -4,3 +4,5 @@ from speechbrain_amd.decoders.seq2seq import (S2STransformerBeamSearcher, S2STra
                                                 S2SWhisperBeamSearcher, S2SWhisperGreedySearcher)
 from speechbrain_amd.decoders.ctc import (CTCBaseSearcher, CTCBeamSearcher, CTCHypothesis,  # noqa: F401
                                            CTCPrefixBeamSearcher, ctc_greedy_decode, filter_ctc_output)
+from speechbrain_amd.decoders.transducer import (TransducerBeamSearcher,  # noqa: F401
+                                                  TransducerGreedySearcherStreamingContext)

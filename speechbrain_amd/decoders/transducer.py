@@ -1,0 +1,132 @@
+"""speechbrain.decoders.transducer mirror: TransducerBeamSearcher's greedy search (decoders/transducer.py:25-345) on the
+device.
+
+The whole search of a batch -- prediction network (PN) steps, joint, classifier, log-softmax and arg-max for every frame --
+is ONE launch of sbk_transducer_greedy_f32 (csrc/transducer.hip), one workgroup per utterance.  Supported: the PN
+[Embedding (dense or one-hot), LSTM (unidirectional, 1..4 layers), Linear], Transducer_joint(joint="sum") with GELU,
+LeakyReLU, Tanh or ReLU, and one classifier Linear.  Transducer beam search (beam_size > 1), LM fusion and other PN layers
+raise NotImplementedError when the searcher is called."""
+from dataclasses import dataclass
+from typing import Any, Optional
+
+import torch
+
+from speechbrain_amd import native
+
+
+@dataclass
+class TransducerGreedySearcherStreamingContext(torch.nn.Module):
+    """The hidden state carried between the chunks of a stream (decoders/transducer.py:15-22)."""
+
+    hidden: Optional[Any] = None
+
+
+class TransducerBeamSearcher(torch.nn.Module):
+    """decoders/transducer.py:25-145.  Constructs for any beam size (reference YAMLs define a beam searcher with an LM
+    beside the greedy one); only a call with ``beam_size > 1`` raises."""
+
+    def __init__(self, decode_network_lst, tjoint, classifier_network, blank_id, beam_size=4, nbest=5, lm_module=None,
+                 lm_weight=0.0, state_beam=2.3, expand_beam=2.3):
+        super().__init__()
+        self.decode_network_lst = decode_network_lst
+        self.tjoint = tjoint
+        self.classifier_network = classifier_network
+        self.blank_id = blank_id
+        self.beam_size = beam_size
+        self.nbest = nbest
+        self.lm = lm_module
+        self.lm_weight = lm_weight
+        if lm_module is None and lm_weight > 0:
+            raise ValueError("Language model is not provided.")
+        self.state_beam = state_beam
+        self.expand_beam = expand_beam
+        if self.beam_size <= 1:
+            self.searcher = self.transducer_greedy_decode
+        else:
+            self.searcher = self.transducer_beam_search_decode
+        self._prepared = None
+        self._prepared_key = None
+
+    def forward(self, tn_output):
+        return self.searcher(tn_output)
+
+    def transducer_beam_search_decode(self, tn_output):
+        raise NotImplementedError(f"transducer beam search (beam_size={self.beam_size}) is not implemented; use beam_size=1")
+
+    # ------------------------------------------------------------------ the network, in the kernel's layout
+    def _networks(self):
+        from speechbrain_amd.nnet.embedding import Embedding
+        from speechbrain_amd.nnet.linear import Linear
+        from speechbrain_amd.nnet.RNN import LSTM
+
+        if self.lm is not None and self.lm_weight > 0:
+            raise NotImplementedError("transducer decoding with LM fusion is not implemented")
+        layers = list(self.decode_network_lst)
+        for layer in layers:
+            if type(layer).__name__ in ("GRU", "RNN", "LiGRU", "LiGRU_Layer"):
+                raise NotImplementedError(f"a {type(layer).__name__} prediction network is not implemented (LSTM only)")
+        if not (len(layers) == 3 and isinstance(layers[0], Embedding) and isinstance(layers[1], LSTM)
+                and isinstance(layers[2], Linear)):
+            raise NotImplementedError("transducer prediction networks other than [Embedding, LSTM, Linear] are not "
+                                      f"implemented (got {[type(x).__name__ for x in layers]})")
+        cls = list(self.classifier_network)
+        if not (len(cls) == 1 and isinstance(cls[0], Linear)):
+            raise NotImplementedError("transducer classifiers other than one Linear are not implemented "
+                                      f"(got {[type(x).__name__ for x in cls]})")
+        return layers[0], layers[1], layers[2], cls[0]
+
+    def _prepare(self, device):
+        """The kernel's weight layouts on ``device``, rebuilt when a parameter changes (the PN and classifier modules are
+        plain list members, as in the reference, so they are not moved with the searcher)."""
+        emb, lstm, proj, lin = self._networks()
+        params = [emb.Embedding.weight] + [p for p in lstm.parameters()] + [p for p in proj.parameters()] + [
+            p for p in lin.parameters()]
+        key = (device,) + tuple((p.data_ptr(), p._version, p.device) for p in params)
+        if self._prepared is None or key != self._prepared_key:
+            d = lambda t: None if t is None else t.detach().to(device)  # noqa: E731
+            layers = [tuple(d(t) for t in layer) for layer in lstm.layer_weights()]
+            self._prepared = native.TransducerPrepared(d(emb.Embedding.weight), layers, d(proj.w.weight), d(proj.w.bias),
+                                                       d(lin.w.weight), d(lin.w.bias))
+            self._prepared_key = key
+        return self._prepared
+
+    # ------------------------------------------------------------------ greedy search
+    def transducer_greedy_decode(self, tn_output, hidden_state=None, return_hidden=False, max_symbols_per_step=5,
+                                 frame_block=0):
+        """decoders/transducer.py:156-291.  Returns (hyps, exp(scores).mean(), None, None[, (out_PN, (h, c))]) with
+        hyps a list of token lists.  The hidden state is a set of device tensors of the reference's shapes, out_PN
+        [B,1,J] and h / c [L,B,H]; a given ``hidden_state`` is updated in place, as the reference does.  ``frame_block``:
+        frames evaluated together by the kernel (0 = its default; the result does not depend on it)."""
+        tn = tn_output.detach().float().contiguous()
+        prep = self._prepare(tn.device)
+        act = self.tjoint.act_code
+        B, T, J = tn.shape
+        L, H = prep.W.n_layers, prep.W.hidden
+        if hidden_state is None:
+            out_pn = torch.empty(B, 1, J, dtype=torch.float32, device=tn.device)
+            h = torch.empty(L, B, H, dtype=torch.float32, device=tn.device)
+            c = torch.empty(L, B, H, dtype=torch.float32, device=tn.device)
+            start = True
+        else:
+            out_pn, (h, c) = hidden_state
+            for t, shape in ((out_pn, (B, 1, J)), (h, (L, B, H)), (c, (L, B, H))):
+                if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
+                    raise ValueError(f"hidden_state: expected contiguous fp32 tensors of shapes [B,1,J], [L,B,H], [L,B,H]; "
+                                     f"got {tuple(t.shape)} {t.dtype}")
+            start = False
+        tokens, count, score = native.transducer_greedy(prep, tn, out_pn, h, c, self.blank_id, max_symbols_per_step,
+                                                        start_from_blank=start, act=act, frame_block=frame_block)
+        counts = count.cpu().tolist()
+        rows = tokens.cpu().tolist()
+        hyps = [row[:n] for row, n in zip(rows, counts)]
+        scores = score.cpu()
+        ret = (hyps, scores.exp().mean(), None, None)
+        if return_hidden:
+            ret += ((out_pn, (h, c)),)
+        return ret
+
+    def transducer_greedy_decode_streaming(self, x: torch.Tensor, context: TransducerGreedySearcherStreamingContext):
+        """decoders/transducer.py:293-317: a `decoding_function` for StreamingASR."""
+        hyp, _scores, _, _, hidden = self.transducer_greedy_decode(x, context.hidden, return_hidden=True)
+        context.hidden = hidden
+        return hyp

@@ -12,7 +12,10 @@ class EncoderDecoderASR(Pretrained):
 
     ``modules`` needs ``encoder`` (Fbank -> InputNormalization -> ConvolutionFrontEnd container) and
     ``decoder`` (a searcher); with ``hparams['transformer_beam_search']`` true, ``modules['transformer']``
-    (TransformerASR) encodes the front-end output (ASR.py:70-74,126-128)."""
+    (TransformerASR) encodes the front-end output (ASR.py:70-74,126-128).  With ``hparams['transducer_beam_search']``
+    true the decoder is a transducer searcher (decoders/transducer.py), called with the encoder output alone as the
+    reference does (ASR.py:160-164); the run_opts precision then scopes only the Transformer children of the encoder,
+    as in EncoderASR."""
 
     HPARAMS_NEEDED = ["tokenizer"]
     MODULES_NEEDED = ["encoder", "decoder"]
@@ -22,8 +25,6 @@ class EncoderDecoderASR(Pretrained):
         self.tokenizer = self.hparams.tokenizer
         self.transducer_beam_search = getattr(self.hparams, "transducer_beam_search", False)
         self.transformer_beam_search = getattr(self.hparams, "transformer_beam_search", False)
-        if self.transducer_beam_search:
-            raise NotImplementedError("transducer decoding is a different model family")
 
     def transcribe_file(self, path, **kwargs):
         waveform = self.load_audio(path, **kwargs)
@@ -33,6 +34,8 @@ class EncoderDecoderASR(Pretrained):
     def encode_batch(self, wavs, wav_lens):
         from speechbrain_amd import native
 
+        if self.transducer_beam_search and not self.transformer_beam_search:
+            return EncoderASR.encode_batch(self, wavs, wav_lens)
         wavs = wavs.float()
         wavs, wav_lens = wavs.to(self.device), wav_lens.to(self.device)
         encoder_out = self.mods.encoder(wavs, wav_lens)  # Fbank / normalisation / CNN: always fp32
@@ -62,7 +65,8 @@ class EncoderDecoderASR(Pretrained):
         with torch.no_grad():
             wav_lens = wav_lens.to(self.device)
             encoder_out = self.encode_batch(wavs, wav_lens)
-            predicted_tokens, _, _, _ = self.mods.decoder(encoder_out, wav_lens)
+            inputs = [encoder_out] if self.transducer_beam_search else [encoder_out, wav_lens]
+            predicted_tokens, _, _, _ = self.mods.decoder(*inputs)
             predicted_words = [self.tokenizer.decode_ids(seq) for seq in predicted_tokens]
         return predicted_words, predicted_tokens
 
@@ -362,9 +366,10 @@ class ASRStreamingContext:
 class StreamingASR(Pretrained):
     """Chunk-by-chunk ASR (inference/ASR.py:978-1363): ``hparams.fea_streaming_extractor`` (a
     StreamingFeatureWrapper) -> ``mods.enc.forward_streaming`` (Conformer with left-context caches) ->
-    ``mods.proj_enc`` -> ``hparams.decoding_function``.  The decoder of the reference's streaming models is a
-    transducer search, which is a different model family; any callable ``decoding_function(x, decoder_context) ->
-    list[list[int]]`` plugs in (e.g. a greedy CTC decoder over ``proj_enc``'s output)."""
+    ``mods.proj_enc`` -> ``hparams.decoding_function``.  The decoder of the reference's streaming models is the transducer
+    greedy search, ``TransducerBeamSearcher.transducer_greedy_decode_streaming`` (decoders/transducer.py); any callable
+    ``decoding_function(x, decoder_context) -> list[list[int]]`` plugs in (e.g. a greedy CTC decoder over ``proj_enc``'s
+    output)."""
 
     HPARAMS_NEEDED = ["fea_streaming_extractor", "make_decoder_streaming_context", "decoding_function",
                       "make_tokenizer_streaming_context", "tokenizer_decode_streaming"]
@@ -373,6 +378,12 @@ class StreamingASR(Pretrained):
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
         self.filter_props = self.hparams.fea_streaming_extractor.properties
+        # The feature extractor is an hparam, not a module, so Pretrained neither moves nor freezes it.  The reference's
+        # Fbank builds its filters on the input's device at every call; here the front-end's tables live in the module,
+        # so the extractor goes to the interface's device (and into eval mode) with the modules.
+        extractor = self.hparams.fea_streaming_extractor
+        if isinstance(extractor, torch.nn.Module):
+            extractor.to(self.device).eval()
 
     def make_streaming_context(self, dynchunktrain_config):
         return ASRStreamingContext(

@@ -76,6 +76,20 @@ class CTCBeamConfig(ctypes.Structure):  # sbk_ctc_beam_config
                 ("char_base1", ctypes.c_uint32), ("char_base2", ctypes.c_uint32), ("space_code", ctypes.c_uint32)]
 
 
+TRANSDUCER_MAX_LAYERS = 4
+ACT_TANH = 5  # SBK_ACT_TANH (the transducer joint only)
+
+
+class TransducerWeights(ctypes.Structure):  # sbk_transducer_weights
+    _fields_ = [("emb_ih", c_void_p)] + [(n, c_void_p * TRANSDUCER_MAX_LAYERS) for n in ("w_ih", "w_hh", "b_ih", "b_hh")] + [
+        (n, c_void_p) for n in ("proj", "proj_b", "out", "out_b")] + [
+        (n, c_int32) for n in ("n_layers", "hidden", "joint", "vocab", "n_emb")]
+
+
+class TransducerConfig(ctypes.Structure):  # sbk_transducer_config
+    _fields_ = [(n, c_int32) for n in ("blank", "max_symbols_per_step", "start_from_blank", "frame_block", "act")]
+
+
 def _declare(lib):
     p, i, f = c_void_p, c_int, c_float
     sig = {
@@ -145,6 +159,9 @@ def _declare(lib):
         "sbk_ctc_greedy_decode_f32": ([p, p, p, p, i, i, i, i, p], c_int),
         "sbk_ctc_beam_search_workspace_bytes": ([i, i, i, i, i], ctypes.c_size_t),
         "sbk_ctc_beam_search_f32": ([p, p, p, i, POINTER(CTCBeamConfig), p, ctypes.c_size_t, p, p, p, i, i, i, p], c_int),
+        "sbk_transducer_greedy_f32": ([POINTER(TransducerWeights), POINTER(TransducerConfig), p, p, p, p, p, p, p, i, i, p],
+                                      c_int),
+        "sbk_lstm_f32": ([p, p, p, p, p, p, p, i, i, i, p], c_int),
         "sbk_beam_search_workspace_bytes": ([POINTER(DecoderWeights), POINTER(SearchConfig), i, i], ctypes.c_size_t),
         "sbk_beam_search_f32": ([POINTER(DecoderWeights), POINTER(SearchConfig), p, p, p, p, p, ctypes.c_size_t, p, p,
                                  p, p, p, p, p, POINTER(c_int32), i, i, p], c_int),
@@ -1559,6 +1576,95 @@ def ctc_beam_search(x, rel_len, table, n_vocab, cfg):
                                      c_void_p(ws.data_ptr() + off), nbytes, _p(paths), _p(scores), _p(count), B, T, V,
                                      _stream(x)), "sbk_ctc_beam_search_f32")
     return paths, scores, count
+
+
+# ------------------------------------------------------------------ transducer greedy decoding (csrc/transducer.hip)
+class TransducerPrepared:
+    """The prediction network, joint and classifier of a transducer in the layouts of sbk_transducer_weights (include/sbk.h):
+    the Embedding folded into layer 0's input weights (one sbk_gemm_nt_f32), the other matrices as they are.  Built once per
+    set of weights; the tensors are kept alive here for as long as the struct points at them."""
+
+    def __init__(self, emb, lstm_layers, proj_w, proj_b, out_w, out_b):
+        """emb [n_emb, E]; lstm_layers: [(w_ih [4H, in], w_hh [4H, H], b_ih or None, b_hh or None)] * L;
+        proj_w [J, H], proj_b [J] or None; out_w [V, J], out_b [V] or None (all fp32 on one device)."""
+        if not 1 <= len(lstm_layers) <= TRANSDUCER_MAX_LAYERS:
+            raise SbkError(f"transducer: {len(lstm_layers)} LSTM layers (1..{TRANSDUCER_MAX_LAYERS} supported)")
+        keep = []
+
+        def t(x):
+            if x is None:
+                return None
+            x = x.detach().float().contiguous()
+            keep.append(x)
+            return x
+
+        w_ih0 = lstm_layers[0][0].detach().float().contiguous()
+        with precision_scope("fp32"):
+            self.emb_ih = t(gemm_nt(emb.detach().float().contiguous(), w_ih0))  # [n_emb, 4H] = E . W_ih^T
+        W = TransducerWeights()
+        W.emb_ih = self.emb_ih.data_ptr()
+        for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(lstm_layers):
+            if l > 0:
+                W.w_ih[l] = t(w_ih).data_ptr()
+            W.w_hh[l] = t(w_hh).data_ptr()
+            W.b_ih[l] = None if b_ih is None else t(b_ih).data_ptr()
+            W.b_hh[l] = None if b_hh is None else t(b_hh).data_ptr()
+        W.proj = t(proj_w).data_ptr()
+        W.proj_b = None if proj_b is None else t(proj_b).data_ptr()
+        W.out = t(out_w).data_ptr()
+        W.out_b = None if out_b is None else t(out_b).data_ptr()
+        W.n_layers, W.hidden, W.joint = len(lstm_layers), lstm_layers[0][1].shape[1], proj_w.shape[0]
+        W.vocab, W.n_emb = out_w.shape[0], emb.shape[0]
+        self.W, self._keep, self.device = W, keep, self.emb_ih.device
+
+
+def lstm(x, layers, hx=None):
+    """torch.nn.LSTM(batch_first=True, unidirectional) on the device: x [B,T,in]; layers [(w_ih, w_hh, b_ih, b_hh)] * L;
+    hx (h0, c0) [L,B,H] or None -> (out [B,T,H], (h [L,B,H], c [L,B,H])).  Per layer: the input part of the gates for the
+    whole sequence with sbk_gemm_nt_f32, then the recurrence with sbk_lstm_f32."""
+    lib = load()
+    _f32(x)
+    B, T, _ = x.shape
+    L, H = len(layers), layers[0][1].shape[1]
+    if hx is None:
+        h = torch.zeros(L, B, H, dtype=torch.float32, device=x.device)
+        c = torch.zeros(L, B, H, dtype=torch.float32, device=x.device)
+    else:
+        h, c = (t.detach().float().contiguous().clone() for t in hx)
+    out = x.contiguous()
+    for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(layers):
+        with precision_scope("fp32"):
+            xp = gemm_nt(out, w_ih.detach().float().contiguous())
+        w_hh = w_hh.detach().float().contiguous()
+        b_ih = None if b_ih is None else b_ih.detach().float().contiguous()
+        b_hh = None if b_hh is None else b_hh.detach().float().contiguous()
+        y = torch.empty(B, T, H, dtype=torch.float32, device=x.device)
+        hl, cl = h[l], c[l]  # (contiguous views of the state)
+        _dev_ok(xp, w_hh, b_ih, b_hh, hl, cl, y)
+        _chk(lib.sbk_lstm_f32(_p(xp), _p(w_hh), _p(b_ih), _p(b_hh), _p(hl), _p(cl), _p(y), B, T, H, _stream(xp)),
+             "sbk_lstm_f32")
+        out = y
+    return out, (h, c)
+
+
+def transducer_greedy(prep: TransducerPrepared, tn, out_pn, h, c, blank, max_symbols_per_step=5, start_from_blank=True,
+                      act=ACT_GELU, frame_block=0):
+    """sbk_transducer_greedy_f32: tn [B,T,J] fp32; the state out_pn [B,J], h / c [L,B,H] is read (unless start_from_blank)
+    and overwritten in place with the final state.  -> (tokens [B, T*(S+1)] int32, count [B] int32, score [B] fp32)."""
+    lib = load()
+    _f32(tn)
+    B, T, J = tn.shape
+    tn = tn.contiguous()
+    _dev_ok(tn, out_pn, h, c)
+    cfg = TransducerConfig(blank=int(blank), max_symbols_per_step=int(max_symbols_per_step),
+                           start_from_blank=1 if start_from_blank else 0, frame_block=int(frame_block), act=int(act))
+    cap = T * (int(max_symbols_per_step) + 1)
+    tokens = torch.empty(B, max(cap, 1), dtype=torch.int32, device=tn.device)
+    count = torch.empty(B, dtype=torch.int32, device=tn.device)
+    score = torch.empty(B, dtype=torch.float32, device=tn.device)
+    _chk(lib.sbk_transducer_greedy_f32(ctypes.byref(prep.W), ctypes.byref(cfg), _p(tn), _p(out_pn), _p(h), _p(c), _p(tokens),
+                                       _p(count), _p(score), B, T, _stream(tn)), "sbk_transducer_greedy_f32")
+    return tokens, count, score
 
 
 # ------------------------------------------------------------------ HIP-event profiler
