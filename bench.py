@@ -3,6 +3,7 @@
 
     python bench.py --gpus 1 --steps 20 --warmup 5
     python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   # + the timed region's token ids as DIR/*.npy
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full   # + the secondary measurements (below), several minutes more
     python bench.py --gpus 8 --steps 20 --warmup 5      # spawns 8 ranks itself (torch.distributed.run, RCCL)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   # same thing
 
@@ -13,7 +14,7 @@ Random weights never emit EOS, so the number of decoding steps is fixed through 
 round(4 tokens/s * padded seconds).  fp32 arithmetic throughout.
 
 One "step" = 128 utterances through the whole path, as duration-sorted RECIPE-SIZED batches of at most 32
-utterances ("duration-sorted batches of <= 32 utts"); `value` is measured on those.  The same
+utterances ("duration-sorted batches of <= 32 utts"); `value` is measured on those.  With --full the same
 utterances are then run again as 128-utterance batches (sized for 288 GB of HBM) and reported as
 `value_batch128`.  Per rank the batches run through ConcurrentTranscriber: --streams worker threads (encoder on a
 normal-, search on a high-priority HIP stream), each encoding --group batches one after the other and decoding them
@@ -41,7 +42,11 @@ asynchronously every 8 steps).
 "value_fp32_mfma_contractions": the same job with every contraction on the fp32 MFMA instruction (the headline's large
 contractions run on the bf16 matrix pipe through the exact three-way operand split), for reference.
 
-One JSON line on rank 0: metric / value (total unpadded audio seconds / max-over-ranks wall time) plus
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line; everything else it can measure
+(secondary_measurements) runs only with --full: the secondary legs, the checks, the latency modes, the roofline objects and
+the CPU baseline.
+
+One JSON line on rank 0: metric / value (total unpadded audio seconds / max-over-ranks wall time); with --full also
 "roofline" (dominant kernel; HIP-event timing of every launch during an instrumented single-stream repetition of
 the same batches), "roofline_top3", "roofline_end_to_end", "cpu_baseline" (the oracle port of the reference's
 PyTorch-CPU path on B = 4 x 10 s, BASELINE.md section 3's CPU shape; child process with a timeout and a smaller
@@ -532,7 +537,7 @@ def roofline_entry(name, v, total_ms):
     return e
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=16, help="steps per GPU; one step = 128 utterances")
@@ -590,8 +595,40 @@ def main():
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed region, write the token ids it returned to DIR/*.npy (dump_outputs): the inputs are "
                          "seeded, so two builds run with the same arguments can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the secondary measurements (secondary_measurements): other batch sizes and "
+                         "precisions in processes of their own, latency modes, the Whisper encoder, the instrumented repetition "
+                         "(roofline, determinism_check, decode step probe), parity_check, configs[1] and the CPU baseline.  "
+                         "Without it a run sets up, warms up, times the steps, writes --dump-outputs and prints the line")
     ap.add_argument("--verbose", action="store_true")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def secondary_measurements(args, rank, world, dist_on):
+    """What a run measures besides the headline.  A plain run measures nothing else; --full adds every secondary measurement
+    that its own --no-* switch, the rank and the world size allow (the fp32-MFMA leg also needs the split-operand contractions
+    to be on, which only the loaded library can tell)."""
+    if not args.full or rank != 0:
+        return set()
+    todo = set()
+    if world == 1 and not dist_on and not args.no_extras:
+        if args.second_batch > 0:
+            todo.add("batch128")
+        if args.precision == "fp32":
+            todo |= {"bf16", "fp32mfma"}
+    if args.latency_runs > 0:
+        todo.add("latency")
+    if world == 1 and not args.no_extras:
+        todo |= {"whisper_encoder", "config1_encoder_S"}
+    if not args.no_roofline:
+        todo |= {"roofline", "parity_check"}
+    if world == 1 and not args.no_cpu_baseline:
+        todo.add("cpu_baseline")
+    return todo
+
+
+def main():
+    args = parse_args()
 
     def note(msg):
         if args.verbose:
@@ -923,14 +960,16 @@ def main():
         if args.dump_outputs:
             dump_outputs(args.dump_outputs, hyps)
 
+    # ---- everything below runs with --full only (secondary_measurements); a plain run prints the line here
+    todo = secondary_measurements(args, rank, world, dist_on)
+
     # ---- secondary legs (N = 1), EACH IN A PROCESS OF ITS OWN (the legs used to share the parent's caching-allocator
     # pools -- one per worker stream -- and the third leg measured 8.3 K where the same leg alone gives 11-12 K): the same
     # utterances as 128-utterance batches; the opt-in bf16 encoder GEMMs + token agreement with the fp32 run; every contraction
     # on the fp32 MFMA instruction (SBK_F32X3=0's path: the headline's large contractions run on the bf16 pipe)
-    extras = world == 1 and not dist_on and not args.no_extras
-    if extras:
+    if todo & {"batch128", "bf16", "fp32mfma"}:
         out["config"]["secondary_legs"] = "each in a process of its own (own allocator pools, worker streams and weight images)"
-    if extras and args.second_batch > 0:
+    if "batch128" in todo:
         r2 = child_leg("batch128")
         out[f"value_batch{args.second_batch}"] = r2.get("value")
         if "error" in r2:
@@ -940,7 +979,7 @@ def main():
             out["config"].setdefault("gpu_memory_reserved_gb", {})[f"batch{args.second_batch}_leg_own_process"] = r2["reserved_gb"]
             out["config"][f"workers_x_group_batch{args.second_batch}"] = r2["workers_x_group"]
         note(f"second run ({args.second_batch}-utterance batches): {r2.get('value')}")
-    if extras and args.precision == "fp32":
+    if "bf16" in todo:
         from speechbrain_amd.utils.metric_stats import token_error_rate
 
         r3 = child_leg("bf16")
@@ -955,7 +994,7 @@ def main():
                                       "everything else fp32; token error rate of its hypotheses against the fp32 run's on the "
                                       "same utterances (random-init weights: flat posteriors amplify every perturbation)")
         note(f"bf16 encoder GEMMs: {r3.get('value')}")
-    if extras and args.precision == "fp32" and native.F32X3:
+    if "fp32mfma" in todo and native.F32X3:
         r4 = child_leg("fp32mfma")
         out["value_fp32_mfma_contractions"] = r4.get("value")
         if "error" in r4:
@@ -966,7 +1005,7 @@ def main():
     # its own like the other secondary legs: measured inside this one -- 100 GB of cached blocks mapped, sixteen retired worker
     # streams -- every mode read 3-4 ms more than in a fresh process (27.5 against 22.9 ms for the persistent step,
     # profiles/r05_final_bench_first.json against profiles/r05_g_*.log)
-    if rank == 0 and args.latency_runs > 0:
+    if "latency" in todo:
         by_mode = None
         if world == 1 and not dist_on:
             r5 = child_leg("latency")
@@ -982,7 +1021,7 @@ def main():
         out["config"]["latency_case"] = "B=1, 10 s utterance, 40 decode steps"
 
     # ---- BASELINE.json configs[4] (stretch): Whisper large-v3 shaped encoder, random weights, 30-second chunks
-    if rank == 0 and world == 1 and not args.no_extras:
+    if "whisper_encoder" in todo:
         try:
             out["config5_whisper_encoder"] = whisper_encoder_leg(dev)
         except Exception as e:  # a secondary measurement must not take the headline down
@@ -990,7 +1029,7 @@ def main():
         note("whisper encoder leg done")
 
     # ---- rooflines: HIP events around every launch, rank 0's batches repeated on one stream
-    if rank == 0 and not args.no_roofline:
+    if "roofline" in todo:
         note("instrumented repetition (HIP events)")
         native.prof_reset()
         native.prof_enable(True)
@@ -1071,7 +1110,7 @@ def main():
     # padded batches.  The grouped search runs the decode GEMMs at other row counts (other kernels, another summation
     # order), so the output heads are peaked (x8, as in tests/: random-init posteriors are flat and any fp32 reassociation
     # flips a near-tie) for BOTH sides; the weights are restored afterwards
-    if rank == 0 and not args.no_roofline:
+    if "parity_check" in todo:
         sub, n_sub = [], 0
         for t in sorted(local_batches, key=lambda t: (t[1].numel(), t[0][0])):  # the smallest batches first: cheap, and several shapes
             sub.append(t)
@@ -1103,7 +1142,7 @@ def main():
             print(f"[bench] parity_check FAILED: {n_bad} of {n_sub} utterances differ", file=sys.stderr, flush=True)
 
     # ---- configs[1]: STFT + Fbank + CNN + Conformer-S encoder forward, 32 x 10 s
-    if rank == 0 and world == 1 and not args.no_extras:
+    if "config1_encoder_S" in todo:
         note("configs[1]: Conformer-S encoder")
         small = build_asr("S", vocab=5000, seed=0, beam_size=10, ctc_weight=0.4, device=str(dev))
         ws = (0.1 * torch.randn(32, 160000, generator=torch.Generator().manual_seed(1234))).to(dev)
@@ -1122,7 +1161,7 @@ def main():
                                     "ms_per_batch": round(ms, 3), "audio_sec_per_s": round(320.0 / (ms * 1e-3), 1)}
         del small
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if "cpu_baseline" in todo:
         note("cpu baseline (subprocess)")
         cpu = cpu_baseline_subprocess()
         ref_tokens = cpu.pop("tokens", None)

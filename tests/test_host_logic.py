@@ -264,6 +264,23 @@ def test_bench_dump_outputs(tmp_path, monkeypatch):
     assert np.array_equal(idx, np.load(tmp_path / "b" / "utterance_index.npy"))
 
 
+def test_bench_plain_run_measures_the_headline_only():
+    """bench.py without --full: no secondary measurement; with --full every one its own --no-* switches, the rank and the world
+    size allow, as before the option existed."""
+    import bench
+
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", "d"])
+    assert not plain.full and bench.secondary_measurements(plain, 0, 1, False) == set()
+    full = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    everything = {"batch128", "bf16", "fp32mfma", "latency", "whisper_encoder", "roofline", "parity_check", "config1_encoder_S",
+                  "cpu_baseline"}
+    assert bench.secondary_measurements(full, 0, 1, False) == everything
+    assert bench.secondary_measurements(full, 1, 2, True) == set()  # (rank 0 alone measures)
+    assert bench.secondary_measurements(full, 0, 2, True) == {"latency", "roofline", "parity_check"}
+    some = bench.parse_args(["--full", "--no-extras", "--no-cpu-baseline", "--latency-runs", "0"])
+    assert bench.secondary_measurements(some, 0, 1, False) == {"roofline", "parity_check"}
+
+
 def test_bench_traffic_rows_of_this_rounds_kernels_only(tmp_path):
     """bench.pmc_traffic: the `traffic` field of the roofline object is the PMC figure of THIS round's kernel as shipped or null --
     a row of an earlier round, and a row counted before a later change of the kernel's schedule ("superseded"), are quoted in

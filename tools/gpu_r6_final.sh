@@ -7,11 +7,11 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"; mkdir -p gpurun_out; export TMPDIR=/tmp
 R=$PWD
 {
   echo "== driver bench"
-  timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/r06_final_bench.json 2> gpurun_out/r06_final_bench.err
-  tail -c 600 gpurun_out/r06_final_bench.err
+  timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$TMPDIR/r06_final_bench.json" 2> "$TMPDIR/r06_final_bench.err"
+  tail -c 600 "$TMPDIR/r06_final_bench.err"
   python - <<'PY'
-import json
-d = json.loads(open("gpurun_out/r06_final_bench.json").read().strip().splitlines()[-1])
+import json, os
+d = json.loads(open(os.path.join(os.environ["TMPDIR"], "r06_final_bench.json")).read().strip().splitlines()[-1])
 keys = ["value", "ms_per_step", "value_batch128", "value_encoder_gemms_bf16", "value_fp32_mfma_contractions", "p50_latency_ms", "p50_latency_ms_by_mode",
         "decode_step_ms", "launches_per_decode_step"]
 print({k: d.get(k) for k in keys})

@@ -9,11 +9,11 @@ R=$PWD
   echo "== suite"; timeout 1500 python -m pytest tests/ -q -m gpu 2>&1 | tail -4
   echo "== smoke"; timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | cut -c1-200
   echo "== driver bench"
-  timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/r06_final3_bench.json 2> gpurun_out/r06_final3_bench.err
-  tail -c 600 gpurun_out/r06_final3_bench.err
+  timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$TMPDIR/r06_final3_bench.json" 2> "$TMPDIR/r06_final3_bench.err"
+  tail -c 600 "$TMPDIR/r06_final3_bench.err"
   python - <<'PY'
-import json
-d = json.loads(open("gpurun_out/r06_final3_bench.json").read().strip().splitlines()[-1])
+import json, os
+d = json.loads(open(os.path.join(os.environ["TMPDIR"], "r06_final3_bench.json")).read().strip().splitlines()[-1])
 keys = ["value", "ms_per_step", "value_batch128", "value_encoder_gemms_bf16", "value_fp32_mfma_contractions", "p50_latency_ms", "p50_latency_ms_by_mode",
         "decode_step_ms", "launches_per_decode_step"]
 print({k: d.get(k) for k in keys})
