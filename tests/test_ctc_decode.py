@@ -82,8 +82,9 @@ def test_ctc_beam_search_kernel_matches_reference(backend):
 
 
 def test_host_restatement_matches_reference():
-    """tests/ctc_host_ref.py (no reference code) against the reference's own outputs: the GPU tests use it as their
-    yardstick at shapes the fixtures do not cover."""
+    """tests/ctc_host_ref.py (no reference code) against the reference's own outputs: tests/test_decode_shapes.py and
+    tests/test_ctc_full_size_gpu.py use it as their yardstick at shapes the fixtures do not cover (wide vocabularies,
+    beams above 100, long inputs, a blank index other than 0)."""
     z, meta = _golden()
     stats = {"checked": 0, "total": 0}
     for i, case in enumerate(meta["beam"]):
