@@ -1040,7 +1040,57 @@ def golden_input_norm():
     print("  cases:", len(out) - 2)
 
 
+def golden_ctc_prefix():
+    """CTCPrefixScore (decoders/ctc.py:26-295) driven step by step in the two modes the model-level goldens never reach:
+    blank 3 / eos 1, and ctc_window_size 4 with an attention matrix per step.  B=2 (one ragged), T=40, V=20, beam 4, five
+    steps; stored: the inputs, the candidates chosen per step (indices into beam * V of every utterance), the attention
+    matrices and the REFERENCE's psi - psi_prev of every step.  Data only."""
+    print("== CTCPrefixScore step protocol: blank != 0, attention window")
+    from speechbrain.decoders.ctc import CTCPrefixScore
+
+    B, T, V, beam, steps = 2, 40, 20, 4, 5
+    g = torch.Generator().manual_seed(77)
+    logp = torch.log_softmax(2.0 * torch.randn(B, T, V, generator=g), -1)
+    enc_len = torch.tensor([T, 29])
+    out = {"logp": logp.numpy(), "enc_len": enc_len.numpy().astype(np.int32)}
+    peaks = [(18, 30), (3, 14), (12, 20), (9, 16), (22, 30)]  # left, right, both sides, both, left again
+    for mode, blank, eos, window in (("blank3_eos1", 3, 1, 0), ("window4", 0, 2, 4)):
+        ref = CTCPrefixScore(logp.clone(), enc_len.clone(), blank, eos, window)
+        n = B * beam
+        bos = 2 if mode == "blank3_eos1" else 1
+        inp, states = torch.full((n,), bos, dtype=torch.long), None
+        deltas, cands, attns = [], [], []
+        for step in range(steps):
+            attn = torch.softmax(torch.randn(n, T, generator=g), -1)
+            lo, hi = peaks[step]
+            attn[torch.arange(n), torch.randint(lo, hi + 1, (n,), generator=g)] = 1.0
+            attn[0, lo], attn[n - 1, hi] = 2.0, 2.0  # (the extremes are reached)
+            delta, memory = ref.forward_step(inp, states, None, attn if window > 0 else None)
+            lp = torch.log_softmax(3.0 * torch.randn(n, V, generator=g), -1)
+            comb = lp + 0.4 * delta
+            comb[delta <= -1e19] = -float("inf")
+            flat = comb.view(B, beam * V).clone()
+            if step == 0:
+                flat[:, V:] = -float("inf")
+            cand = flat.topk(beam, dim=-1).indices
+            if step == 2:  # a hypothesis repeats its last token
+                cand[0, 0] = (cand[0, 0] // V) * V + inp.view(B, beam)[0, cand[0, 0] // V]
+            assert bool((delta.reshape(B, beam * V).gather(1, cand) > -1e19).all())
+            states = ref.permute_mem(memory, cand)
+            inp = (cand % V).view(-1)
+            deltas.append(delta.numpy()), cands.append(cand.numpy()), attns.append(attn.numpy())
+        out[f"{mode}/cfg"] = np.array([blank, eos, window, beam], dtype=np.int32)
+        out[f"{mode}/bos"] = np.int32(bos)
+        out[f"{mode}/delta"], out[f"{mode}/cand"] = np.stack(deltas), np.stack(cands)
+        out[f"{mode}/attn"] = np.stack(attns).astype(np.float32)
+        print(f"  {mode}: live fraction per step", [round(float((d > -1e19).mean()), 2) for d in deltas])
+    np.savez_compressed(os.path.join(OUT, "ctc_prefix.npz"), **out)
+
+
 if __name__ == "__main__":
+    if "--ctc-prefix-only" in sys.argv:
+        golden_ctc_prefix()
+        sys.exit(0)
     if "--whisper-large-only" in sys.argv:
         golden_whisper_large_shape()
         sys.exit(0)
@@ -1096,4 +1146,5 @@ if __name__ == "__main__":
     golden_input_norm()
     golden_whisper_model()
     golden_whisper_large_shape()
+    golden_ctc_prefix()
     print("OK")

@@ -214,7 +214,33 @@ __global__ void __launch_bounds__(256) ctc_score_step_kernel(CtcStepArgs a, cons
   // every lane then reads the same address per frame (broadcast, conflict-free)
   float* tab = lds;
   int* segs = reinterpret_cast<int*>(lds + (size_t)T * BP);
-  {
+  const int u_begin = start - 1, u_end = end - 1;  // frame t uses table entry u = t-1
+  if (a.win) {
+    // An attention window may begin or end inside a scale segment and leave the segment's largest entry -- the one the
+    // prepared table is scaled by -- outside the scored frames; entries more than 126 bits below it were flushed to zero
+    // when that table was built, although they are all this step sums.  Rebuild the table from the unscaled block-float
+    // state, scaled per segment by the largest entry among the SCORED frames.
+    for (int i = threadIdx.x; i < nseg * BP; i += 256) {
+      const int seg = i / BP, j = i % BP;
+      int e = kNegE;
+      if (j0 + j < a.beam) {
+        const BF* row = st + (size_t)(b * a.beam + j0 + j) * T;
+        for (int u = max(seg * kSeg, u_begin); u < min((seg + 1) * kSeg, u_end); ++u)
+          if (row[u].mg > 0.0f) e = max(e, row[u].eg);
+      }
+      segs[i] = e;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < T * BP; i += 256) {
+      const int u = i / BP, j = i % BP;
+      float v = 0.0f;
+      if (j0 + j < a.beam && u >= u_begin && u < u_end) {
+        const BF s = st[(size_t)(b * a.beam + j0 + j) * T + u];
+        v = sbk::fast_ldexp(s.mg, (s.mg > 0.0f ? s.eg : kNegE) - segs[(u / kSeg) * BP + j]);
+      }
+      tab[i] = v;
+    }
+  } else {
     float4* dst = reinterpret_cast<float4*>(tab);
     for (int i = threadIdx.x; i < T * (BP / 4); i += 256)
       dst[i] = *reinterpret_cast<const float4*>(sg + ((size_t)b * T + i / (BP / 4)) * bp + j0 + 4 * (i % (BP / 4)));
@@ -245,7 +271,6 @@ __global__ void __launch_bounds__(256) ctc_score_step_kernel(CtcStepArgs a, cons
   // the NEXT chunk are requested before the current chunk is accumulated (two chunks in flight per lane).
   constexpr int CH = 16 / TPT < 8 ? 8 : 16 / TPT;
   static_assert(kSeg % CH == 0, "ctc_score_step: chunks must tile a scale segment");
-  const int u_begin = start - 1, u_end = end - 1;
   auto fetch = [&](float (&buf)[TPT][CH], int cb) {
 #pragma unroll
     for (int q = 0; q < CH; ++q) {
@@ -326,8 +351,8 @@ __global__ void __launch_bounds__(256) ctc_score_step_kernel(CtcStepArgs a, cons
 // The one token per hypothesis that repeats the prefix' last token uses phi = beta instead of
 // gamma (ctc.py:175-186): recompute that entry.  One wave per hypothesis, lanes over frames.
 __global__ void __launch_bounds__(64) ctc_same_token_kernel(CtcStepArgs a, const float* __restrict__ P,
-                                                            const float* __restrict__ sb, const int* __restrict__ se,
-                                                            float* __restrict__ psi_out) {
+                                                            const BF* __restrict__ st, const float* __restrict__ sb,
+                                                            const int* __restrict__ se, float* __restrict__ psi_out) {
   const int n = blockIdx.x, lane = threadIdx.x;
   if (a.step_ptr) a.prefix_len = a.step_ptr[0];
   const int b = n / a.beam, c = a.last_tok[n];
@@ -345,9 +370,12 @@ __global__ void __launch_bounds__(64) ctc_same_token_kernel(CtcStepArgs a, const
     E = 0;
   }
   for (int u = start - 1 + lane; u < end - 1; u += 64) {
-    const float term = sb[(size_t)n * T + u] * Pb[(size_t)(u + 1) * a.ldp + c];
+    // (with an attention window: the unscaled state, see ctc_score_step_kernel)
+    const float bt = a.win ? st[(size_t)n * T + u].mb : sb[(size_t)n * T + u];
+    const float term = bt * Pb[(size_t)(u + 1) * a.ldp + c];
     const int k = sbk::frexp_exp(term);
-    const int et = term > 0.0f ? se[((size_t)b * nseg + u / kSeg) * beam_pitch(a.beam) + n % a.beam] + k : kNegE;
+    const int eb = a.win ? st[(size_t)n * T + u].eb : se[((size_t)b * nseg + u / kSeg) * beam_pitch(a.beam) + n % a.beam];
+    const int et = term > 0.0f ? eb + k : kNegE;
     const float mt = sbk::fast_ldexp(term, -k);
     const int E2 = max(E, et);
     m = sbk::fast_ldexp(m, E - E2) + sbk::fast_ldexp(mt, et - E2);
@@ -388,15 +416,26 @@ __global__ void __launch_bounds__(256) ctc_combine_kernel(CtcStepArgs a, const f
 // Such affine maps compose associatively (lower-triangular A stays lower-triangular), so the T-step
 // recurrence becomes: each lane composes the maps of its own run of frames, a 6-step wave scan
 // composes the lane maps, and each lane replays its run from the scanned prefix.  Maps and states
-// are block-float: (a, c, d) * 2^ea, (v0, v1) * 2^ev, (nb, bl) * 2^e -- exact power-of-two scaling.
+// are block-float -- exact power-of-two scaling.  Every entry of a map carries its OWN exponent: over a
+// run of a few hundred frames the all-token path (a), the all-blank path (d) and the mixed paths (c, v0, v1)
+// drift apart by more than the 2^126 a shared exponent can span, and an entry flushed against its
+// neighbour is not negligible -- the next run may favour exactly that path (c2 * v0 against d2 * v1).
+// Only the two sides of ONE sum share an exponent, where the smaller side below 2^-126 is below rounding.
+// A state (nb, bl) * 2^e keeps a shared exponent: each frame re-seeds nb from phi and bl from nb.
 struct AMap {
   float a, c, d, v0, v1;
-  int ea, ev;
+  int ea, ec, ed, e0, e1;
 };
 struct AState {
   float nb, bl;
   int e;
 };
+__device__ __forceinline__ int clamp_e(int e) { return max(e, kNegE); }
+__device__ __forceinline__ void norm1(float& x, int& e) {
+  const int k = sbk::frexp_exp(x);
+  x = sbk::fast_ldexp(x, -k);
+  e = x > 0.0f ? clamp_e(e + k) : kNegE;
+}
 __device__ __forceinline__ void norm2(float& x, float& y, int& e) {
   const float m = fmaxf(x, y);
   const int k = sbk::frexp_exp(m);
@@ -404,23 +443,23 @@ __device__ __forceinline__ void norm2(float& x, float& y, int& e) {
   y = sbk::fast_ldexp(y, -k);
   e = m > 0.0f ? e + k : kNegE;
 }
-__device__ __forceinline__ void norm3(float& x, float& y, float& z, int& e) {
-  const float m = fmaxf(fmaxf(x, y), z);
-  const int k = sbk::frexp_exp(m);
-  x = sbk::fast_ldexp(x, -k);
-  y = sbk::fast_ldexp(y, -k);
-  z = sbk::fast_ldexp(z, -k);
-  e = m > 0.0f ? e + k : kNegE;
+// x * 2^ex += y * 2^ey (an exact zero takes part with the exponent of zero, whatever exponent it arrived with)
+__device__ __forceinline__ void bf_add(float& x, int& ex, float y, int ey) {
+  const int ax = x > 0.0f ? ex : kNegE, ay = y > 0.0f ? ey : kNegE;
+  const int E = max(ax, ay);
+  x = sbk::fast_ldexp(x, ax - E) + sbk::fast_ldexp(y, ay - E);
+  ex = E;
 }
-__device__ __forceinline__ int clamp_e(int e) { return max(e, kNegE); }
 // s' = M s
 __device__ __forceinline__ AState apply_map(const AMap& m, const AState& s) {
-  // A s has exponent ea + e; v has exponent ev
-  const int e1 = clamp_e(m.ea + s.e), e2 = m.ev;
-  const int E = max(e1, e2);
-  const float x = sbk::fast_ldexp(m.a * s.nb, e1 - E) + sbk::fast_ldexp(m.v0, e2 - E);
-  const float y = sbk::fast_ldexp(m.c * s.nb + m.d * s.bl, e1 - E) + sbk::fast_ldexp(m.v1, e2 - E);
-  AState r{x, y, E};
+  float x = m.a * s.nb, y = m.c * s.nb;
+  int ex = clamp_e(m.ea + s.e), ey = clamp_e(m.ec + s.e);
+  bf_add(x, ex, m.v0, m.e0);
+  bf_add(y, ey, m.d * s.bl, clamp_e(m.ed + s.e));
+  bf_add(y, ey, m.v1, m.e1);
+  const int ax = x > 0.0f ? ex : kNegE, ay = y > 0.0f ? ey : kNegE;
+  const int E = max(ax, ay);
+  AState r{sbk::fast_ldexp(x, ax - E), sbk::fast_ldexp(y, ay - E), E};
   norm2(r.nb, r.bl, r.e);
   return r;
 }
@@ -428,32 +467,44 @@ __device__ __forceinline__ AState apply_map(const AMap& m, const AState& s) {
 __device__ __forceinline__ AMap compose(const AMap& m2, const AMap& m1) {
   AMap r;
   r.a = m2.a * m1.a;
-  r.d = m2.d * m1.d;
-  r.c = m2.c * m1.a + m2.d * m1.c;
   r.ea = clamp_e(m2.ea + m1.ea);
-  norm3(r.a, r.c, r.d, r.ea);
-  const int e1 = clamp_e(m2.ea + m1.ev), e2 = m2.ev;
-  const int E = max(e1, e2);
-  r.v0 = sbk::fast_ldexp(m2.a * m1.v0, e1 - E) + sbk::fast_ldexp(m2.v0, e2 - E);
-  r.v1 = sbk::fast_ldexp(m2.c * m1.v0 + m2.d * m1.v1, e1 - E) + sbk::fast_ldexp(m2.v1, e2 - E);
-  r.ev = E;
-  norm2(r.v0, r.v1, r.ev);
+  norm1(r.a, r.ea);
+  r.d = m2.d * m1.d;
+  r.ed = clamp_e(m2.ed + m1.ed);
+  norm1(r.d, r.ed);
+  r.c = m2.c * m1.a;
+  r.ec = clamp_e(m2.ec + m1.ea);
+  bf_add(r.c, r.ec, m2.d * m1.c, clamp_e(m2.ed + m1.ec));
+  norm1(r.c, r.ec);
+  r.v0 = m2.a * m1.v0;
+  r.e0 = clamp_e(m2.ea + m1.e0);
+  bf_add(r.v0, r.e0, m2.v0, m2.e0);
+  norm1(r.v0, r.e0);
+  r.v1 = m2.c * m1.v0;
+  r.e1 = clamp_e(m2.ec + m1.e0);
+  bf_add(r.v1, r.e1, m2.d * m1.v1, clamp_e(m2.ed + m1.e1));
+  bf_add(r.v1, r.e1, m2.v1, m2.e1);
+  norm1(r.v1, r.e1);
   return r;
 }
 __device__ __forceinline__ AMap frame_map(float pc, float pb, float mphi, int ephi) {
   AMap m;
   m.a = pc;
-  m.c = pb;
-  m.d = pb;
   m.ea = 0;
-  norm3(m.a, m.c, m.d, m.ea);
-  m.v0 = pc * mphi;
+  norm1(m.a, m.ea);
+  m.c = pb;
+  m.ec = 0;
+  norm1(m.c, m.ec);
+  m.d = m.c;
+  m.ed = m.ec;
+  m.v0 = m.a * mphi;
+  m.e0 = clamp_e(m.ea + ephi);
+  norm1(m.v0, m.e0);
   m.v1 = 0.0f;
-  m.ev = ephi;
-  norm2(m.v0, m.v1, m.ev);
+  m.e1 = kNegE;
   return m;
 }
-__device__ __forceinline__ AMap identity_map() { return AMap{1.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0, kNegE}; }
+__device__ __forceinline__ AMap identity_map() { return AMap{1.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0, kNegE, 0, kNegE, kNegE}; }
 __device__ __forceinline__ AMap shfl_up_map(const AMap& m, int delta, int lane) {
   const int src = max(lane - delta, 0);
   AMap r;
@@ -463,7 +514,10 @@ __device__ __forceinline__ AMap shfl_up_map(const AMap& m, int delta, int lane) 
   r.v0 = sbk::shfl(m.v0, src);
   r.v1 = sbk::shfl(m.v1, src);
   r.ea = sbk::shfl(m.ea, src);
-  r.ev = sbk::shfl(m.ev, src);
+  r.ec = sbk::shfl(m.ec, src);
+  r.ed = sbk::shfl(m.ed, src);
+  r.e0 = sbk::shfl(m.e0, src);
+  r.e1 = sbk::shfl(m.e1, src);
   return r;
 }
 
@@ -756,7 +810,8 @@ int ctc_psi_step(const float* P, const float* state, const int32_t* last_tok, co
 #undef SBK_CTC_LAUNCH_NT
   int rc = launch_status("ctc_score_step");
   if (rc) return rc;
-  SBK_LAUNCH(ctc_same_token_kernel, dim3(B * beam), dim3(64), 0, st, a, P, (const float*)v.sb, (const int*)v.se, psi);
+  SBK_LAUNCH(ctc_same_token_kernel, dim3(B * beam), dim3(64), 0, st, a, P, (const BF*)v.st, (const float*)v.sb,
+             (const int*)v.se, psi);
   return launch_status("ctc_same_token");
 }
 
