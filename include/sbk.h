@@ -60,12 +60,40 @@ size_t sbk_prof_report(char* buf, size_t cap);
 int sbk_prof_gemm_repeat_f32(const float* A, const float* W, float* C, int M, int N, int K, float* workspace,
                              size_t workspace_floats, int iters, float* us_per_launch, sbk_stream_t stream);
 
-/* Measurement: phase time stamps (100 MHz ticks) of the most recent persistent few-row decoding step launched with knob 49 set
+/* Measurement: phase time stamps (100 MHz ticks) of the most recent persistent few-row decoding step launched with SBK_KNOB_PERSIST_STAMPS set
  * (csrc/decoder_persist.hip): [start, (end of phase, end of barrier) x barriers, end] of workgroup 0.  Synchronises the device;
  * returns the number of stamps written to the HOST array `out`.  tools/latency_probe.py --stamps prints them. */
 int sbk_prof_persist_stamps(long long* out, int cap);
 
-/* tuning knobs for experiments (key 1: K chunks per fetch batch of the skinny GEMM, 0 = automatic) */
+/* Tuning switches for experiments and tests: route selectors that let a small shape reach a kernel, and the A/B switches of
+ * defaults that are still open questions.  Process-wide; each default and the measurement behind it stand at the variable's
+ * definition in csrc/.  speechbrain_amd.native.knobs(name=value, ...) sets them by name for the length of a `with` block. */
+enum sbk_knob {
+  SBK_KNOB_SKINNY_OFF = 2,       /* 1 = few-row GEMMs take the LDS-tiled kernels instead of the skinny ones */
+  SBK_KNOB_CROSS_ROWS = 4,       /* decode-step cross-attention: 7 = ring / MFMA kernel from 128 (utterance, head) pairs on, 5 = always, 0 = never */
+  SBK_KNOB_CROSS_FC256 = 8,      /* cross-attention memory frames per workgroup (1 = 256, 2 = 64, 0 = 128); 3 = ring kernel as one run per utterance */
+  SBK_KNOB_TILED_SPLITK = 14,    /* rows from which K >= 2048 few-row shapes take 64 x 64 tiles with a 4-way K split (0 = off) */
+  SBK_KNOB_SK_MODE = 18,         /* persistent stream-K GEMM: 0 = never, 1 = routed by shape, 2 = always, 3 = always from 8 tiles on */
+  SBK_KNOB_SK_MIN_ROWS = 24,     /* fewer rows than this never take the persistent GEMM in routed mode */
+  SBK_KNOB_X3_ROUTE_ROWS = 34,   /* rows from which the searches' projections take sbk_gemm_nt_f32x3 */
+  SBK_KNOB_X3_ROUTE_TILES = 35,  /* ... and the 128 x 128 tiles from which they do */
+  SBK_KNOB_SCORE_FUSED = 40,     /* 1 = a decoding step's scoring as one pass per hypothesis row, 0 = separate launches */
+  SBK_KNOB_X3R_MODE = 41,        /* decode-step projections on gemm_x3r: 0 = off, otherwise on (3 = always the rolled step loop) */
+  SBK_KNOB_X3R_MIN_ROWS = 42,    /* hypothesis rows from which the search routes a projection to gemm_x3r */
+  SBK_KNOB_X3R_LN = 45,          /* LayerNorm in gemm_x3r's prologue: 0 = a launch of its own, 1 = fused (narrow vocabularies), 2 = always */
+  SBK_KNOB_PERSIST = 47,         /* persistent few-row decoding step: 0 = off, 1 = cooperative launch, 2 = plain launch */
+  SBK_KNOB_PERSIST_GRID = 48,    /* workgroups of the persistent step's launch */
+  SBK_KNOB_PERSIST_STAMPS = 49,  /* 1 = the persistent step records phase time stamps (sbk_prof_persist_stamps) */
+  SBK_KNOB_X3R_XC = 51,          /* gemm_x3r: column groups among the XCDs (1 / 2 / 4 / 8; 0 = automatic) */
+  SBK_KNOB_NT_MASK = 53,         /* non-temporal loads: bit 0 = ring K tiles, 1 = ring V tiles, 2 = CTC posteriors */
+  SBK_KNOB_SELF_ANC = 55,        /* 1 = decode-step self-attention over the beams' shared ancestry */
+  SBK_KNOB_X3R_PAIR = 58,        /* gemm_x3r operand loads of two k steps together: bit 0 = plain kernel, 1 = LayerNorm-prologue kernel */
+  SBK_KNOB_PERSIST_TREE = 59,    /* 1 = two-level arrival counters in the persistent step's grid barrier, 0 = one counter */
+  SBK_KNOB_ATTN_EXP2 = 60,       /* 1 = the relative-position attention's softmax weights as 2^x on v_exp_f32, 0 = expf */
+  SBK_KNOB_LP256 = 61,           /* 256 x 256-tile bf16 / fp8 GEMM: 0 = never, 1 = from 128 tiles on, 2 = always */
+  SBK_KNOB_X3P_FAST_EPI = 63     /* 1 = gemm_nt_x3p's hot epilogue forms as straight-line code, 0 = the generic form always */
+};
+/* an unknown key is ignored */
 void sbk_prof_set_knob(int key, int value);
 /* ABI 11: the current value of a switch (INT_MIN for an unknown key), so that an experiment or a test can restore what it found */
 int sbk_prof_get_knob(int key);

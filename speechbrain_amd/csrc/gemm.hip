@@ -1414,47 +1414,6 @@ extern "C" int sbk_prof_gemm_repeat_f32(const float* A, const float* W, float* C
   return rc;
 }
 
-// the tuning / measurement switch behind a key (nullptr: no such key)
-static int* knob_slot(int key) {
-  switch (key) {
-    case 2: return &sbk::g_skinny_off;
-    case 4: return &sbk::g_cross_rows;
-    case 8: return &sbk::g_cross_fc256;
-    case 14: return &sbk::g_tiled_splitk;
-    case 18: return &sbk::g_sk_mode;
-    case 24: return &sbk::g_sk_min_rows;
-    case 34: return &sbk::g_x3_route_rows;
-    case 35: return &sbk::g_x3_route_tiles;
-    case 40: return &sbk::g_score_fused;
-    case 41: return &sbk::g_x3r_mode;
-    case 42: return &sbk::g_x3r_min_rows;
-    case 45: return &sbk::g_x3r_ln;
-    case 47: return &sbk::g_persist;
-    case 48: return &sbk::g_persist_grid;
-    case 49: return &sbk::g_persist_stamps;
-    case 51: return &sbk::g_x3r_xc;
-    case 53: return &sbk::g_nt_mask;
-    case 54: return &sbk::g_x3r_probe;
-    case 55: return &sbk::g_self_anc;
-    case 58: return &sbk::g_x3r_pair;
-    case 59: return &sbk::g_persist_tree;
-    case 60: return &sbk::g_attn_exp2;
-    case 61: return &sbk::g_lp256;
-    case 62: return &sbk::g_lp256_mode;
-    case 63: return &sbk::g_x3p_fast_epi;
-    case 64: return &sbk::g_x3p_mode;
-    default: return nullptr;
-  }
-}
-extern "C" void sbk_prof_set_knob(int key, int value) {
-  if (int* p = knob_slot(key)) *p = value;
-}
-// current value of a switch (a test restores what it found); INT_MIN for an unknown key
-extern "C" int sbk_prof_get_knob(int key) {
-  const int* p = knob_slot(key);
-  return p ? *p : (-2147483647 - 1);
-}
-
 
 // ---- fp32 contraction on the bf16 matrix pipe (exact three-way operand split) ----------------------------------
 extern "C" int sbk_split_bf16x3(const float* W, int ldw, uint16_t* W3, int N, int K, sbk_stream_t stream) {

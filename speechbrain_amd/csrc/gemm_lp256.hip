@@ -56,14 +56,11 @@ constexpr int kStgPitch = 72, kStgF = 16 * kStgPitch;  // a wave's epilogue stag
 static_assert(8 * kStgF <= kSlotF, "the staging area is one slot");
 constexpr size_t kLdsBytes = (size_t)2 * kSlotF * sizeof(float);
 
-// MODE: 0 = the kernel.  Measurement builds (key 62, tools/microbench.py --lp256-modes; results are garbage, timings are what they are
-// for): bit 0 = no LDS-DMA after a tile's first two K tiles, 1 = no MFMAs, 2 = no epilogue, 3 = no fragment fetches.  Schedule variants
-// (same results): bit 4 = the wave raises its priority for its MFMA phase, bit 5 = the LDS reads are awaited AFTER the phase barrier
-// (group 1 in the second half of a K tile keeps the early wait: those reads are the last ones of the slot the other group refills
-// behind that barrier).
-template <bool FP8, int MODE, int ACT>
+// (Measured in round 6 with builds since removed -- the bf16 kernel without its LDS-DMA after a tile's first two K tiles, without its
+// MFMAs, without its epilogue, without its fragment fetches; and two schedule variants with the same results: the wave raising its
+// priority for its MFMA phase, and the LDS reads awaited AFTER the phase barrier: DESIGN.md section 5, profiles/r06_z_*.)
+template <bool FP8, int ACT>
 __global__ void __launch_bounds__(512, 2) gemm_nt_lp256_kernel(sbk::Lp256Args s) {
-  constexpr bool kNoDma = MODE & 1, kNoMfma = MODE & 2, kNoEpi = MODE & 4, kNoFetch = MODE & 8, kPrio = MODE & 16, kLateDrain = MODE & 32;
   SBK_DYN_LDS(float, lds);  // [2 slots][A 256 rows | W 256 rows][128 bytes]  (ONE LDS object)
   const unsigned char* const gA = s.A;
   const unsigned char* const gW = s.W;
@@ -144,15 +141,6 @@ __global__ void __launch_bounds__(512, 2) gemm_nt_lp256_kernel(sbk::Lp256Args s)
   // ---- fragments of one step (64 bytes of every row of the wave's 128 + 64 rows): 12 ds_read_b128, 48 registers
   using Frag = std::conditional_t<FP8, uint4, sbk::bf16x8>;
   Frag fa[2][4], fw[2][2];  // [16-byte piece][sub-tile]: bf16 = k step (8 k per lane), fp8 = low / high half of the lane's 32 bytes
-  if constexpr (kNoFetch) {  // (defined operands the optimiser cannot see through)
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) fa[p][i] = sbk::opaque_zero<Frag>();
-#pragma unroll
-      for (int jj = 0; jj < 2; ++jj) fw[p][jj] = sbk::opaque_zero<Frag>();
-    }
-  }
   auto fetch = [&](int slot, int h) SBK_INLINE_LAMBDA {
     const float* sa = lds + slot * kSlotF + (wrow0 + lrow) * kRowF;
     const float* sb = lds + slot * kSlotF + kPanelF + (wcol0 + lrow) * kRowF;
@@ -168,15 +156,7 @@ __global__ void __launch_bounds__(512, 2) gemm_nt_lp256_kernel(sbk::Lp256Args s)
     }
   };
   auto multiply = [&]() SBK_INLINE_LAMBDA {
-    if constexpr (kNoMfma) {  // (the fetched fragments stay live)
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) sbk::keep(fa[p][i]);
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) sbk::keep(fw[p][jj]);
-      }
-    } else if constexpr (FP8) {
+    if constexpr (FP8) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -341,42 +321,29 @@ __global__ void __launch_bounds__(512, 2) gemm_nt_lp256_kernel(sbk::Lp256Args s)
       const int slot = n & 1;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        if constexpr (!kNoDma) {
-          if (h == 0) {
-            if (m + 1 < KT) {
-              issue(m + 1, slot ^ 1);
-            } else if (ord + 1 < ntile) {  // (this tile's last K tile was issued a K tile ago: the loader moves on to the next tile)
-              setup(t + t_stride);
-              issue(0, slot ^ 1);
-            }
+        if (h == 0) {
+          if (m + 1 < KT) {
+            issue(m + 1, slot ^ 1);
+          } else if (ord + 1 < ntile) {  // (this tile's last K tile was issued a K tile ago: the loader moves on to the next tile)
+            setup(t + t_stride);
+            issue(0, slot ^ 1);
           }
         }
-        if constexpr (!kNoFetch) fetch(slot, h);
-        const bool early = !kLateDrain || (h == 1 && group == 1);  // (uniform)
-        if (early) sbk::lds_drain();
+        fetch(slot, h);
+        sbk::lds_drain();
         if (h == 1) sbk::vm_drain();
         phase_barrier();
-        if (!early) sbk::lds_drain();
-        if constexpr (kPrio) sbk::set_prio<1>();
         multiply();
-        if constexpr (kPrio) sbk::set_prio<0>();
         phase_barrier();
       }
     }
     if (group == 0) sbk::block_barrier_raw();
     // both groups aligned, nobody reads the slot of this tile's last K tile any more: it is the epilogue's staging area (the other slot
     // holds the next tile's first K tile, landed and published above)
-    if constexpr (kNoEpi) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) sbk::pin(acc[i][jj]);
-    } else {
-      epilogue(t, (n - 1) & 1);
-      // (the epilogue's stores retired in the compiler's books too: see vm_drain_visible.  The next tile's first K tile landed before
-      // the epilogue; what this waits for is the stores' acknowledgement -- measured neutral against not waiting, visits AA / AB)
-      sbk::vm_drain_visible();
-    }
+    epilogue(t, (n - 1) & 1);
+    // (the epilogue's stores retired in the compiler's books too: see vm_drain_visible.  The next tile's first K tile landed before
+    // the epilogue; what this waits for is the stores' acknowledgement -- measured neutral against not waiting, visits AA / AB)
+    sbk::vm_drain_visible();
     zero();
     if (ord + 1 < ntile) {
       sbk::lds_drain();
@@ -386,7 +353,7 @@ __global__ void __launch_bounds__(512, 2) gemm_nt_lp256_kernel(sbk::Lp256Args s)
   }
 }
 
-template <bool FP8, int MODE, int ACT>
+template <bool FP8, int ACT>
 int launch_lp256(const sbk::Lp256Args& a0, hipStream_t st) {
   sbk::Lp256Args a = a0;
   a.tiles_m = sbk::cdiv(a.M, 256);
@@ -403,10 +370,10 @@ int launch_lp256(const sbk::Lp256Args& a0, hipStream_t st) {
   }
   static bool once = false;
   if (!once) {
-    (void)SBK_ALLOW_DYN_LDS((gemm_nt_lp256_kernel<FP8, MODE, ACT>), kLdsBytes);
+    (void)SBK_ALLOW_DYN_LDS((gemm_nt_lp256_kernel<FP8, ACT>), kLdsBytes);
     once = true;
   }
-  SBK_LAUNCH((gemm_nt_lp256_kernel<FP8, MODE, ACT>), dim3((unsigned)G), dim3(512), kLdsBytes, st, a);
+  SBK_LAUNCH((gemm_nt_lp256_kernel<FP8, ACT>), dim3((unsigned)G), dim3(512), kLdsBytes, st, a);
   return sbk::launch_status(FP8 ? "sbk_gemm_nt_fp8a" : "sbk_gemm_nt_bf16a");
 }
 
@@ -427,26 +394,18 @@ bool lp256_routed(const Lp256Args& a) {
   // (6 000 x 1 280 x 1 280, 120 tiles: 41 against 80 us)
   return (long)cdiv(a.M, 256) * cdiv(a.N, 256) >= ((a.C && a.R) ? 96 : 128);
 }
-int g_lp256_mode = 0;  // key 62: MODE of gemm_nt_lp256_kernel (bf16 operands only; measurement builds 1 / 2 / 4 / 8, schedule variants 16 / 32 / 48)
 int gemm_nt_lp256(const Lp256Args& a, bool fp8, hipStream_t st) {
   if (fp8) {
     switch (a.act) {
-      case SBK_ACT_GELU: return launch_lp256<true, 0, SBK_ACT_GELU>(a, st);
-      case SBK_ACT_SWISH: return launch_lp256<true, 0, SBK_ACT_SWISH>(a, st);
-      default: return launch_lp256<true, 0, SBK_ACT_NONE>(a, st);
+      case SBK_ACT_GELU: return launch_lp256<true, SBK_ACT_GELU>(a, st);
+      case SBK_ACT_SWISH: return launch_lp256<true, SBK_ACT_SWISH>(a, st);
+      default: return launch_lp256<true, SBK_ACT_NONE>(a, st);
     }
   }
-  if (a.act == SBK_ACT_GELU) return launch_lp256<false, 0, SBK_ACT_GELU>(a, st);
-  if (a.act == SBK_ACT_SWISH) return launch_lp256<false, 0, SBK_ACT_SWISH>(a, st);
-  switch (g_lp256_mode) {
-    case 1: return launch_lp256<false, 1, SBK_ACT_NONE>(a, st);
-    case 2: return launch_lp256<false, 2, SBK_ACT_NONE>(a, st);
-    case 4: return launch_lp256<false, 4, SBK_ACT_NONE>(a, st);
-    case 8: return launch_lp256<false, 8, SBK_ACT_NONE>(a, st);
-    case 16: return launch_lp256<false, 16, SBK_ACT_NONE>(a, st);
-    case 32: return launch_lp256<false, 32, SBK_ACT_NONE>(a, st);
-    case 48: return launch_lp256<false, 48, SBK_ACT_NONE>(a, st);
-    default: return launch_lp256<false, 0, SBK_ACT_NONE>(a, st);
+  switch (a.act) {
+    case SBK_ACT_GELU: return launch_lp256<false, SBK_ACT_GELU>(a, st);
+    case SBK_ACT_SWISH: return launch_lp256<false, SBK_ACT_SWISH>(a, st);
+    default: return launch_lp256<false, SBK_ACT_NONE>(a, st);
   }
 }
 }  // namespace sbk

@@ -40,7 +40,6 @@ using sbk::f32x16;
 
 namespace sbk {
 int g_x3p_fast_epi = 1;  // key 63
-int g_x3p_mode = 0;  // key 64
 // csrc/gemm.hip: the caller-registered stream workspace (slabs of kX3pSlabFloats floats each, tile tickets)
 bool stream_ws(hipStream_t st, float** slabs, int** cnt);
 int device_cus();
@@ -113,11 +112,10 @@ struct X3pArgs {
 };
 
 // WM x WN waves (= 8), each TM x TN sub-tiles of 32 x 32.
-// MODE: 0 = the kernel; measurement builds (key 64, tools/microbench.py --x3p-modes; garbage results): bit 0 = no LDS-DMA after a
-// segment's first two stages, 1 = no MFMAs, 2 = no epilogue, 3 = no fragment fetches.
-template <int WM, int WN, int TM, int TN, int MODE>
+// (Measured in round 6 with builds since removed -- the kernel without its LDS-DMA after a segment's first two stages, without its
+// MFMAs, without its epilogue, without its fragment fetches: profiles/r06_ae_*.)
+template <int WM, int WN, int TM, int TN>
 __global__ void __launch_bounds__(512, 2) gemm_nt_x3p_kernel(X3pArgs s) {
-  constexpr bool kNoDma = MODE & 1, kNoMfma = MODE & 2, kNoEpi = MODE & 4, kNoFetch = MODE & 8;
   static_assert(WM * WN == 8, "eight waves: two per SIMD, half a stage apart");
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   constexpr int RBA = BM / 64, RBW = BN / 64;            // row blocks (chunks of 64 rows) of the A / W panels of a tile
@@ -243,15 +241,6 @@ __global__ void __launch_bounds__(512, 2) gemm_nt_x3p_kernel(X3pArgs s) {
   const int wbase = (NPA + (wcol0 >> 6) * 6 + half) * kChunkFloats + lrow * 4;
 
   sbk::bf16x8 af[3][TM], wf[3][TN];
-  if constexpr (kNoFetch) {
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i) af[p][i] = sbk::opaque_zero<sbk::bf16x8>();
-#pragma unroll
-      for (int jj = 0; jj < TN; ++jj) wf[p][jj] = sbk::opaque_zero<sbk::bf16x8>();
-    }
-  }
   auto fetch = [&](int slot) SBK_INLINE_LAMBDA {
     const float* sa = lds + slot * STAGE + abase;
     const float* sw = lds + slot * STAGE + wbase;
@@ -268,16 +257,6 @@ __global__ void __launch_bounds__(512, 2) gemm_nt_x3p_kernel(X3pArgs s) {
     // smallest terms first; consecutive MFMAs go to different accumulators.  W is the FIRST operand: a lane owns one row m
     // of C and registers 4g .. 4g+3 hold four consecutive columns (16-byte epilogue vectors), as in gemm_nt_sk_kernel<X3>
     constexpr int PW_[6] = {0, 2, 1, 0, 1, 0}, PA_[6] = {2, 0, 1, 1, 0, 0};  // (W piece, A piece): hi.lo lo.hi mid.mid hi.mid mid.hi hi.hi
-    if constexpr (kNoMfma) {
-#pragma unroll
-      for (int p = 0; p < 3; ++p) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i) sbk::keep(af[p][i]);
-#pragma unroll
-        for (int jj = 0; jj < TN; ++jj) sbk::keep(wf[p][jj]);
-      }
-      return;
-    }
 #pragma unroll
     for (int t = 0; t < 6; ++t)
 #pragma unroll
@@ -523,17 +502,10 @@ __global__ void __launch_bounds__(512, 2) gemm_nt_x3p_kernel(X3pArgs s) {
         if (tid == 0) sbk::atomic_store_agent(cnt + tile, 0);  // re-armed for the next launch on this stream
       }
     }
-    if constexpr (kNoEpi) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int jj = 0; jj < TN; ++jj) sbk::pin(acc[i][jj]);
-    } else {
-      if (store) epilogue(tile);
-      // (the epilogue's stores retired in the compiler's books as well: with stores "in flight" it put an s_waitcnt vmcnt(0) of its own
-      // behind the LDS-DMA issue of every stage -- sbk::vm_drain_visible; the segment start waits for everything anyway)
-      sbk::vm_drain_visible();
-    }
+    if (store) epilogue(tile);
+    // (the epilogue's stores retired in the compiler's books as well: with stores "in flight" it put an s_waitcnt vmcnt(0) of its own
+    // behind the LDS-DMA issue of every stage -- sbk::vm_drain_visible; the segment start waits for everything anyway)
+    sbk::vm_drain_visible();
   };
 
   // the barrier between two phases.  The scheduling fences pin it: MFMAs touch no memory, so the scheduler would otherwise
@@ -560,12 +532,10 @@ __global__ void __launch_bounds__(512, 2) gemm_nt_x3p_kernel(X3pArgs s) {
     for (int n = 0; n < ns; ++n) {
       // ---- fetch phase (the SIMD's other wave multiplies meanwhile)
       const int slot = n % 3;
-      if constexpr (!kNoDma) {
-        if (n + 2 < ns) issue(lo + n + 2, (n + 2) % 3);  // its slot was last read in stage n - 1: two barriers ago for both groups
-      }
-      if constexpr (!kNoFetch) fetch(slot);
+      if (n + 2 < ns) issue(lo + n + 2, (n + 2) % 3);  // its slot was last read in stage n - 1: two barriers ago for both groups
+      fetch(slot);
       sbk::lds_drain();
-      if (!kNoDma && n + 2 < ns) {
+      if (n + 2 < ns) {
         wait_keep_one_stage();  // this wave's share of stage n + 1 has landed (stage n + 2 may fly on)
       } else {
         sbk::vm_drain();
@@ -590,7 +560,7 @@ __global__ void __launch_bounds__(512, 2) gemm_nt_x3p_kernel(X3pArgs s) {
   }
 }
 
-template <int WM, int WN, int TM, int TN, int MODE>
+template <int WM, int WN, int TM, int TN>
 int launch_x3p(const X3pArgs& a0, hipStream_t st) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   constexpr size_t lds = (size_t)3 * ((BM / 64 + BN / 64) * 6) * kChunk;
@@ -612,10 +582,10 @@ int launch_x3p(const X3pArgs& a0, hipStream_t st) {
   }
   static bool once = false;
   if (!once) {
-    (void)SBK_ALLOW_DYN_LDS((gemm_nt_x3p_kernel<WM, WN, TM, TN, MODE>), lds);
+    (void)SBK_ALLOW_DYN_LDS((gemm_nt_x3p_kernel<WM, WN, TM, TN>), lds);
     once = true;
   }
-  SBK_LAUNCH((gemm_nt_x3p_kernel<WM, WN, TM, TN, MODE>), dim3((unsigned)G), dim3(512), lds, st, a);
+  SBK_LAUNCH((gemm_nt_x3p_kernel<WM, WN, TM, TN>), dim3((unsigned)G), dim3(512), lds, st, a);
   return sbk::launch_status("sbk_gemm_nt_x3p");
 }
 
@@ -638,13 +608,7 @@ int gemm_nt_x3p(const uint16_t* PA, const uint16_t* PW, const float* bias, const
   // algorithmic bytes: both operand images once (6 B per element) + the result (+ the residual)
   const double bytes = 6.0 * ((double)M * K + (double)N * K) + (C ? 4.0 : 0.0) * M * N + (PC ? 6.0 : 0.0) * M * N + (R ? 4.0 : 0.0) * M * N;
   ProfScope prof("gemm_nt_x3p", flops, bytes, st);
-  switch (g_x3p_mode) {  // key 64: measurement builds
-    case 1: return launch_x3p<4, 2, 2, 2, 1>(a, st);
-    case 2: return launch_x3p<4, 2, 2, 2, 2>(a, st);
-    case 4: return launch_x3p<4, 2, 2, 2, 4>(a, st);
-    case 8: return launch_x3p<4, 2, 2, 2, 8>(a, st);
-    default: return launch_x3p<4, 2, 2, 2, 0>(a, st);
-  }
+  return launch_x3p<4, 2, 2, 2>(a, st);
 }
 }  // namespace sbk
 

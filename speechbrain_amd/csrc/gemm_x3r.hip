@@ -309,18 +309,9 @@ __global__ void __launch_bounds__(256, 2) gemm_x3r_kernel(X3rArgs g) {
 // 13.3 us at N = K = 512, 13.9 against 13.1 with the LayerNorm prologue, 33.8 against 34.8 at K = 2 048 -- the long-K projection is not
 // waiting for its chain: 160 workgroups pull 205 MB of operand fragments out of L2 in 34 us, 6 TB/s --, 41.5 against 30.9 at N = 2 048;
 // the step 1.72 ms either way with N <= 512 routed to it, the headline 11.8-11.9 against 12.0 K.  Removed; profiles/r06_k_*.)
-// MEASUREMENT ONLY (knob 54 = 2 / 3): every XCD reads the whole buffer once (workgroup b runs on XCD b % 8 and takes slice b / 8
-// of 32), so that the launch behind it finds the operand in its XCD's L2 -- prices what a projection loses to cold operands
-// inside a decoding step (profiles/r06_b_*).  `sink` is never written (the sum of finite values is not NaN-compared true).
-__global__ void __launch_bounds__(256) x3r_touch_kernel(const uint4* __restrict__ p, size_t n16, unsigned* __restrict__ sink) {
-  const size_t per = (n16 + 31) / 32, b0 = (size_t)(blockIdx.x >> 3) * per, b1 = b0 + per < n16 ? b0 + per : n16;
-  unsigned acc = 0;
-  for (size_t i = b0 + threadIdx.x; i < b1; i += 256) {
-    const uint4 v = p[i];
-    acc ^= v.x ^ v.y ^ v.z ^ v.w;
-  }
-  if (acc == 0x9e3779b9u && n16 == 1) *sink = acc;
-}
+// (What a projection loses to cold operands inside a decoding step was measured in round 6 with builds since removed: every launch
+// issued twice, the repeat finding its operands where the first left them, and a launch in front that read the weight panel, or the
+// panel and the A rows, into every XCD's L2 -- profiles/r06_b_*.)
 
 }  // namespace
 
@@ -338,9 +329,6 @@ int g_x3r_ln = 1;
 int g_x3r_pair = 1;   // key 58: operand loads of two k steps issued together (bit 0: plain kernel -- the default: 31.0 against 34.8 us at K = 2 048,
                       // 13.0-13.2 against 13.3 at N = K = 512 in the step's device timeline; bit 1: with the LayerNorm prologue -- off: 32.6 /
                       // 22.7 / 14.4 against 31.5 / 21.8 / 13.0 us, its rows are in the L1 / L2 from the statistics pre-pass; profiles/r06_l_*)
-int g_x3r_probe = 0;  // key 54, MEASUREMENT ONLY (results of in-place launches are wrong with 1): 1 = every launch is issued twice, the second under the
-                      // profiler name *_rep (its operands are where the first left them); 2 = the weight panel is read into every XCD's L2 by a
-                      // launch in front ("x3r_touch"); 3 = the panel and the A rows
 int g_x3r_xc = 0;  // key 51: column groups among the XCDs (1 / 2 / 4 / 8; 0 = the count that minimises the fabric traffic)
 
 // A fp32 [M, K] (row stride lda); ln_eps >= 0: the operand is LayerNorm(A) over K with the affine folded into (PW, bias), row
@@ -361,16 +349,7 @@ static int launch_x3r(const float* A, int lda, const uint16_t* PW, const float* 
       if (c * ab + (8 / c) * wb < xc * ab + (8 / xc) * wb) xc = c;
   }
   X3rArgs a{A, reinterpret_cast<const uint4*>(PW), bias, R, C, K / 64, lda, ldr, ldc, M, N, K, act, tm, tn, alpha, ln_eps, xc};
-  if (g_x3r_probe >= 2) {
-    ProfScope pt("x3r_touch", 0.0, 8.0 * 6.0 * (double)N * K, st);
-    SBK_LAUNCH(x3r_touch_kernel, dim3(256), dim3(256), 0, st, reinterpret_cast<const uint4*>(PW), (size_t)N * K * 6 / 16, (unsigned*)nullptr);
-    if (g_x3r_probe == 3 && lda == K)
-      SBK_LAUNCH(x3r_touch_kernel, dim3(256), dim3(256), 0, st, reinterpret_cast<const uint4*>(A), (size_t)M * K * 4 / 16, (unsigned*)nullptr);
-  }
-  const int reps = g_x3r_probe == 1 ? 2 : 1;
-  int rc_last = 0;
-  for (int rep = 0; rep < reps; ++rep) {
-  ProfScope prof(rep ? (ln ? "gemm_ln_x3r_rep" : "gemm_x3r_rep") : (ln ? "gemm_ln_x3r" : "gemm_x3r"), 2.0 * M * N * K,
+  ProfScope prof(ln ? "gemm_ln_x3r" : "gemm_x3r", 2.0 * M * N * K,
                  4.0 * M * (double)K + 6.0 * (double)N * K + (4.0 + (R ? 4.0 : 0.0)) * M * (double)N, st);
   dim3 grid(8 * cdiv(tm, 8 / xc) * cdiv(tn, xc)), block(256);
   const int pair = g_x3r_pair;  // bit 0: the plain kernel, bit 1: the LayerNorm-prologue kernel
@@ -385,20 +364,16 @@ static int launch_x3r(const float* A, int lda, const uint16_t* PW, const float* 
     } else {
       SBK_LAUNCH((gemm_x3r_kernel<0, 5>), grid, block, 0, st, a);
     }
-    rc_last = launch_status("gemm_ln_x3r");
+    return launch_status("gemm_ln_x3r");
+  }
+  if (K == 512 && N >= 1024 && g_x3r_mode != 3) {
+    if (pair & 1) SBK_LAUNCH((gemm_x3r_kernel<8, 0, true>), grid, block, 0, st, a);
+    else SBK_LAUNCH((gemm_x3r_kernel<8>), grid, block, 0, st, a);
   } else {
-    if (K == 512 && N >= 1024 && g_x3r_mode != 3) {
-      if (pair & 1) SBK_LAUNCH((gemm_x3r_kernel<8, 0, true>), grid, block, 0, st, a);
-      else SBK_LAUNCH((gemm_x3r_kernel<8>), grid, block, 0, st, a);
-    } else {
-      if (pair & 1) SBK_LAUNCH((gemm_x3r_kernel<0, 0, true>), grid, block, 0, st, a);
-      else SBK_LAUNCH((gemm_x3r_kernel<0>), grid, block, 0, st, a);
-    }
-    rc_last = launch_status("gemm_x3r");
+    if (pair & 1) SBK_LAUNCH((gemm_x3r_kernel<0, 0, true>), grid, block, 0, st, a);
+    else SBK_LAUNCH((gemm_x3r_kernel<0>), grid, block, 0, st, a);
   }
-  if (rc_last) return rc_last;
-  }
-  return rc_last;
+  return launch_status("gemm_x3r");
 }
 int gemm_nt_x3r(const float* A, int lda, const uint16_t* PW, const float* bias, const float* R, int ldr, float* C, int ldc, int M,
                 int N, int K, int act, float alpha, hipStream_t st) {

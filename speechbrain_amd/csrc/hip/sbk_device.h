@@ -119,26 +119,11 @@ __device__ __forceinline__ void sched_group() { __builtin_amdgcn_sched_group_bar
 // later basic block (next to its use), i.e. out of the MFMA stream it was written to be issued under.
 __device__ __forceinline__ void pin(unsigned& x) { asm volatile("" : "+v"(x)); }
 __device__ __forceinline__ void pin(float& x) { asm volatile("" : "+v"(x)); }
-__device__ __forceinline__ void pin(f32x16& x) { asm volatile("" : "+v"(x)); }  // (an MFMA result: keeps the MFMA at this point of the stream)
 
 // 2^x as ONE v_exp_f32 (no range fix-ups: fine for softmax weights, x <= 0 or -inf; libm's exp2f / expf add a scaling and its undo);
 // wave_any: the predicate holds in at least one lane (wave-uniform result)
 __device__ __forceinline__ float exp2_raw(float x) { return __builtin_amdgcn_exp2f(x); }
 __device__ __forceinline__ bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0; }
-// measurement builds: a 16-byte value stays live up to this point / an all-zero 16-byte value the optimiser cannot see through
-template <class T>
-__device__ __forceinline__ void keep(const T& x) {
-  static_assert(sizeof(T) == 16, "keep: one register quad");
-  const u32x4 u = __builtin_bit_cast(u32x4, x);
-  asm volatile("" ::"v"(u));
-}
-template <class T>
-__device__ __forceinline__ T opaque_zero() {
-  static_assert(sizeof(T) == 16, "opaque_zero: one register quad");
-  u32x4 u = {0u, 0u, 0u, 0u};
-  asm volatile("" : "+v"(u));
-  return __builtin_bit_cast(T, u);
-}
 // GELU (erf form) for the epilogues of the REDUCED-PRECISION contractions (bf16 / e4m3 activations: csrc/gemm_lp.hip, gemm_lp256.hip;
 // the fp32 parity path keeps libm's erff).  1 + erf(x / sqrt 2) = 2 - erfc(z) for x >= 0 and erfc(z) for x < 0, z = |x| / sqrt 2, with
 // erfc by Abramowitz & Stegun 7.1.26 (absolute error <= 1.5e-7: below half an ulp of the bf16 / e4m3 value it is rounded to, and the
@@ -158,9 +143,6 @@ __device__ __forceinline__ float gelu_erfc(float x) {
   const float q = (p * t) * exp2_raw(-1.44269504088896340736f * (z * z));  // erfc(z)
   return (0.5f * x) * (x >= 0.0f ? 2.0f - q : q);
 }
-// wave priority for the instruction arbiter of the SIMD (0 = default .. 3)
-template <int P>
-__device__ __forceinline__ void set_prio() { __builtin_amdgcn_s_setprio(P); }
 
 // x * 2^e and the exponent k of x = f * 2^k, f in [0.5,1) (0 for x = 0): single VALU instructions
 // (v_ldexp_f32 / v_frexp_exp_i32_f32) without the libm special-case wrappers.

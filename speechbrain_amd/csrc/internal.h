@@ -2,6 +2,7 @@
 // call the same launchers the C ABI exposes, without re-validating arguments).
 #pragma once
 #include "common.h"
+#include "knobs.h"
 
 namespace sbk {
 int gemm_nt(const float* A, int lda, const float* W, int ldw, const float* bias, const float* R, int ldr, float* C,
@@ -25,7 +26,6 @@ bool x3r_routed(int M, int N, int K);
 int gemm_ln_nt_x3r(const float* A, int lda, const uint16_t* PWf, const float* bf, const float* R, int ldr, float* C, int ldc, int M,
                    int N, int K, float eps, int act, float alpha, hipStream_t st);
 bool x3r_ln_routed(int K);
-extern int g_x3r_mode, g_x3r_min_rows, g_x3r_ln, g_x3r_probe, g_x3r_pair;
 // The decoding step of <= 16 hypothesis rows as ONE cooperative launch (csrc/decoder_persist.hip; keys 47 / 48).
 // persist_eligible: shapes / weights it takes (head_dim 64, folded LayerNorm weights present, <= 16 layers); decoder_step_persist
 // returns -1 when the launch cannot be made (the caller then issues the launch-per-operation step).
@@ -35,17 +35,11 @@ int decoder_step_persist(const sbk_decoder_weights* W, const int32_t* tokens, co
                          float* x, float* qkv, float* ctx, float* q, float* ff, float* h, float* logits, float* const* kcache,
                          float* const* vcache, float* const* ckv, int* bar, int bar_seq, int* grid_io, int step, int n, int B, int T,
                          int beam, int Lmax, bool want_logits, hipStream_t st);
-extern int g_persist, g_persist_grid, g_persist_stamps, g_persist_tree;
 // Device-resident step counter of the search running on this host thread (nullptr: the step is the
 // launch argument).  When set, every step-dependent kernel reads the step from it, so that the launches
 // of one decoding step are identical for every step and can be replayed from a captured hipGraph.
 extern thread_local const int32_t* g_step_ptr;
 extern thread_local int g_step_min_steps;  // min_decode_steps of that search (eos floor: step < min_steps)
-extern int g_cross_rows;
-extern int g_nt_mask;
-extern int g_self_anc;
-extern int g_attn_exp2;
-extern int g_cross_fc256;
 // bf16 x bf16 / e4m3 x e4m3 contraction on 256 x 256 tiles (csrc/gemm_lp256.hip): the large shapes of sbk_gemm_nt_bf16a / _fp8a.
 // lda / ldw in BYTES; KT = bytes of a row of K / 128; sa / sw / C8 only with fp8 operands.  lp256_routed: key 61 and the shape.
 struct Lp256Args {
@@ -66,9 +60,6 @@ struct Lp256Args {
 };
 bool lp256_routed(const Lp256Args& a);
 int gemm_nt_lp256(const Lp256Args& a, bool fp8, hipStream_t st);
-extern int g_lp256, g_lp256_mode, g_x3p_mode, g_x3p_fast_epi;
-extern int g_x3r_xc;
-extern int g_score_fused;  // key 40: 1 (default) = the step's scoring as one pass per hypothesis row (csrc/search.hip)
 constexpr float kCtcNeg = -1e20f;  // the CTC scorer's finite "log 0" (ctc.py:150, scorer.py:1250)
 // The arithmetic of a decoding step's scoring, shared by the separate kernels (log_softmax_row / ctc_combine / am_only /
 // beam_topk_stage1) and the fused pass (score_topk_row_kernel).  Written with explicitly rounded operations so that

@@ -205,6 +205,31 @@ def load(path: Optional[str] = None):
     return lib
 
 
+# name -> key of the library's tuning switches (include/sbk.h, enum sbk_knob: SBK_KNOB_<NAME>)
+KNOBS = {
+    "skinny_off": 2, "cross_rows": 4, "cross_fc256": 8, "tiled_splitk": 14, "sk_mode": 18, "sk_min_rows": 24,
+    "x3_route_rows": 34, "x3_route_tiles": 35, "score_fused": 40, "x3r_mode": 41, "x3r_min_rows": 42, "x3r_ln": 45,
+    "persist": 47, "persist_grid": 48, "persist_stamps": 49, "x3r_xc": 51, "nt_mask": 53, "self_anc": 55, "x3r_pair": 58,
+    "persist_tree": 59, "attn_exp2": 60, "lp256": 61, "x3p_fast_epi": 63,
+}
+
+
+@contextlib.contextmanager
+def knobs(**values):
+    """``with knobs(persist=0, cross_rows=5): ...`` -- set the named tuning switches for the block and put back what they held
+    before, also when the block raises.  The switches are process-wide.  An unknown name raises KeyError before any is set."""
+    lib = load()
+    wanted = {KNOBS[name]: int(value) for name, value in values.items()}
+    found = {key: lib.sbk_prof_get_knob(key) for key in wanted}
+    try:
+        for key, value in wanted.items():
+            lib.sbk_prof_set_knob(key, value)
+        yield
+    finally:
+        for key, value in found.items():
+            lib.sbk_prof_set_knob(key, value)
+
+
 def _chk(rc: int, what: str):
     if rc != 0:
         raise SbkError(f"{what} failed (rc={rc}): {_lib.sbk_last_error().decode()}")

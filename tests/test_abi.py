@@ -61,3 +61,25 @@ def test_product_refuses_cpu_tensors(lib_path):
     native.load()
     with pytest.raises(native.SbkError):
         native.gemm_nt(torch.zeros(4, 4), torch.zeros(4, 4))
+
+
+def header_knobs():
+    """name -> key of enum sbk_knob in include/sbk.h"""
+    src = open(os.path.join(ROOT, "include", "sbk.h")).read()
+    return {name.lower(): int(key) for name, key in re.findall(r"\bSBK_KNOB_([A-Z0-9_]+)\s*=\s*(\d+)", src)}
+
+
+def test_knob_names_agree_between_header_binding_and_library(lib_path):
+    """One table in three places: the SBK_KNOB_* enum of include/sbk.h, native.KNOBS, and the keys csrc/knobs.cpp knows.
+    A key the enum does not list is unknown to the library: reading it gives INT_MIN."""
+    from speechbrain_amd import native
+
+    enum = header_knobs()
+    assert len(enum) == 23 and len(set(enum.values())) == 23
+    assert enum == native.KNOBS
+    lib = ctypes.CDLL(lib_path)
+    lib.sbk_prof_get_knob.restype = ctypes.c_int
+    int_min = -2 ** 31
+    known = {key for key in range(128) if lib.sbk_prof_get_knob(key) != int_min}
+    assert known == set(enum.values())
+    assert not known & {54, 62, 64}  # (the measurement builds removed after round 6)

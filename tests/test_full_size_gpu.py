@@ -128,12 +128,10 @@ def test_conformer_l_decoder_logprobs_and_search_vs_oracle():
     assert hyps == hyps_ref
     assert float((scores.cpu() - scores_ref).abs().max()) <= 1e-3
     # the same with the step's projections on sbk_gemm_nt_x3r (round 4: the route of every step with ~200 hypothesis rows
-    # or more -- the bench's grouped searches; this search has 20 rows, so the row threshold is lowered, knob 42): the
+    # or more -- the bench's grouped searches; this search has 20 rows, so the row threshold is lowered, x3r_min_rows): the
     # kernel the headline's decode loop spends its time in, inside the oracle comparison at Conformer-L size
-    lib = native.load()
-    lib.sbk_prof_set_knob(42, 1)
-    lib.sbk_prof_set_knob(47, 0)  # (the 2-row prefix above ran as the persistent few-row step, csrc/decoder_persist.hip; here the x3r route is wanted)
-    try:
+    # (persist: the 2-row prefix above ran as the persistent few-row step, csrc/decoder_persist.hip; here the x3r route is wanted)
+    with native.knobs(x3r_min_rows=1, persist=0):
         assert h.layers[0].sa_in_wp and h.layers[0].ff2_wp and h.W.seq_wp
         pred3 = native.decoder_prefix(h, tgt.int().cuda(), enc_ref.cuda(), enc_lens.cuda())
         lp3 = native.log_softmax(native.gemm_nt(pred3, asr.mods.seq_lin.w.weight, asr.mods.seq_lin.w.bias))
@@ -142,15 +140,12 @@ def test_conformer_l_decoder_logprobs_and_search_vs_oracle():
         hyps3, _, scores3, _ = asr.mods.decoder(enc_ref.cuda(), lens.cuda())
         assert hyps3 == hyps_ref
         assert float((scores3.cpu() - scores_ref).abs().max()) <= 1e-3
-    finally:
-        lib.sbk_prof_set_knob(42, 192)
-        lib.sbk_prof_set_knob(47, 1)
 
 
 def test_ring_cross_attention_conformer_l_geometry_default_knobs_vs_oracle():
     """csrc/decoder.hip cross_attn_ring_kernel at the geometry and under the knobs it SHIPS with, inside an
     oracle comparison on the GPU.  Conformer-L decoder (d 512, 8 heads of 64, 6 layers), 16 utterances = 128 (utterance, head)
-    pairs -- the default routing's threshold (knob 4 = 7) --, memories of T' = 420 frames with lengths 0.45 .. 1 of that, so the
+    pairs -- the default routing's threshold (cross_rows = 7) --, memories of T' = 420 frames with lengths 0.45 .. 1 of that, so the
     default run rule cuts each memory into 4 runs of 112 frames (partials, cross_merge; the short utterances leave EMPTY later
     runs, the last run of the longest holds 84 frames = 5 tiles + a 4-frame tile), beam 10 (a 16-column MFMA tile with six
     padding columns), no CTC (the oracle's Python-loop scorer would take minutes).  Then 32 utterances (256 pairs: the other
@@ -191,14 +186,12 @@ def test_ring_cross_attention_conformer_l_geometry_default_knobs_vs_oracle():
         if B == 16:  # teacher-forced decoder outputs on the search's own best hypotheses (one hypothesis row per memory: 16 x 8 pairs)
             tgt = torch.tensor([[1] + list(h[: L - 1]) for h in hyps])
             h = native.DecoderHandle(asr.mods.transformer, asr.mods.seq_lin)
-            lib = native.load()
-            lib.sbk_prof_set_knob(47, 0)  # (16 rows would otherwise run as the persistent few-row step, which has its own attention)
             native.prof_enable(True)
             try:
-                pred = native.decoder_prefix(h, tgt.int().cuda(), enc.cuda(), enc_lens.cuda())
+                with native.knobs(persist=0):  # (16 rows would otherwise run as the persistent few-row step, which has its own attention)
+                    pred = native.decoder_prefix(h, tgt.int().cuda(), enc.cuda(), enc_lens.cuda())
             finally:
                 native.prof_enable(False)
-                lib.sbk_prof_set_knob(47, 1)
             rep = native.prof_report()
             native.prof_reset()
             assert rep.get("cross_attn_ring", {}).get("count", 0) > 0 and rep.get("cross_merge", {}).get("count", 0) > 0, sorted(rep)

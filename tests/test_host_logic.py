@@ -309,3 +309,39 @@ def test_bench_traffic_rows_of_this_rounds_kernels_only(tmp_path):
     t = bench.pmc_traffic("gemm_x3r", roof)  # the committed file: this round's row of the kernel as shipped
     assert "traffic_note" in roof and "traffic_provenance" in roof and t and t > 9437184 and roof["mfma_busy_pmc"]
 
+
+
+@pytest.fixture
+def emu_native():
+    import emu_utils
+
+    nat = emu_utils.attach()
+    yield nat
+    emu_utils.detach()
+
+
+def test_knobs_scope_restores_what_it_found(emu_native):
+    """native.knobs puts back the values it FOUND (not the library's defaults) on normal exit and when the block raises;
+    nested scopes unwind in order; an unknown name raises KeyError before any switch is touched."""
+    nat = emu_native
+    get = nat.load().sbk_prof_get_knob
+    key = nat.KNOBS
+    assert set(key.values()) == {k for k in range(128) if get(k) != -2 ** 31}  # (the emulator build has the same table)
+    d_persist, d_rows, d_grid = get(key["persist"]), get(key["cross_rows"]), get(key["persist_grid"])
+    with nat.knobs(persist_grid=d_grid + 5):  # a found value that is not the default
+        with nat.knobs(persist=d_persist + 1, cross_rows=d_rows + 2):
+            assert (get(key["persist"]), get(key["cross_rows"]), get(key["persist_grid"])) == (d_persist + 1, d_rows + 2, d_grid + 5)
+            with nat.knobs(persist=d_persist + 3, persist_grid=d_grid + 7):
+                assert (get(key["persist"]), get(key["cross_rows"]), get(key["persist_grid"])) == (d_persist + 3, d_rows + 2, d_grid + 7)
+            assert (get(key["persist"]), get(key["cross_rows"]), get(key["persist_grid"])) == (d_persist + 1, d_rows + 2, d_grid + 5)
+            with pytest.raises(ZeroDivisionError):
+                with nat.knobs(persist=d_persist + 4):
+                    assert get(key["persist"]) == d_persist + 4
+                    1 / 0
+            assert get(key["persist"]) == d_persist + 1
+            with pytest.raises(KeyError):
+                with nat.knobs(cross_rows=d_rows + 9, x3r_probe=1):  # (a removed knob: no such name)
+                    raise AssertionError("the block must not run")
+            assert (get(key["persist"]), get(key["cross_rows"])) == (d_persist + 1, d_rows + 2)
+        assert (get(key["persist"]), get(key["cross_rows"]), get(key["persist_grid"])) == (d_persist, d_rows, d_grid + 5)
+    assert (get(key["persist"]), get(key["cross_rows"]), get(key["persist_grid"])) == (d_persist, d_rows, d_grid)

@@ -61,7 +61,7 @@ def test_gemm_skinny_splitk(backend, M, N, K):
 
 @pytest.mark.parametrize("M,N,K", [(100, 72, 2048), (300, 200, 2048), (1280, 512, 2048), (1100, 768, 768)])
 def test_gemm_tiled_splitk_variant(backend, M, N, K):
-    """csrc/gemm.hip gemm_nt_splitk_kernel (tuning knob 14): few rows, long K through 64x64 LDS tiles with a K split +
+    """csrc/gemm.hip gemm_nt_splitk_kernel (knob tiled_splitk): few rows, long K through 64x64 LDS tiles with a K split +
     the fixed-order reduce -- same epilogue (bias, GELU, alpha, residual in place), ragged M and N; against the fp64
     product and against the register-operand split-K path; bit-identical over repeated launches."""
     nat, dev = backend
@@ -73,17 +73,13 @@ def test_gemm_tiled_splitk_variant(backend, M, N, K):
     b, r = torch.randn(N, generator=g), torch.randn(M, N, generator=g)
     ref = r + 0.5 * F.gelu(a.double() @ w.double().t() + b).float()
     scale = float((a.abs() @ w.abs().t()).max())
-    lib = nat.load()
     args = (a.to(dev), w.to(dev), b.to(dev), r.to(dev))
-    lib.sbk_prof_set_knob(14, 0)
-    try:
+    with nat.knobs(tiled_splitk=0):
         base = nat.gemm_nt_splitk(*args, act=nat.ACT_GELU, alpha=0.5, slices=4)  # the register-operand split-K path
-        lib.sbk_prof_set_knob(14, 64)
+    with nat.knobs(tiled_splitk=64):
         out = nat.gemm_nt_splitk(*args, act=nat.ACT_GELU, alpha=0.5, slices=4)
         for _ in range(3 if dev.type == "cuda" else 1):
             assert torch.equal(nat.gemm_nt_splitk(*args, act=nat.ACT_GELU, alpha=0.5, slices=4), out)
-    finally:
-        lib.sbk_prof_set_knob(14, 256)
     assert _md(out, ref) <= 2e-6 * scale + 1e-5
     assert _md(base, ref) <= 2e-6 * scale + 1e-5
 
@@ -557,7 +553,7 @@ def test_attention_bf16_rows_through_lds(backend, B, T, H, ragged):
 @pytest.mark.parametrize("M,N,K", [(700, 300, 96), (1000, 130, 64), (257, 128, 640), (520, 260, 128), (2100, 300, 64), (4100, 512, 512),
                                    (130, 1030, 2048)])
 def test_gemm_stream_k(backend, M, N, K):
-    """The stream-K LDS-DMA kernel (128-wide tiles: the encoder's contractions), forced at small ragged shapes (knob 18 = 2:
+    """The stream-K LDS-DMA kernel (128-wide tiles: the encoder's contractions), forced at small ragged shapes (knob sk_mode = 2:
     the grid follows the device, so the tiles are cut by the unit ranges of several workgroups -- partial slabs + last-arriver
     reduction -- next to whole tiles); bias / activation / scaled residual / row mask; run-to-run bit-identical."""
     nat, dev = backend
@@ -568,9 +564,7 @@ def test_gemm_stream_k(backend, M, N, K):
     w = torch.randn(N, K, generator=g) - torch.arange(N)[:, None] * 0.02
     b, r = torch.randn(N, generator=g), torch.randn(M, N, generator=g)
     scale = float((a.abs() @ w.abs().t()).max())
-    lib = nat.load()
-    lib.sbk_prof_set_knob(18, 2)
-    try:
+    with nat.knobs(sk_mode=2):
         ad, wd, bd, rd = a.to(dev), w.to(dev), b.to(dev), r.to(dev)
         out = nat.gemm_nt(ad, wd, bd, rd, act=nat.ACT_SWISH, alpha=0.5)
         ref = r + 0.5 * F.silu(a.double() @ w.double().t() + b).float()
@@ -590,8 +584,6 @@ def test_gemm_stream_k(backend, M, N, K):
         if N == K:  # in-place residual
             out = nat.gemm_nt(x, wd, None, x)
             assert _md(out, a + (a.double() @ w.double().t()).float()) <= 2e-6 * scale + 1e-5
-    finally:
-        lib.sbk_prof_set_knob(18, 1)
 
 
 @pytest.mark.parametrize("M,N,K", [(700, 300, 96), (1000, 132, 64), (257, 128, 640), (520, 260, 128), (2100, 300, 64), (1100, 520, 96),
@@ -765,20 +757,13 @@ def test_gemm_x3r(backend, M, N, K):
     assert _md(plain, prod.float()) <= 2e-6 * scale + 1e-5
     # the ownership of the tile space by the XCDs (1 / 2 / 4 / 8 column groups x 8 / 4 / 2 / 1 row groups; default: the split
     # with the fewest bytes across the fabric) only permutes the workgroups: every tile exactly once, the same bits
-    try:
-        for xc in (1, 2, 4, 8):
-            nat.load().sbk_prof_set_knob(51, xc)
+    for xc in (1, 2, 4, 8):
+        with nat.knobs(x3r_xc=xc):
             assert torch.equal(nat.gemm_nt_x3r(ad, wd, bd, rd, act=nat.ACT_SWISH, alpha=0.5), out), xc
-    finally:
-        nat.load().sbk_prof_set_knob(51, 0)
-    # the order in which the operand loads are issued (knob 58: two k steps together) changes no bit
-    keep = nat.load().sbk_prof_get_knob(58)
-    try:
-        for sched in (0, 3):
-            nat.load().sbk_prof_set_knob(58, sched)
+    # the order in which the operand loads are issued (knob x3r_pair: two k steps together) changes no bit
+    for sched in (0, 3):
+        with nat.knobs(x3r_pair=sched):
             assert torch.equal(nat.gemm_nt_x3r(ad, wd, bd, rd, act=nat.ACT_SWISH, alpha=0.5), out), sched
-    finally:
-        nat.load().sbk_prof_set_knob(58, keep)
 
 
 @pytest.mark.parametrize("M,N,K", [(1280, 512, 512), (300, 132, 512), (70, 1536, 512), (1280, 2048, 512), (1, 40, 512),
@@ -814,13 +799,9 @@ def test_gemm_ln_x3r(backend, M, N, K):
         assert torch.equal(nat.gemm_ln_nt_x3r(ad, wfd, bfd, eps, residual=rd, act=nat.ACT_SWISH, alpha=0.5), out)
     plain = nat.gemm_ln_nt_x3r(ad, wfd, bfd, eps)
     assert _md(plain, (prod + b.double()).float()) <= 2e-6 * scale + 1e-5
-    keep = nat.load().sbk_prof_get_knob(58)
-    try:
-        for sched in (0, 3):  # (the issue order of the operand loads changes no bit)
-            nat.load().sbk_prof_set_knob(58, sched)
+    for sched in (0, 3):  # (the issue order of the operand loads changes no bit)
+        with nat.knobs(x3r_pair=sched):
             assert torch.equal(nat.gemm_ln_nt_x3r(ad, wfd, bfd, eps), plain), sched
-    finally:
-        nat.load().sbk_prof_set_knob(58, keep)
     if K % 256 == 0:
         two = nat.gemm_nt_x3r(nat.layernorm(ad, gd, btd, eps), wd, bd)
         assert _md(plain, two) <= 2e-6 * scale + 1e-5
@@ -909,7 +890,7 @@ def test_gemm_fp8a(backend, M, N, K):
 @pytest.mark.parametrize("M,N,K", [(300, 260, 256), (520, 300, 384), (256, 512, 128), (1100, 700, 640), (1300, 1100, 256), (12000, 1280, 1280),
                                    (12000, 3840, 1280), (4100, 1280, 5120)])
 def test_gemm_lp256_tiles_equal_the_128_tile_kernels(backend, M, N, K):
-    """csrc/gemm_lp256.hip (256 x 256 tiles, eight waves in two groups half a step apart, a ring of two 64 KB K tiles; key 61): the
+    """csrc/gemm_lp256.hip (256 x 256 tiles, eight waves in two groups half a step apart, a ring of two 64 KB K tiles; knob lp256): the
     large shapes of sbk_gemm_nt_bf16a / sbk_gemm_nt_fp8a.  It forms the same sums in the same order as the 128 x 128 kernels (K
     ascending, one accumulator per output element, the same MFMA instruction), so every output of every form -- fp32 with bias /
     GELU / alpha / residual, bf16, e4m3 -- must be bit-identical between the two routes; ragged last tiles in both dimensions, one
@@ -918,8 +899,6 @@ def test_gemm_lp256_tiles_equal_the_128_tile_kernels(backend, M, N, K):
     nat, dev = backend
     if dev.type == "cpu" and M * N * K > 4e8:
         pytest.skip("large shape: GPU only")
-    lib = nat.load()
-    keep = lib.sbk_prof_get_knob(61)
     g = torch.Generator().manual_seed(M + N + K)
     a = torch.randn(M, K, generator=g) * (1.0 + torch.arange(M)[:, None] * 0.01)
     w = torch.randn(N, K, generator=g) * 0.05
@@ -937,16 +916,13 @@ def test_gemm_lp256_tiles_equal_the_128_tile_kernels(backend, M, N, K):
                     nat.gemm_nt_fp8a(aq, wd, bd, out_dtype=torch.bfloat16), nat.gemm_nt_fp8a(aq, wd, bd, act=nat.ACT_GELU, out_dtype="fp8").q]
         return [o.cpu() for o in out]
 
-    try:
-        lib.sbk_prof_set_knob(61, 0)
+    with nat.knobs(lp256=0):
         want = forms()
-        lib.sbk_prof_set_knob(61, 2)
+    with nat.knobs(lp256=2):
         for _ in range(3 if dev.type == "cuda" else 1):
             got = forms()
             for i, (x, y) in enumerate(zip(got, want)):
                 assert torch.equal(x, y), (i, float((x.float() - y.float()).abs().max()))
-    finally:
-        lib.sbk_prof_set_knob(61, keep)
 
 
 def test_no_stream_workspace_is_an_error_not_an_allocation(backend):
@@ -1018,7 +994,7 @@ def test_cross_attention_register_ring_kernel(backend, d_model, nhead, B, T, bea
     """csrc/decoder.hip cross_attn_ring_kernel (head_dim 64: a wave per (utterance, head, run of frames), 16-frame K / V tiles
     straight into MFMA operand registers three tiles deep, transposed scores and context on the matrix cores, online softmax
     over the runs of the memory) through the KV-cached decoder: teacher-forced decoder outputs must match the frame-per-thread
-    kernel (knob 4 = 0) and the oracle's full-prefix decode -- ragged memory lengths (partial last tile, runs past a short
+    kernel (cross_rows = 0) and the oracle's full-prefix decode -- ragged memory lengths (partial last tile, runs past a short
     utterance's end, fewer tiles than the ring is deep), several hypotheses per utterance, a 20-frame memory."""
     nat, dev = backend
     from speechbrain_amd.inference.builders import build_modules, flat_state_dict
@@ -1037,29 +1013,18 @@ def test_cross_attention_register_ring_kernel(backend, d_model, nhead, B, T, bea
     ref = O.decode(tgt, enc, enc_len, sd, cfg, "Transformer.")
     h = nat.DecoderHandle(tr, seq)
     outs = {}
-    nat.load().sbk_prof_set_knob(47, 0)  # (<= 16 rows would otherwise run as the persistent few-row step, which has its own attention)
-    try:
+    with nat.knobs(persist=0):  # (<= 16 rows would otherwise run as the persistent few-row step, which has its own attention)
         for knob in (0, 5):
-            nat.load().sbk_prof_set_knob(4, knob)
-            try:
+            with nat.knobs(cross_rows=knob):
                 outs[knob] = nat.decoder_prefix(h, tgt.int().to(dev), enc.to(dev), enc_len.to(dev)).cpu()
-            finally:
-                nat.load().sbk_prof_set_knob(4, 7)
         assert float((outs[0] - ref).abs().max()) <= 5e-5
         assert float((outs[5] - ref).abs().max()) <= 5e-5
-        # one run per utterance (knob 8 = 3: the wave walks the whole memory and writes the context itself -- no partials, no
+        # one run per utterance (cross_fc256 = 3: the wave walks the whole memory and writes the context itself -- no partials, no
         # merge launch: what a search of >= 128 utterances x 8 heads gets by default)
-        nat.load().sbk_prof_set_knob(4, 5)
-        nat.load().sbk_prof_set_knob(8, 3)
-        try:
+        with nat.knobs(cross_rows=5, cross_fc256=3):
             one = nat.decoder_prefix(h, tgt.int().to(dev), enc.to(dev), enc_len.to(dev)).cpu()
             again = nat.decoder_prefix(h, tgt.int().to(dev), enc.to(dev), enc_len.to(dev)).cpu()
-        finally:
-            nat.load().sbk_prof_set_knob(4, 7)
-            nat.load().sbk_prof_set_knob(8, 0)
         assert float((one - ref).abs().max()) <= 5e-5 and torch.equal(one, again)
-    finally:
-        nat.load().sbk_prof_set_knob(47, 1)
     if beam_rows == 1:
         return
     # the search itself (beam_rows hypotheses per utterance share a memory) vs the oracle's search
@@ -1073,11 +1038,8 @@ def test_cross_attention_register_ring_kernel(backend, d_model, nhead, B, T, bea
     hyps_ref, _, sc_ref, _ = O.beam_search(enc_u, wl, sd, cfg, O.SearchCfg(beam=beam_rows, ctc_weight=0.0, max_decode_ratio=ratio))
     bs = S2STransformerBeamSearcher(modules=[tr, seq], bos_index=1, eos_index=2, min_decode_ratio=0.0, max_decode_ratio=ratio,
                                     beam_size=beam_rows, using_eos_threshold=False, length_normalization=True)
-    nat.load().sbk_prof_set_knob(4, 5)
-    try:
+    with nat.knobs(cross_rows=5):
         hyps, _, sc, _ = bs(enc_u.to(dev), wl.to(dev))
-    finally:
-        nat.load().sbk_prof_set_knob(4, 7)
     assert hyps == hyps_ref
     assert float((sc.cpu() - sc_ref).abs().max()) <= 1e-4
 
@@ -1104,14 +1066,11 @@ def test_cross_attention_register_ring_kernel_edge_shapes(backend, d_model, nhea
     tgt = torch.randint(0, 40, (B, 5), generator=gen)
     ref = O.decode(tgt, enc, enc_len, sd, cfg, "Transformer.")
     h = nat.DecoderHandle(tr, seq)
-    lib = nat.load()
-    lib.sbk_prof_set_knob(47, 0)  # (not the persistent few-row step, which has its own attention)
-    try:
+    with nat.knobs(persist=0):  # (not the persistent few-row step, which has its own attention)
         outs = {}
         for rows, one_run in ((0, 0), (5, 0), (5, 3)):
-            lib.sbk_prof_set_knob(4, rows)
-            lib.sbk_prof_set_knob(8, one_run)
-            outs[(rows, one_run)] = nat.decoder_prefix(h, tgt.int().to(dev), enc.to(dev), enc_len.to(dev)).cpu()
+            with nat.knobs(cross_rows=rows, cross_fc256=one_run):
+                outs[(rows, one_run)] = nat.decoder_prefix(h, tgt.int().to(dev), enc.to(dev), enc_len.to(dev)).cpu()
         for k, v in outs.items():
             assert float((v - ref).abs().max()) <= 5e-5, k
         # from 200 frames on the default rule cuts the memory into runs (partials + cross_merge: another summation order than
@@ -1125,25 +1084,20 @@ def test_cross_attention_register_ring_kernel_edge_shapes(backend, d_model, nhea
         bs = S2STransformerBeamSearcher(modules=[tr, seq], bos_index=1, eos_index=2, min_decode_ratio=0.0, max_decode_ratio=ratio,
                                         beam_size=beam, using_eos_threshold=False, length_normalization=True)
         for one_run in (0, 3):
-            lib.sbk_prof_set_knob(4, 5)
-            lib.sbk_prof_set_knob(8, one_run)
-            hyps, _, sc, _ = bs(enc.to(dev), wl.to(dev))
+            with nat.knobs(cross_rows=5, cross_fc256=one_run):
+                hyps, _, sc, _ = bs(enc.to(dev), wl.to(dev))
             assert hyps == hyps_ref, one_run
             assert float((sc.cpu() - sc_ref).abs().max()) <= 1e-4
-    finally:
-        lib.sbk_prof_set_knob(4, 7)
-        lib.sbk_prof_set_knob(8, 0)
-        lib.sbk_prof_set_knob(47, 1)
 
 
 @pytest.mark.parametrize("d_model,nhead,B,beam,steps", [(128, 2, 3, 10, 70), (128, 2, 2, 16, 40), (192, 3, 5, 2, 20), (128, 2, 1, 3, 130)])
 def test_self_attention_over_shared_ancestry(backend, d_model, nhead, B, beam, steps):
-    """csrc/decoder.hip self_attn_anc_kernel (knob 55 = 1; head_dim 64, 2 .. 16 beams: a workgroup per (utterance, head) whose four
+    """csrc/decoder.hip self_attn_anc_kernel (self_anc = 1; head_dim 64, 2 .. 16 beams: a workgroup per (utterance, head) whose four
     waves each list the DISTINCT (slot, position) cache rows of the beams' prefixes over a quarter of the positions, with a mask of
     the beams descending from each row, fetch every row once and score it against all beams on the matrix cores -- a (row, beam) pair
     outside the beam's ancestry is masked to probability 0 -- and merge their partial softmaxes through LDS) through the
     beam search: token ids and scores against the oracle's full-prefix search and against the wave-per-(hypothesis, head) kernel
-    (knob 55 = 0) -- prefixes longer than 64 positions (two passes of the list builder, > 3 tiles: whole rounds of the register
+    (self_anc = 0) -- prefixes longer than 64 positions (two passes of the list builder, > 3 tiles: whole rounds of the register
     ring), a full 16-beam tile, 2 and 3 beams (masks with few bits), 5 utterances x 3 heads = 15 waves (a partial last workgroup),
     130 steps with 3 beams (rows of other beams fill whole tiles: the -inf guard of the online softmax)."""
     nat, dev = backend
@@ -1165,17 +1119,14 @@ def test_self_attention_over_shared_ancestry(backend, d_model, nhead, B, beam, s
     hyps_ref, _, sc_ref, _ = O.beam_search(enc, wl, sd, cfg, O.SearchCfg(beam=beam, ctc_weight=0.0, max_decode_ratio=ratio, min_decode_ratio=min_ratio))
     bs = S2STransformerBeamSearcher(modules=[tr, seq], bos_index=1, eos_index=2, min_decode_ratio=min_ratio, max_decode_ratio=ratio,
                                     beam_size=beam, using_eos_threshold=False, length_normalization=True)
-    lib = nat.load()
-    keep55 = lib.sbk_prof_get_knob(55)
-    lib.sbk_prof_set_knob(47, 0)  # (not the persistent few-row step, which has its own attention)
-    try:
+    with nat.knobs(persist=0):  # (not the persistent few-row step, which has its own attention)
         got = {}
         for anc in (1, 0):
-            lib.sbk_prof_set_knob(55, anc)
             nat.prof_reset()
             nat.prof_enable(True)
             try:
-                hyps, _, sc, _ = bs(enc.to(dev), wl.to(dev))
+                with nat.knobs(self_anc=anc):
+                    hyps, _, sc, _ = bs(enc.to(dev), wl.to(dev))
             finally:
                 nat.prof_enable(False)
             rep = nat.prof_report()
@@ -1186,9 +1137,6 @@ def test_self_attention_over_shared_ancestry(backend, d_model, nhead, B, beam, s
             assert float((sc.cpu() - sc_ref).abs().max()) <= 1e-4, anc
         assert min(len(h) for h in got[1][0]) >= steps - 6  # (long prefixes were actually decoded)
         assert float((got[1][1] - got[0][1]).abs().max()) <= 2e-5
-    finally:
-        lib.sbk_prof_set_knob(55, keep55)
-        lib.sbk_prof_set_knob(47, 1)
 
 
 @pytest.mark.parametrize("M,N,K", [(70, 50, 48), (300, 130, 64), (5000, 300, 80)])

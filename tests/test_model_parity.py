@@ -271,14 +271,13 @@ def test_persistent_few_row_decoding_step_vs_oracle_and_the_launch_per_operation
     hand-over of the activations.  Against the oracle: teacher-forced decoder outputs 5e-5 (3 rows, beam 1), beam search
     with CTC for one utterance at beam 10 and beam 16 (the full 16-row tile) and three utterances at beam 4 (12 rows, ragged
     memory lengths), a 300-frame memory (several 256-frame runs per wave in the cross-attention), the greedy searcher --
-    token ids exact, scores 1e-4; and against the launch-per-operation path of the same library (knob 47 = 0): ids equal,
-    scores 2e-5.  The profiler's launch names show which path ran; with another grid (knob 48) the result is the same."""
+    token ids exact, scores 1e-4; and against the launch-per-operation path of the same library (persist = 0): ids equal,
+    scores 2e-5.  The profiler's launch names show which path ran; with another grid (persist_grid) the result is the same."""
     nat, dev = backend
     from speechbrain_amd.decoders import CTCScorer, S2STransformerBeamSearcher, S2STransformerGreedySearcher, ScorerBuilder
 
     dm, H, dffn = (128, 2, 256) if shape == "d128" else (512, 8, 2048)
     mods, sd, cfg, gen = _persist_model(dev, dm, H, dffn, 2, 60, 7 if shape == "d128" else 9)
-    lib = nat.load()
 
     def searcher(beam, ratio, ctc=0.4):
         scorer = ScorerBuilder(full_scorers=[CTCScorer(ctc_fc=mods["ctc_lin"], blank_index=0, eos_index=2)], weights={"ctc": ctc})
@@ -295,65 +294,49 @@ def test_persistent_few_row_decoding_step_vs_oracle_and_the_launch_per_operation
             nat.prof_enable(False)
         return out, nat.prof_report()
 
-    try:
-        enc = torch.randn(3, 30, dm, generator=gen)
-        wl = torch.tensor([1.0, 0.7, 0.9])
-        enc_len = torch.round(30 * wl).int()
-        tgt = torch.randint(0, 60, (3, 6), generator=gen)
-        h = nat.DecoderHandle(mods["Transformer"], mods["seq_lin"])
-        pred, rep = run(lambda: nat.decoder_prefix(h, tgt.int().to(dev), enc.to(dev), enc_len.to(dev)))
-        assert rep.get("decoder_step_persist", {}).get("count", 0) == tgt.shape[1] and "self_attn_step" not in rep, sorted(rep)
-        assert float((pred.cpu() - O.decode(tgt, enc, enc_len, sd, cfg, "Transformer.")).abs().max()) <= 5e-5
-        cases = [("one utterance, beam 10", enc[:1], wl[:1], 10, 8.5 / 30), ("three utterances, beam 4", enc, wl, 4, 8.5 / 30)]
-        if shape == "d128":
-            long_enc = torch.randn(1, 300, dm, generator=gen)
-            cases += [("one utterance, beam 16", enc[1:2], torch.ones(1), 16, 6.5 / 30),
-                      ("300-frame memory", long_enc, torch.tensor([0.93]), 10, 6.5 / 300)]
-        for tag, e, w, beam, ratio in cases:
-            ref_h, _, ref_s, _ = O.beam_search(e, w, sd, cfg, O.SearchCfg(beam=beam, ctc_weight=0.4, max_decode_ratio=ratio))
-            bs = searcher(beam, ratio)
-            (hyps, _, sc, _), rep = run(lambda: bs(e.to(dev), w.to(dev)))
-            assert rep.get("decoder_step_persist", {}).get("count", 0) >= 1 and "cross_attn_step" not in rep and "gemm_skinny_ln" not in rep, (tag, sorted(rep))
-            assert hyps == ref_h, tag
-            assert float((sc.cpu() - ref_s).abs().max()) <= 1e-4, tag
-            lib.sbk_prof_set_knob(47, 0)
-            try:
-                (hyps0, _, sc0, _), rep0 = run(lambda: bs(e.to(dev), w.to(dev)))
-            finally:
-                lib.sbk_prof_set_knob(47, 1)
-            assert "decoder_step_persist" not in rep0 and ("self_attn_step" in rep0 or "self_attn_anc" in rep0), (tag, sorted(rep0))
-            assert hyps0 == hyps and float((sc0 - sc).abs().max()) <= 2e-5, tag
-        # another grid: fewer workgroups than column tiles / attention items (every loop over tiles and items runs more than once)
-        e, w = enc[:1], wl[:1]
-        bs = searcher(10, 8.5 / 30)
-        base = bs(e.to(dev), w.to(dev))
-        for grid in (3, 1000):
-            lib.sbk_prof_set_knob(48, grid)
-            try:
-                got = bs(e.to(dev), w.to(dev))
-            finally:
-                lib.sbk_prof_set_knob(48, 128)
-            assert got[0] == base[0] and torch.equal(got[2], base[2]), grid  # (the arithmetic does not depend on the grid)
-        # the grid barriers on a two-level arrival counter (knob 59): the same results, grid sizes with full, ragged and single sub-counters
-        keep59 = lib.sbk_prof_get_knob(59)
-        try:
-            lib.sbk_prof_set_knob(59, 1)
-            for grid in (128, 3, 13, 1000):
-                lib.sbk_prof_set_knob(48, grid)
-                got = bs(e.to(dev), w.to(dev))
-                assert got[0] == base[0] and torch.equal(got[2], base[2]), ("tree", grid)
-        finally:
-            lib.sbk_prof_set_knob(59, keep59)
-            lib.sbk_prof_set_knob(48, 128)
-        gs = S2STransformerGreedySearcher(modules=[mods["Transformer"], mods["seq_lin"]], bos_index=1, eos_index=2, min_decode_ratio=0.0,
-                                          max_decode_ratio=8.5 / 30)
-        (g_h, _, g_s, _), rep = run(lambda: gs(enc.to(dev), wl.to(dev)))
-        assert rep.get("decoder_step_persist", {}).get("count", 0) >= 1, sorted(rep)
-        ref_g = O.greedy_search(enc, wl, sd, cfg, O.SearchCfg(beam=1, max_decode_ratio=8.5 / 30))
-        assert g_h == ref_g[0]
-    finally:
-        lib.sbk_prof_set_knob(47, 1)
-        lib.sbk_prof_set_knob(48, 128)
+    enc = torch.randn(3, 30, dm, generator=gen)
+    wl = torch.tensor([1.0, 0.7, 0.9])
+    enc_len = torch.round(30 * wl).int()
+    tgt = torch.randint(0, 60, (3, 6), generator=gen)
+    h = nat.DecoderHandle(mods["Transformer"], mods["seq_lin"])
+    pred, rep = run(lambda: nat.decoder_prefix(h, tgt.int().to(dev), enc.to(dev), enc_len.to(dev)))
+    assert rep.get("decoder_step_persist", {}).get("count", 0) == tgt.shape[1] and "self_attn_step" not in rep, sorted(rep)
+    assert float((pred.cpu() - O.decode(tgt, enc, enc_len, sd, cfg, "Transformer.")).abs().max()) <= 5e-5
+    cases = [("one utterance, beam 10", enc[:1], wl[:1], 10, 8.5 / 30), ("three utterances, beam 4", enc, wl, 4, 8.5 / 30)]
+    if shape == "d128":
+        long_enc = torch.randn(1, 300, dm, generator=gen)
+        cases += [("one utterance, beam 16", enc[1:2], torch.ones(1), 16, 6.5 / 30),
+                  ("300-frame memory", long_enc, torch.tensor([0.93]), 10, 6.5 / 300)]
+    for tag, e, w, beam, ratio in cases:
+        ref_h, _, ref_s, _ = O.beam_search(e, w, sd, cfg, O.SearchCfg(beam=beam, ctc_weight=0.4, max_decode_ratio=ratio))
+        bs = searcher(beam, ratio)
+        (hyps, _, sc, _), rep = run(lambda: bs(e.to(dev), w.to(dev)))
+        assert rep.get("decoder_step_persist", {}).get("count", 0) >= 1 and "cross_attn_step" not in rep and "gemm_skinny_ln" not in rep, (tag, sorted(rep))
+        assert hyps == ref_h, tag
+        assert float((sc.cpu() - ref_s).abs().max()) <= 1e-4, tag
+        with nat.knobs(persist=0):
+            (hyps0, _, sc0, _), rep0 = run(lambda: bs(e.to(dev), w.to(dev)))
+        assert "decoder_step_persist" not in rep0 and ("self_attn_step" in rep0 or "self_attn_anc" in rep0), (tag, sorted(rep0))
+        assert hyps0 == hyps and float((sc0 - sc).abs().max()) <= 2e-5, tag
+    # another grid: fewer workgroups than column tiles / attention items (every loop over tiles and items runs more than once)
+    e, w = enc[:1], wl[:1]
+    bs = searcher(10, 8.5 / 30)
+    base = bs(e.to(dev), w.to(dev))
+    for grid in (3, 1000):
+        with nat.knobs(persist_grid=grid):
+            got = bs(e.to(dev), w.to(dev))
+        assert got[0] == base[0] and torch.equal(got[2], base[2]), grid  # (the arithmetic does not depend on the grid)
+    # the grid barriers on a two-level arrival counter (persist_tree): the same results, grid sizes with full, ragged and single sub-counters
+    for grid in (128, 3, 13, 1000):
+        with nat.knobs(persist_tree=1, persist_grid=grid):
+            got = bs(e.to(dev), w.to(dev))
+        assert got[0] == base[0] and torch.equal(got[2], base[2]), ("tree", grid)
+    gs = S2STransformerGreedySearcher(modules=[mods["Transformer"], mods["seq_lin"]], bos_index=1, eos_index=2, min_decode_ratio=0.0,
+                                      max_decode_ratio=8.5 / 30)
+    (g_h, _, g_s, _), rep = run(lambda: gs(enc.to(dev), wl.to(dev)))
+    assert rep.get("decoder_step_persist", {}).get("count", 0) >= 1, sorted(rep)
+    ref_g = O.greedy_search(enc, wl, sd, cfg, O.SearchCfg(beam=1, max_decode_ratio=8.5 / 30))
+    assert g_h == ref_g[0]
 
 
 @pytest.mark.parametrize("ln", [1, 0])
@@ -361,9 +344,9 @@ def test_decoder_on_the_x3r_route_vs_oracle(backend, ln):
     """The decode step's projections as sbk_gemm_nt_x3r (csrc/gemm.hip: gemm_x3r_kernel -- fp32 results on the bf16
     matrix pipe from the panel images of the decoder's weights; the route of every step with ~200 hypothesis rows or
     more): d_model 256 / d_ffn 512 are eligible widths (K % 256 == 0), the row threshold is lowered so that this small
-    search takes it (knob 42).  Teacher-forced decoder outputs 5e-5 and a beam search with CTC (ids exact, scores 1e-4)
+    search takes it (x3r_min_rows).  Teacher-forced decoder outputs 5e-5 and a beam search with CTC (ids exact, scores 1e-4)
     against the oracle; with norm1 / norm2 / norm3 and decoder.norm inside the projections they feed (sbk_gemm_ln_nt_x3r,
-    knob 45 = 1: the default -- the profiler's launch names show which route ran) and as launches of their own (0); the
+    x3r_ln = 1: the default -- the profiler's launch names show which route ran) and as launches of their own (0); the
     result does not change when the route is switched off."""
     nat, dev = backend
     from speechbrain_amd.decoders import CTCScorer, S2STransformerBeamSearcher, ScorerBuilder
@@ -385,63 +368,54 @@ def test_decoder_on_the_x3r_route_vs_oracle(backend, ln):
     wl = torch.tensor([1.0, 0.7, 0.9])
     enc_len = torch.round(30 * wl).int()
     tgt = torch.randint(0, 60, (3, 6), generator=gen)
-    lib = nat.load()
-    lib.sbk_prof_set_knob(45, ln)
-    lib.sbk_prof_set_knob(42, 1)
-    lib.sbk_prof_set_knob(47, 0)  # (12 rows: without it the step would be the persistent few-row launch, csrc/decoder_persist.hip)
-    try:
-        h = nat.DecoderHandle(mods["Transformer"], mods["seq_lin"])
-        assert h.layers[0].sa_in_wp and h.layers[0].ff2_wp and h.W.seq_wp  # the panel images exist for these widths
-        assert h.layers[0].sa_in_wfp and h.layers[0].ca_q_wfp and h.layers[0].ff1_wfp and h.W.seq_wfp  # and the folded ones
-        nat.prof_reset()
-        nat.prof_enable(True)
-        pred = nat.decoder_prefix(h, tgt.int().to(dev), enc.to(dev), enc_len.to(dev))
-        nat.prof_enable(False)
-        rep = nat.prof_report()
-        fused = rep.get("gemm_ln_x3r", {}).get("count", 0)
-        assert ("gemm_ln_x3r" in rep) == (ln == 1), sorted(rep)
-        # fused: three per layer and position; the LayerNorm launches left are decoder.norm, whose rows are this entry's result
-        norms = rep.get("layernorm", {}).get("count", 0)
-        assert (fused == 6 * tgt.shape[1] and norms == tgt.shape[1]) if ln else fused == 0, (fused, norms)
-        assert float((pred.cpu() - O.decode(tgt, enc, enc_len, sd, cfg, "Transformer.")).abs().max()) <= 5e-5
-        ratio = 8.5 / 30
-        hyps_ref, _, sc_ref, _ = O.beam_search(enc, wl, sd, cfg, O.SearchCfg(beam=4, ctc_weight=0.4, max_decode_ratio=ratio))
-        scorer = ScorerBuilder(full_scorers=[CTCScorer(ctc_fc=mods["ctc_lin"], blank_index=0, eos_index=2)], weights={"ctc": 0.4})
-        bs = S2STransformerBeamSearcher(modules=[mods["Transformer"], mods["seq_lin"]], bos_index=1, eos_index=2,
-                                        min_decode_ratio=0.0, max_decode_ratio=ratio, beam_size=4,
-                                        using_eos_threshold=False, length_normalization=True, scorer=scorer)
-        nat.prof_reset()
-        nat.prof_enable(True)
-        hyps, _, sc, _ = bs(enc.to(dev), wl.to(dev))
-        nat.prof_enable(False)
-        rep = nat.prof_report()
-        if ln:  # a search step: every LayerNorm of the decoder, decoder.norm included, inside a projection
-            assert rep["gemm_ln_x3r"]["count"] % 6 == 0 and "layernorm" not in rep, sorted(rep)  # (decoder.norm: the few-row fused kernel at 12 rows)
-        assert hyps == hyps_ref
-        assert float((sc.cpu() - sc_ref).abs().max()) <= 1e-4
-        if ln:
-            # decoder.norm inside the vocabulary projection as well: at bench sizes (1 280 rows x 5 000 tokens) the few-row
-            # fused kernel does not take that shape; here it is switched off (knob 2) so that this small search takes the route
-            lib.sbk_prof_set_knob(2, 1)
-            try:
-                nat.prof_reset()
-                nat.prof_enable(True)
-                hyps_v, _, sc_v, _ = bs(enc.to(dev), wl.to(dev))
-                nat.prof_enable(False)
-                rep = nat.prof_report()
-            finally:
-                lib.sbk_prof_set_knob(2, 0)
-            assert rep["gemm_ln_x3r"]["count"] % 7 == 0 and "layernorm" not in rep, sorted(rep)
-            assert hyps_v == hyps_ref and float((sc_v.cpu() - sc_ref).abs().max()) <= 1e-4
-        lib.sbk_prof_set_knob(41, 0)  # the fp32-MFMA route of the same handle
-        hyps0, _, sc0, _ = bs(enc.to(dev), wl.to(dev))
-        assert hyps0 == hyps and float((sc0 - sc).abs().max()) <= 1e-4
-    finally:
-        nat.prof_enable(False)
-        lib.sbk_prof_set_knob(41, 2)
-        lib.sbk_prof_set_knob(45, 1)
-        lib.sbk_prof_set_knob(42, 192)
-        lib.sbk_prof_set_knob(47, 1)
+    # (persist: at 12 rows the step would otherwise be the persistent few-row launch, csrc/decoder_persist.hip)
+    with nat.knobs(x3r_ln=ln, x3r_min_rows=1, persist=0):
+        try:
+            h = nat.DecoderHandle(mods["Transformer"], mods["seq_lin"])
+            assert h.layers[0].sa_in_wp and h.layers[0].ff2_wp and h.W.seq_wp  # the panel images exist for these widths
+            assert h.layers[0].sa_in_wfp and h.layers[0].ca_q_wfp and h.layers[0].ff1_wfp and h.W.seq_wfp  # and the folded ones
+            nat.prof_reset()
+            nat.prof_enable(True)
+            pred = nat.decoder_prefix(h, tgt.int().to(dev), enc.to(dev), enc_len.to(dev))
+            nat.prof_enable(False)
+            rep = nat.prof_report()
+            fused = rep.get("gemm_ln_x3r", {}).get("count", 0)
+            assert ("gemm_ln_x3r" in rep) == (ln == 1), sorted(rep)
+            # fused: three per layer and position; the LayerNorm launches left are decoder.norm, whose rows are this entry's result
+            norms = rep.get("layernorm", {}).get("count", 0)
+            assert (fused == 6 * tgt.shape[1] and norms == tgt.shape[1]) if ln else fused == 0, (fused, norms)
+            assert float((pred.cpu() - O.decode(tgt, enc, enc_len, sd, cfg, "Transformer.")).abs().max()) <= 5e-5
+            ratio = 8.5 / 30
+            hyps_ref, _, sc_ref, _ = O.beam_search(enc, wl, sd, cfg, O.SearchCfg(beam=4, ctc_weight=0.4, max_decode_ratio=ratio))
+            scorer = ScorerBuilder(full_scorers=[CTCScorer(ctc_fc=mods["ctc_lin"], blank_index=0, eos_index=2)], weights={"ctc": 0.4})
+            bs = S2STransformerBeamSearcher(modules=[mods["Transformer"], mods["seq_lin"]], bos_index=1, eos_index=2,
+                                            min_decode_ratio=0.0, max_decode_ratio=ratio, beam_size=4,
+                                            using_eos_threshold=False, length_normalization=True, scorer=scorer)
+            nat.prof_reset()
+            nat.prof_enable(True)
+            hyps, _, sc, _ = bs(enc.to(dev), wl.to(dev))
+            nat.prof_enable(False)
+            rep = nat.prof_report()
+            if ln:  # a search step: every LayerNorm of the decoder, decoder.norm included, inside a projection
+                assert rep["gemm_ln_x3r"]["count"] % 6 == 0 and "layernorm" not in rep, sorted(rep)  # (decoder.norm: the few-row fused kernel at 12 rows)
+            assert hyps == hyps_ref
+            assert float((sc.cpu() - sc_ref).abs().max()) <= 1e-4
+            if ln:
+                # decoder.norm inside the vocabulary projection as well: at bench sizes (1 280 rows x 5 000 tokens) the few-row
+                # fused kernel does not take that shape; here it is switched off (skinny_off) so that this small search takes the route
+                with nat.knobs(skinny_off=1):
+                    nat.prof_reset()
+                    nat.prof_enable(True)
+                    hyps_v, _, sc_v, _ = bs(enc.to(dev), wl.to(dev))
+                    nat.prof_enable(False)
+                    rep = nat.prof_report()
+                assert rep["gemm_ln_x3r"]["count"] % 7 == 0 and "layernorm" not in rep, sorted(rep)
+                assert hyps_v == hyps_ref and float((sc_v.cpu() - sc_ref).abs().max()) <= 1e-4
+            with nat.knobs(x3r_mode=0):  # the fp32-MFMA route of the same handle
+                hyps0, _, sc0, _ = bs(enc.to(dev), wl.to(dev))
+            assert hyps0 == hyps and float((sc0 - sc).abs().max()) <= 1e-4
+        finally:
+            nat.prof_enable(False)
 
 
 def build_lm(g, dev):
@@ -639,17 +613,11 @@ def test_cross_attention_kernel_variants(backend, nhead, rows):
     bs = S2STransformerBeamSearcher(modules=[mods["Transformer"], mods["seq_lin"]], bos_index=1, eos_index=2,
                                     min_decode_ratio=0.0, max_decode_ratio=ratio, beam_size=5,
                                     using_eos_threshold=False, length_normalization=True)
-    nat.load().sbk_prof_set_knob(4, 0)
-    nat.load().sbk_prof_set_knob(8, {3: 1, 4: 2}.get(rows, 0))  # 3 / 4 = 256- / 64-frame splits
-    nat.load().sbk_prof_set_knob(47, 0)  # (15 rows: not the persistent few-row step, which has its own attention)
-    try:
+    # cross_fc256: 3 / 4 = 256- / 64-frame splits; persist: 15 rows would otherwise run as the persistent few-row step, which has its own attention
+    with nat.knobs(cross_rows=0, cross_fc256={3: 1, 4: 2}.get(rows, 0), persist=0):
         h = nat.DecoderHandle(mods["Transformer"], mods["seq_lin"])
         pred = nat.decoder_prefix(h, tgt.int().to(dev), enc.to(dev), enc_len.to(dev))
         hyps, _, sc, _ = bs(enc.to(dev), wl.to(dev))  # several beams per (utterance, head) workgroup
-    finally:
-        nat.load().sbk_prof_set_knob(4, 7)
-        nat.load().sbk_prof_set_knob(8, 0)
-        nat.load().sbk_prof_set_knob(47, 1)
     assert float((pred.cpu() - O.decode(tgt, enc, enc_len, sd, cfg, "Transformer.")).abs().max()) <= 5e-5
     hyps_ref, _, sc_ref, _ = O.beam_search(enc, wl, sd, cfg, O.SearchCfg(beam=5, max_decode_ratio=ratio))
     assert hyps == hyps_ref
@@ -1110,17 +1078,11 @@ def test_search_projections_on_the_split_operand_kernel(backend):
     lens = torch.tensor([1.0, 0.7, 0.9])
     h = asr.mods.decoder._handle()
     assert h.W.seq_w3 and all(h.layers[l].ca_kv_w3 for l in range(2))
-    lib = nat.load()
     dec = asr.mods.decoder
     enc = asr.encode_batch(wav, lens)
     ref = dec(enc, lens.to(dev))  # thresholds at their defaults: the fp32-MFMA kernels
-    lib.sbk_prof_set_knob(34, 1)
-    lib.sbk_prof_set_knob(35, 1)
-    try:
+    with nat.knobs(x3_route_rows=1, x3_route_tiles=1):
         got = dec(enc, lens.to(dev))
-    finally:
-        lib.sbk_prof_set_knob(34, 1024)
-        lib.sbk_prof_set_knob(35, 192)
     assert got[0] == ref[0]
     assert float((got[1].cpu() - ref[1].cpu()).abs().max()) <= 1e-4
     sd = flat_state_dict(asr)
@@ -1135,7 +1097,7 @@ def test_search_projections_on_the_split_operand_kernel(backend):
 def test_fused_scoring_equals_separate_kernels(backend, tag):
     """The step's scoring as ONE pass per hypothesis row (csrc/search.hip:score_topk_row_kernel: log-softmax, eos rules,
     scorer combination, candidate values and the row's top-`beam` from registers; the default) against the launches it
-    replaces (log_softmax_row / row_max / ctc_combine or am_only / beam_topk_stage1; knob 40 = 0): every expression and
+    replaces (log_softmax_row / row_max / ctc_combine or am_only / beam_topk_stage1; score_fused = 0): every expression and
     reduction order is the same, so hypotheses, scores and per-token log-probs must be IDENTICAL, bit for bit -- with
     the CTC scorer, with the eos threshold and without a scorer, with the LM scorer in front of CTC, for top-k lists
     and in a grouped search with per-utterance step limits."""
@@ -1168,14 +1130,10 @@ def test_fused_scoring_equals_separate_kernels(backend, tag):
         with torch.no_grad():
             return bs(enc, wl)
 
-    lib = nat.load()
     out = {}
-    try:
-        for fused in (1, 0):
-            lib.sbk_prof_set_knob(40, fused)
+    for fused in (1, 0):
+        with nat.knobs(score_fused=fused):
             out[fused] = (run(), run(return_topk=True, topk=min(3, beam)), run(temperature=1.7))
-    finally:
-        lib.sbk_prof_set_knob(40, 1)
     for run_no, (a, b) in enumerate(zip(out[1], out[0])):
         for out_no, (x, y) in enumerate(zip(a, b)):
             if torch.is_tensor(x):
@@ -1204,15 +1162,10 @@ def test_fused_scoring_large_vocabulary(backend, vocab):
     bs = S2STransformerBeamSearcher(modules=[mods["Transformer"], mods["seq_lin"]], bos_index=1, eos_index=2,
                                     min_decode_ratio=0.0, max_decode_ratio=0.3, beam_size=10, using_eos_threshold=True,
                                     length_normalization=True, scorer=scorer, return_topk=True, topk=4)
-    lib = nat.load()
     out = {}
-    try:
-        for fused in (1, 0):
-            lib.sbk_prof_set_knob(40, fused)
-            with torch.no_grad():
-                out[fused] = bs(enc, wl)
-    finally:
-        lib.sbk_prof_set_knob(40, 1)
+    for fused in (1, 0):
+        with nat.knobs(score_fused=fused), torch.no_grad():
+            out[fused] = bs(enc, wl)
     for x, y in zip(out[1], out[0]):
         assert torch.equal(x.cpu(), y.cpu()) if torch.is_tensor(x) else x == y
     assert int(out[1][0].max()) > 2  # (something was decoded)

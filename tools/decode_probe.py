@@ -26,8 +26,9 @@ args = ap.parse_args()
 
 dev = torch.device("cuda:0")
 native.load()
-for kv in args.knob:
-    native.load().sbk_prof_set_knob(*[int(v) for v in kv.split("=")])
+for kv in args.knob:  # a name of native.KNOBS or a key number
+    key, value = kv.split("=")
+    native.load().sbk_prof_set_knob(int(key) if key.isdigit() else native.KNOBS[key], int(value))
 asr = build_asr("L", vocab=5000, seed=0, beam_size=10, ctc_weight=0.4, device="cuda:0")
 dec = asr.mods.decoder
 g = torch.Generator().manual_seed(3)

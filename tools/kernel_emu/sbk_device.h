@@ -403,10 +403,6 @@ static inline float gelu_erfc(float x) {  // (the device version's formula; its 
   const float q = (p * t) * exp2f(-1.44269504088896340736f * (z * z));
   return (0.5f * x) * (x >= 0.0f ? 2.0f - q : q);
 }
-template <class T>
-static inline void keep(const T&) {}
-template <class T>
-static inline T opaque_zero() { T t; memset(&t, 0, sizeof(T)); return t; }
 static inline float exp2_raw(float x) { return exp2f(x); }
 static inline bool wave_any(bool p) {  // (every fiber of the wave calls it)
   int v = p ? 1 : 0;
@@ -419,11 +415,8 @@ template <bool NT>
 static inline float ld4(const float* p) { return *p; }
 template <int MASK, int SIZE>
 static inline void sched_group() {}
-template <int P>
-static inline void set_prio() {}
 static inline void pin(unsigned&) {}
 static inline void pin(float&) {}
-static inline void pin(f32x16&) {}
 static inline void vm_drain() {}
 static inline void vm_drain_visible() {}
 static inline void lds_drain() {}

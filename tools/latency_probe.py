@@ -1,8 +1,8 @@
 """Single-utterance latency (B = 1, 10 s, 40 decoding steps, beam 10 + CTC: the bench's p50 case) with the decode step as the
-persistent few-row launch (csrc/decoder_persist.hip, knob 47) or as launches per operation -- wall clock per call, the search
+persistent few-row launch (csrc/decoder_persist.hip, knob persist) or as launches per operation -- wall clock per call, the search
 alone from a fixed encoder output, and (--report) HIP-event time per kernel class.
 
-    python tools/latency_probe.py [--runs 7] [--knob 47=0] [--knob 48=64] [--overlap 0|3] [--report]
+    python tools/latency_probe.py [--runs 7] [--knob persist=0] [--knob persist_grid=64] [--overlap 0|3] [--report]
 """
 import argparse
 import os
@@ -21,14 +21,15 @@ ap.add_argument("--seconds", type=float, default=10.0)
 ap.add_argument("--overlap", type=int, default=0)
 ap.add_argument("--graph", type=int, default=0)
 ap.add_argument("--report", action="store_true")
-ap.add_argument("--stamps", action="store_true", help="phase times of the last persistent step of a search (knob 49)")
-ap.add_argument("--knob", action="append", default=[])
+ap.add_argument("--stamps", action="store_true", help="phase times of the last persistent step of a search (knob persist_stamps)")
+ap.add_argument("--knob", action="append", default=[], metavar="KEY=VALUE", help="KEY: a name of native.KNOBS or a key number")
 args = ap.parse_args()
 
 dev = torch.device("cuda:0")
 lib = native.load()
 for kv in args.knob:
-    lib.sbk_prof_set_knob(*[int(v) for v in kv.split("=")])
+    key, value = kv.split("=")
+    lib.sbk_prof_set_knob(int(key) if key.isdigit() else native.KNOBS[key], int(value))
 asr = build_asr("L", vocab=5000, seed=0, beam_size=10, ctc_weight=0.4, device="cuda:0")
 dec = asr.mods.decoder
 dec.overlap_ctc, dec.graph_mode = args.overlap, args.graph
@@ -72,10 +73,9 @@ with torch.no_grad(), torch.cuda.stream(st):
     if args.stamps:
         import ctypes
 
-        lib.sbk_prof_set_knob(49, 1)
-        dec(enc, ldev)
-        torch.cuda.synchronize()
-        lib.sbk_prof_set_knob(49, 0)
+        with native.knobs(persist_stamps=1):
+            dec(enc, ldev)
+            torch.cuda.synchronize()
         buf = (ctypes.c_longlong * 256)()
         n = lib.sbk_prof_persist_stamps(buf, 256)
         t = [buf[i] * 0.01 for i in range(n)]  # 100 MHz ticks -> us

@@ -69,10 +69,10 @@ if __name__ == "__main__":
             P = torch.randn(2 * T - 1, d, device=dev)
             u = torch.randn(d, device=dev) * 0.1
             kl = torch.full((B,), T, dtype=torch.int32, device=dev)
-            nat.load().sbk_prof_set_knob(60, 0)  # softmax weights through libm's expf (before round 6)
-            t_rel0 = timeit(lambda: nat.relpos_attention(qkv, P, u, u, kl, H, 1 / math.sqrt(d)), n=20, warm=3)
-            nat.load().sbk_prof_set_knob(60, 1)  # 2^(.) on one v_exp_f32 + the rescale skipped when no lane has a new maximum (default)
-            t_rel = timeit(lambda: nat.relpos_attention(qkv, P, u, u, kl, H, 1 / math.sqrt(d)), n=20, warm=3)
+            with nat.knobs(attn_exp2=0):  # softmax weights through libm's expf (before round 6)
+                t_rel0 = timeit(lambda: nat.relpos_attention(qkv, P, u, u, kl, H, 1 / math.sqrt(d)), n=20, warm=3)
+            with nat.knobs(attn_exp2=1):  # 2^(.) on one v_exp_f32 + the rescale skipped when no lane has a new maximum (default)
+                t_rel = timeit(lambda: nat.relpos_attention(qkv, P, u, u, kl, H, 1 / math.sqrt(d)), n=20, warm=3)
             t_rope = timeit(lambda: nat.rope_attention(qkv, tab.cosines, tab.sines, kl, H, 1 / math.sqrt(d)), n=20, warm=3)
             fl = B * H * T * T * Dh
             print(f"attn B={B} T={T}: relpos {t_rel:8.1f} us {6.0*fl/t_rel/1e6:6.1f} TF/s (expf form {t_rel0:8.1f} us) | rope {t_rope:8.1f} us {4.0*fl/t_rope/1e6:6.1f} TF/s", flush=True)
@@ -81,23 +81,20 @@ if __name__ == "__main__":
         print("decode-step GEMMs: register-operand 32x32 tiles (skinny) vs LDS-tiled")
         for M in (320, 640, 1280):
             for (N, K) in [(512, 512), (1536, 512), (2048, 512), (512, 2048), (5000, 512)]:
-                nat.load().sbk_prof_set_knob(2, 0)
-                gemm_case(M, N, K, 8)
-                nat.load().sbk_prof_set_knob(2, 1)
-                gemm_case(M, N, K, 8)
-        nat.load().sbk_prof_set_knob(2, 0)
+                for off in (0, 1):
+                    with nat.knobs(skinny_off=off):
+                        gemm_case(M, N, K, 8)
         sys.exit(0)
     # (Modes that toggled knobs removed in round 5 -- --enc-gemm, --relpos-t, --attn2, --k512, --skinny, --sk, --sk64, --pmc-decode,
     #  --flat64, the tile / grid / measurement-mode columns of --x3p / --x3 / --bf16a -- went with the kernels they compared: their
     #  logs are under profiles/r02_* .. r04_*.)
     if "--ffn2" in sys.argv:  # few rows, K = 2048: register-operand split-K (default) vs 64x64 LDS tiles with a 4-way K split
         for knob in (0, 1):
-            nat.load().sbk_prof_set_knob(14, knob)
             print("K = 2048 path:", "64x64 LDS tiles, 4-way K split" if knob else "register-operand tiles")
-            for M in (10, 40, 80, 160, 320, 640, 1280, 2560):
-                gemm_case(M, 512, 2048, 8)
-            gemm_case(1280, 768, 3072, 8)
-        nat.load().sbk_prof_set_knob(14, 0)
+            with nat.knobs(tiled_splitk=knob):
+                for M in (10, 40, 80, 160, 320, 640, 1280, 2560):
+                    gemm_case(M, 512, 2048, 8)
+                gemm_case(1280, 768, 3072, 8)
         sys.exit(0)
     if "--stream" in sys.argv:  # hand-written float4 streaming kernels of the library (sbk_prof_stream_f32): the HBM calibration
         for mb in (64, 256, 1024, 4096):
@@ -115,14 +112,12 @@ if __name__ == "__main__":
     if "--enc-layer" in sys.argv:  # the Conformer-L encoder in situ (32 utterances x 5 / 10 / 20 / 30 s): per-kernel event times by GEMM routing
         from speechbrain_amd.inference.builders import build_asr
         asr = build_asr("L", vocab=5000, seed=0, device="cuda:0")
-        variants = (("tile grid", {18: 0}), ("routed (default)", {18: 1}))
+        variants = (("tile grid", 0), ("routed (default)", 1))
         for sec in (5, 10, 20, 30):
             wav = (0.1 * torch.randn(32, sec * 16000, generator=torch.Generator().manual_seed(sec))).to(dev)
             lens = torch.ones(32, device=dev)
-            for tag, knobs in variants:
-                for k, v in knobs.items():
-                    nat.load().sbk_prof_set_knob(k, v)
-                with torch.no_grad():
+            for tag, sk_mode in variants:
+                with torch.no_grad(), nat.knobs(sk_mode=sk_mode):
                     for _ in range(2):
                         asr.encode_batch(wav, lens)
                     torch.cuda.synchronize()
@@ -137,7 +132,6 @@ if __name__ == "__main__":
                 gms, gfl = sum(v["ms"] for v in gem.values()), sum(v["flops"] for v in gem.values())
                 print(f"enc 32x{sec}s {tag:18s}: all kernels {tot / 3:8.2f} ms | GEMMs {gms / 3:8.2f} ms {gfl / gms / 1e9:6.1f} TF/s |",
                       {k: (round(v["ms"] / 3, 2), round(v["flops"] / v["ms"] / 1e9, 1)) for k, v in gem.items()}, flush=True)
-        nat.load().sbk_prof_set_knob(18, 1)
         sys.exit(0)
     if "--enc-bf16" in sys.argv:  # Conformer-L encoder under precision bf16: bf16 activations in memory (feed-forward pairs) vs fp32 activations rounded on load
         from speechbrain_amd.inference.builders import build_asr
@@ -176,30 +170,26 @@ if __name__ == "__main__":
                 rc = nat.load().sbk_prof_mfma_peak_f32(nat._p(sink), wgs, 20000, rnd, ctypes.byref(tf), nat._stream(sink))
                 assert rc == 0
                 print(f"mfma peak: {wgs} workgroups x 4 waves, {'random' if rnd else 'zero'} operands: {tf.value:7.1f} TFLOP/s", flush=True)
-        for tag, knobs in (("stream-K", {18: 1}), ("tile grid", {18: 0})):
-            for k, v in knobs.items():
-                nat.load().sbk_prof_set_knob(k, v)
+        for tag, mode in (("stream-K", 1), ("tile grid", 0)):
             print("variant:", tag, flush=True)
-            for (M, N, K) in [(56064, 2048, 512), (56064, 512, 2048), (56064, 512, 512)]:
-                gemm_case(M, N, K, 0, iters=30)
-        nat.load().sbk_prof_set_knob(18, 1)
+            with nat.knobs(sk_mode=mode):
+                for (M, N, K) in [(56064, 2048, 512), (56064, 512, 2048), (56064, 512, 512)]:
+                    gemm_case(M, N, K, 0, iters=30)
         print("zero-filled operands (DVFS give-back), stream-K then tile grid")
         for mode in (1, 0):
-            nat.load().sbk_prof_set_knob(18, mode)
             for (M, N, K) in [(56064, 2048, 512), (56064, 512, 2048)]:
                 a = torch.zeros(M, K, device=dev); w = torch.zeros(N, K, device=dev); out = torch.empty(M, N, device=dev)
                 us = ctypes.c_float(0)
-                rc = nat.load().sbk_prof_gemm_repeat_f32(nat._p(a), nat._p(w), nat._p(out), M, N, K, None, 0, 30, ctypes.byref(us), nat._stream(a))
+                with nat.knobs(sk_mode=mode):
+                    rc = nat.load().sbk_prof_gemm_repeat_f32(nat._p(a), nat._p(w), nat._p(out), M, N, K, None, 0, 30, ctypes.byref(us), nat._stream(a))
                 assert rc == 0
                 print(f"gemm zeros M={M} N={N} K={K}: {us.value:8.2f} us  {2.0*M*N*K/us.value/1e6:7.2f} TFLOP/s", flush=True)
-        nat.load().sbk_prof_set_knob(18, 1)
         sys.exit(0)
     if "--sk-pmc" in sys.argv:  # short: the two big-GEMM kernels for a counters pass
         for mode in (1, 0):
-            nat.load().sbk_prof_set_knob(18, mode)
-            for (M, N, K) in [(56064, 2048, 512), (56064, 512, 2048), (12800, 2048, 512)]:
-                gemm_case(M, N, K, 0, iters=5)
-        nat.load().sbk_prof_set_knob(18, 1)
+            with nat.knobs(sk_mode=mode):
+                for (M, N, K) in [(56064, 2048, 512), (56064, 512, 2048), (12800, 2048, 512)]:
+                    gemm_case(M, N, K, 0, iters=5)
         sys.exit(0)
     if "--x3-pmc" in sys.argv:  # short: the split-operand kernel at a bench-sized shape for a counters pass
         nat.F32X3, nat.F32X3_MIN_ROWS, nat.F32X3_MIN_TILES = True, 1, 1
@@ -294,7 +284,7 @@ if __name__ == "__main__":
             t2 = ev_time(lambda: nat.layernorm_x3p(x, g, b, 1e-5))
             print(f"ln-x3p M={M} d=512: layernorm {t0:6.1f} us ({8.0*M*512/t0/1e3:5.0f} GB/s) + split {t1:6.1f} us | layernorm_x3p {t2:6.1f} us ({10.0*M*512/t2/1e3:5.0f} GB/s)", flush=True)
         sys.exit(0)
-    if "--x3p-modes" in sys.argv:  # measurement builds of gemm_nt_x3p_kernel (key 64) at the encoder's shapes
+    if "--x3p-epi" in sys.argv:  # gemm_nt_x3p's epilogue at the encoder's shapes: the generic form / the straight-line forms (x3p_fast_epi)
         def ev_time(fn, n=20):
             fn(); fn()
             torch.cuda.synchronize()
@@ -305,8 +295,6 @@ if __name__ == "__main__":
             e1.record()
             torch.cuda.synchronize()
             return e0.elapsed_time(e1) * 1e3 / n
-        lib = nat.load()
-        names = {0: "kernel", 1: "no LDS-DMA in the loop", 2: "no MFMAs", 4: "no epilogue", 8: "no fragment fetches"}
         for (M, N, K, act, res, pout) in [(56064, 2048, 512, nat.ACT_SWISH, False, True), (56064, 512, 2048, nat.ACT_NONE, True, False),
                                           (56064, 1536, 512, nat.ACT_NONE, False, False), (56064, 512, 512, nat.ACT_NONE, True, False),
                                           (14016, 2048, 512, nat.ACT_SWISH, False, True), (14016, 512, 2048, nat.ACT_NONE, True, False)]:
@@ -316,22 +304,16 @@ if __name__ == "__main__":
             fn = (lambda: nat.gemm_nt_x3p(pa, w, b, r, act=act, alpha=0.5, panel_out=True, fp32_out=False)) if pout else \
                  (lambda: nat.gemm_nt_x3p(pa, w, b, r, act=act, alpha=0.5))
             line = f"x3p M={M} N={N} K={K} act={act}{' + residual' if res else ''}{' -> panel' if pout else ''}:"
-            modes = (0, 0) if "--x3p-epi" in sys.argv else (0, 1, 2, 4, 8, 0)
             outs = []
-            for fe in ((0, 1, 0, 1) if "--x3p-epi" in sys.argv else (1,)):  # key 63: the generic epilogue / the straight-line forms
-                lib.sbk_prof_set_knob(63, fe)
-                if "--x3p-epi" in sys.argv:
-                    line += f"  | key 63 = {fe}:"
+            for fe in (0, 1, 0, 1):
+                with nat.knobs(x3p_fast_epi=fe):
                     o = fn()
                     outs.append(o.data.clone() if hasattr(o, "data") and not torch.is_tensor(o) else o.clone())
-                for mode in modes:
-                    lib.sbk_prof_set_knob(64, mode)
-                    t = ev_time(fn)
-                    line += f"  [{names[mode]}] {t:6.1f} us"
-            lib.sbk_prof_set_knob(64, 0)
-            lib.sbk_prof_set_knob(63, 1)
-            same = f"  identical: {bool(torch.equal(outs[0], outs[1]))}" if outs else ""
-            print(line + f"  ({2.0*M*N*K/t/1e6:5.1f} TF/s){same}", flush=True)
+                    line += f"  | x3p_fast_epi = {fe}:"
+                    for _ in range(2):
+                        t = ev_time(fn)
+                        line += f" {t:6.1f} us"
+            print(line + f"  ({2.0*M*N*K/t/1e6:5.1f} TF/s)  identical: {bool(torch.equal(outs[0], outs[1]))}", flush=True)
         sys.exit(0)
     if "--x3p" in sys.argv:  # both operands pre-split, panel layout, 256-wide tiles (csrc/gemm_x3p.hip) vs the f32x3 kernel
         def ev_time(fn, n=30):
@@ -421,36 +403,6 @@ if __name__ == "__main__":
             line += f" bf16-A LDS-DMA kernel: {t32:7.1f} us {2.0*M*N*K/t32/1e6:7.1f} TF/s |"
             print(line, flush=True)
         sys.exit(0)
-    if "--lp256-modes" in sys.argv:  # measurement builds / schedule variants of gemm_nt_lp256_kernel (key 62), bf16 operands
-        def ev_time(fn, n=20):
-            fn(); fn()
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(n):
-                fn()
-            e1.record()
-            torch.cuda.synchronize()
-            return e0.elapsed_time(e1) * 1e3 / n
-        lib = nat.load()
-        names = {0: "kernel", 1: "no LDS-DMA in the loop", 2: "no MFMAs", 4: "no epilogue", 8: "no fragment fetches", 16: "MFMA phase at priority 1",
-                 32: "LDS reads awaited behind the barrier", 48: "both"}
-        for (M, N, K, od, res) in [(12000, 3840, 1280, torch.bfloat16, False), (12000, 1280, 5120, torch.float32, True),
-                                   (12000, 1280, 1280, torch.float32, True), (8192, 8192, 8192, torch.bfloat16, False)]:
-            a = torch.randn(M, K, device=dev).bfloat16(); w = torch.randn(N, K, device=dev) * 0.05
-            b = torch.randn(N, device=dev); r = torch.randn(M, N, device=dev) if res else None
-            fn = lambda: nat.gemm_nt_bf16a(a, w, b, r, out_dtype=od)
-            lib.sbk_prof_set_knob(61, 0)
-            t = ev_time(fn)
-            print(f"M={M} N={N} K={K} out={str(od).replace('torch.', '')}{' + residual' if res else ''}: 128^2 kernel {t:7.1f} us {2.0*M*N*K/t/1e6:7.1f} TF/s", flush=True)
-            lib.sbk_prof_set_knob(61, 2)
-            for mode in (0, 1, 2, 4, 8, 16, 32, 48, 0):
-                lib.sbk_prof_set_knob(62, mode)
-                t = ev_time(fn)
-                print(f"    mode {mode:2d} ({names[mode]}): {t:7.1f} us {2.0*M*N*K/t/1e6:7.1f} TF/s", flush=True)
-            lib.sbk_prof_set_knob(62, 0)
-            lib.sbk_prof_set_knob(61, 1)
-        sys.exit(0)
     if "--lp256-pmc" in sys.argv:  # short: the Whisper layer's four contractions on the 256 x 256 kernel, 6 launches each, for the counters passes
         shapes = [(12000, 3840, 1280, nat.ACT_NONE, torch.bfloat16), (12000, 1280, 1280, nat.ACT_NONE, torch.float32),
                   (12000, 5120, 1280, nat.ACT_GELU, "hidden"), (12000, 1280, 5120, nat.ACT_NONE, torch.float32)]
@@ -467,7 +419,7 @@ if __name__ == "__main__":
                         nat.gemm_nt_bf16a(ab, w, b, r, act=act, out_dtype=torch.bfloat16 if od == "hidden" else od)
                 torch.cuda.synchronize()
         sys.exit(0)
-    if "--lp256" in sys.argv:  # bf16 / e4m3 activation x weight contractions: 128 x 128 tiles (key 61 = 0) vs 256 x 256 (csrc/gemm_lp256.hip)
+    if "--lp256" in sys.argv:  # bf16 / e4m3 activation x weight contractions: 128 x 128 tiles (lp256 = 0) vs 256 x 256 (csrc/gemm_lp256.hip)
         def ev_time(fn, n=20):
             fn(); fn()
             torch.cuda.synchronize()
@@ -478,7 +430,6 @@ if __name__ == "__main__":
             e1.record()
             torch.cuda.synchronize()
             return e0.elapsed_time(e1) * 1e3 / n
-        lib = nat.load()
         # (rows, N, K, activation, output): the four projections of a Whisper large-v3 encoder layer at 8 x 30 s, then Conformer-L's
         if "--lp256-small" in sys.argv:  # where the 256 x 256 route starts to pay: 36 ... 360 tiles (1 / 2 / 4 / 8 x 30 s of Whisper rows)
             small = [(M, N, K, nat.ACT_NONE, od) for M in (1500, 3000, 6000) for (N, K, od) in ((3840, 1280, torch.bfloat16), (1280, 1280, torch.float32), (5120, 1280, "hidden"), (1280, 5120, torch.float32))]
@@ -496,10 +447,9 @@ if __name__ == "__main__":
                              ("fp8a", lambda: nat.gemm_nt_fp8a(aq, w, b, r, act=act, out_dtype="fp8" if od == "hidden" else od))):
                 ts = []
                 for knob in (0, 2):
-                    lib.sbk_prof_set_knob(61, knob)
-                    ts.append(ev_time(fn))
+                    with nat.knobs(lp256=knob):
+                        ts.append(ev_time(fn))
                 line += f"  {name} 128^2 {ts[0]:7.1f} us {2.0*M*N*K/ts[0]/1e6:7.1f} TF/s | 256^2 {ts[1]:7.1f} us {2.0*M*N*K/ts[1]/1e6:7.1f} TF/s;"
-            lib.sbk_prof_set_knob(61, 1)
             print(line, flush=True)
         sys.exit(0)
     if "--copy" in sys.argv:  # what a plain streaming kernel reaches on this box (calibrates the HBM rooflines)
@@ -518,11 +468,10 @@ if __name__ == "__main__":
     print("launch overhead (empty-ish layernorm 4 rows):", end=" ")
     x = torch.randn(4, 512, device=dev); g = torch.ones(512, device=dev); bb = torch.zeros(512, device=dev)
     print(f"{timeit(lambda: nat.layernorm(x, g, bb, 1e-5)):.2f} us")
-    print("decode-step shapes at 320 rows: register-operand (skinny) kernels, then the LDS-tiled ones (knob 2 = 1)")
+    print("decode-step shapes at 320 rows: register-operand (skinny) kernels, then the LDS-tiled ones (skinny_off = 1)")
     for (M, N, K) in [(320, 512, 512), (320, 1536, 512), (320, 2048, 512), (320, 512, 2048), (320, 5000, 512)]:
         gemm_case(M, N, K, 8)
-    nat.load().sbk_prof_set_knob(2, 1)
-    for (M, N, K) in [(320, 512, 512), (320, 1536, 512), (320, 2048, 512), (320, 512, 2048), (320, 5000, 512), (640, 2048, 512), (640, 5000, 512)]:
-        gemm_case(M, N, K, 8)
-    nat.load().sbk_prof_set_knob(2, 0)
+    with nat.knobs(skinny_off=1):
+        for (M, N, K) in [(320, 512, 512), (320, 1536, 512), (320, 2048, 512), (320, 512, 2048), (320, 5000, 512), (640, 2048, 512), (640, 5000, 512)]:
+            gemm_case(M, N, K, 8)
     sys.exit(0)
