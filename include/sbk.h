@@ -474,6 +474,47 @@ int sbk_transducer_greedy_f32(const sbk_transducer_weights* W, const sbk_transdu
                               float* out_pn, float* h, float* c, int32_t* tokens, int32_t* count, float* score, int B, int T,
                               sbk_stream_t stream);
 
+/* ---- transducer beam search (csrc/transducer.hip; additive entries, ABI 11 unchanged) -----------------------------------
+ * TransducerBeamSearcher.transducer_beam_search_decode (decoders/transducer.py:320-476) without a language model, for the
+ * networks of sbk_transducer_weights above.  One workgroup per utterance runs every frame of tn [B,T,J] in one launch; the
+ * rules ("Transducer beam search") in short: a hypothesis is (tokens starting with the blank, an fp32
+ * score, a PN state); its key is score / len(tokens), an fp32 division.  Per frame A = the previous B, B = {}; until
+ * len(B) >= beam_size, or B's best (by key) has score >= state_beam + the score of A's best (by key; the first of equal keys
+ * in list order), A's best is removed and expanded: one PN step on its last token, the joint with tn[b,t], log-softmax with
+ * the greedy kernel's arithmetic (the same bits), the beam_size best tokens in torch.topk's order (NaN first, then by value,
+ * equal values by index).  The blank candidate joins B with the OLD state; a non-blank candidate within expand_beam of the
+ * best non-blank one joins A with the new state.  After the last frame B is sorted by key (descending, stable).
+ *   max_expansions: the reference's loop has no bound (it never leaves a frame whose blank stays out of the top beam_size);
+ *     here a frame stops expanding after max_expansions expansions, carries the beam_size best of A forward as they are if
+ *     B is still empty, and sets SBK_TBEAM_CAPPED in the utterance's status.  Past that point the result is unspecified
+ *     (but in bounds); with status 0 it is the reference's.
+ *   workspace: sbk_transducer_beam_workspace_bytes(W, cfg, B, T) bytes, 16-byte aligned: the token tree (parent, token),
+ *     the pool of PN states and cached PN outputs (global memory: a state is 4 KB per layer at the recipes' size) and, first,
+ *     [B] int32: the number of expansions utterance b made (a diagnostic).  The library allocates nothing.
+ *   out_tokens [B, nbest, max_tokens] int32, out_len [B, nbest], out_score [B, nbest] (score / len, the key), best first;
+ *     out_count [B] = min(nbest, len(B)) entries of utterance b are written.  The leading blank is not part of out_tokens or
+ *     out_len (but counts in the key, as in the reference).  A hypothesis longer than max_tokens keeps its first max_tokens
+ *     tokens and sets SBK_TBEAM_TRUNCATED.  out_status [B]: 0 or a sum of SBK_TBEAM_* bits.
+ * beam_size 2..SBK_TRANSDUCER_MAX_BEAM and <= V; nbest >= 1; max_expansions >= 1; the hypothesis lists live in LDS, so
+ * beam_size * max_expansions is limited by it (refused with a message otherwise). */
+#define SBK_TRANSDUCER_MAX_BEAM 32
+enum {
+  SBK_TBEAM_CAPPED = 1,    /* a frame reached max_expansions */
+  SBK_TBEAM_TRUNCATED = 2, /* a returned hypothesis was longer than max_tokens */
+  SBK_TBEAM_EXHAUSTED = 4  /* A ran empty (non-finite log-probabilities): the last expanded hypothesis was carried forward */
+};
+typedef struct sbk_transducer_beam_config {
+  int32_t blank, beam_size, nbest;
+  float state_beam, expand_beam;
+  int32_t max_expansions, max_tokens, act;
+} sbk_transducer_beam_config;
+size_t sbk_transducer_beam_workspace_bytes(const sbk_transducer_weights* W, const sbk_transducer_beam_config* cfg, int B,
+                                           int T);
+int sbk_transducer_beam_search_f32(const sbk_transducer_weights* W, const sbk_transducer_beam_config* cfg, const float* tn,
+                                   void* workspace, size_t workspace_bytes, int32_t* out_tokens, int32_t* out_len,
+                                   float* out_score, int32_t* out_count, int32_t* out_status, int B, int T,
+                                   sbk_stream_t stream);
+
 /* log_softmax(x / temperature) * weight over the last dimension, x [rows,V] (seq2seq.py:1933). */
 int sbk_log_softmax_f32(const float* x, float* out, int rows, int V, float temperature, float weight,
                         sbk_stream_t stream);

@@ -1,8 +1,10 @@
 // Transducer greedy decoding on the device: TransducerBeamSearcher.transducer_greedy_decode (decoders/transducer.py:156-291)
 // for the prediction network [Embedding, LSTM, Linear], Transducer_joint(joint="sum") and one classifier Linear.  One
 // workgroup per utterance runs every frame in ONE launch with the utterance's PN state in LDS; the weights stream from L2.
-// The semantics reproduced here are listed in DESIGN.md section 5 ("Transducer greedy decoding").
+// The semantics reproduced here are listed in DESIGN.md section 5 ("Transducer greedy decoding").  Further down: the beam
+// search of the same class (transducer_beam_search_decode, decoders/transducer.py:320-476) on the same step code.
 #include <math.h>
+#include <string.h>
 
 #include "argmax.h"
 #include "common.h"
@@ -146,6 +148,19 @@ __device__ void pn_step(const TdArgs& a, int tok, float* s_pn, float* s_h, float
   __syncthreads();
 }
 
+// The statistics of one wave's log-softmax over x[0..V): the log-probability of entry v is (x[v] - m) - ls.  Every lane of the
+// wave calls it; the greedy and the beam search share it, so both see the same bits.
+__device__ __forceinline__ void log_softmax_stats(const float* x, int V, float& m, float& ls) {
+  const int lane = threadIdx.x & 63;
+  m = -INFINITY;
+  for (int v = lane; v < V; v += 64) m = fmaxf(m, x[v]);
+  for (int s = 32; s >= 1; s >>= 1) m = fmaxf(m, shfl_xor(m, s));
+  float se = 0.0f;
+  for (int v = lane; v < V; v += 64) se += expf(x[v] - m);
+  for (int s = 32; s >= 1; s >>= 1) se += shfl_xor(se, s);
+  ls = logf(se);
+}
+
 __global__ __launch_bounds__(kTdThreads) void transducer_greedy_kernel(TdArgs a) {
   SBK_DYN_LDS(float, lds);
   const sbk_transducer_weights& W = a.W;
@@ -195,13 +210,8 @@ __global__ __launch_bounds__(kTdThreads) void transducer_greedy_kernel(TdArgs a)
     // 3. log-softmax and arg-max of each frame (one wave per frame)
     for (int f = wave; f < fe; f += kTdThreads / 64) {
       const float* x = s_logit + (size_t)f * V;
-      float m = -INFINITY;
-      for (int v = lane; v < V; v += 64) m = fmaxf(m, x[v]);
-      for (int s = 32; s >= 1; s >>= 1) m = fmaxf(m, shfl_xor(m, s));
-      float se = 0.0f;
-      for (int v = lane; v < V; v += 64) se += expf(x[v] - m);
-      for (int s = 32; s >= 1; s >>= 1) se += shfl_xor(se, s);
-      const float ls = logf(se);
+      float m, ls;
+      log_softmax_stats(x, V, m, ls);
       float bv = NAN;
       int bi = 0x7fffffff;
       for (int v = lane; v < V; v += 64) {
@@ -276,6 +286,265 @@ __global__ __launch_bounds__(kTdThreads) void lstm_layer_kernel(const float* __r
   for (int m = tid; m < H; m += kTdThreads) h[(size_t)b * H + m] = s_h[m], c[(size_t)b * H + m] = s_c[m];
 }
 
+// ------------------------------------------------------------------------------------------------------------ beam search
+// TransducerBeamSearcher.transducer_beam_search_decode (decoders/transducer.py:320-476) without an LM; the rules are listed in
+// DESIGN.md section 5 ("Transducer beam search").  One workgroup per utterance.  The lists A and B of a frame live in LDS; the
+// token tree and the PN states (with the PN outputs they produced) live in the caller's workspace.
+struct TbHyp {
+  int node;     // the hypothesis' node of the utterance's token tree (parent, token)
+  int tok;      // its last token: the PN's next input
+  float score;  // logp_score
+  int len;      // len(prediction), the leading blank included
+  int state;    // the slot whose h / c are hidden_dec (-1: zeros)
+  int pn;       // the slot that holds this (tok, state)'s PN step already (-1: not computed yet)
+  int stamp;    // list order: the order of the appends
+};
+
+struct TbArgs {
+  TdArgs g;      // W and tn (what pn_step reads)
+  int2* nodes;   // [B][node_cap] (parent, token)
+  float* slots;  // [B][n_slots][slot_floats]: out_PN [J], h [L*H], c [L*H] after one PN step
+  int32_t* expansions;  // [B]
+  int32_t* out_tokens;  // [B][nbest][max_tokens]
+  int32_t* out_len;     // [B][nbest]
+  float* out_score;     // [B][nbest]
+  int32_t* out_count;   // [B]
+  int32_t* out_status;  // [B]
+  int beam, nbest, max_exp, max_tokens, cap_a, n_slots, slot_floats, node_cap;
+  float state_beam, expand_beam;
+};
+
+// The sort key logp_score / len(prediction): an fp32 division.  (A NaN key ranks below everything, so that a search over
+// non-finite inputs still picks one hypothesis.)
+__device__ __forceinline__ float tb_key(const TbHyp& h) {
+  const float k = h.score / (float)h.len;
+  return isnan(k) ? -INFINITY : k;
+}
+
+// The index of the first maximal key of list[0..n), n > 0, in list order (the smallest stamp).  Every lane of one wave calls it.
+__device__ __forceinline__ int tb_best(const TbHyp* list, int n) {
+  const int lane = threadIdx.x & 63;
+  float bk = -INFINITY;
+  int bs = 0x7fffffff, bi = -1;
+  for (int i = lane; i < n; i += 64) {
+    const float k = tb_key(list[i]);
+    const int s = list[i].stamp;
+    if (bi < 0 || k > bk || (k == bk && s < bs)) bk = k, bs = s, bi = i;
+  }
+  for (int m = 32; m >= 1; m >>= 1) {
+    const float k = shfl_xor(bk, m);
+    const int s = shfl_xor(bs, m), i = shfl_xor(bi, m);
+    if (i >= 0 && (bi < 0 || k > bk || (k == bk && s < bs))) bk = k, bs = s, bi = i;
+  }
+  return bi;
+}
+
+__global__ __launch_bounds__(kTdThreads) void transducer_beam_kernel(TbArgs a) {
+  SBK_DYN_LDS(float, lds);
+  const sbk_transducer_weights& W = a.g.W;
+  const int H = W.hidden, G = 4 * H, J = W.joint, V = W.vocab, L = W.n_layers, LH = L * H;
+  float* s_z = lds;             // [J] joint activations
+  float* s_logit = s_z + J;     // [V]
+  float* s_pn = s_logit + V;    // [J]
+  float* s_h = s_pn + J;        // [L][H]
+  float* s_c = s_h + LH;        // [L][H]
+  float* s_g = s_c + LH;        // [G]
+  float* s_gh = s_g + G;        // [G]
+  float* s_topv = s_gh + G;     // [beam] the top-k log-probabilities of an expansion ...
+  int* s_topi = reinterpret_cast<int*>(s_topv + a.beam);  // [beam] ... and their tokens
+  int* s_used = s_topi + a.beam;                          // [n_slots] slot is referenced by a hypothesis of this frame
+  TbHyp* A = reinterpret_cast<TbHyp*>(s_used + a.n_slots);  // [cap_a]
+  TbHyp* Bl = A + a.cap_a;                                  // [beam]
+  __shared__ int s_na, s_nb, s_act, s_slot, s_status, s_nodes, s_stamp, s_total;
+  __shared__ TbHyp s_cur;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int blank = a.g.blank;
+  const float* tnb = a.g.tn + (size_t)b * a.g.T * J;
+  int2* nodes = a.nodes + (size_t)b * a.node_cap;
+  float* slots = a.slots + (size_t)b * a.n_slots * a.slot_floats;
+
+  if (tid == 0) {
+    nodes[0] = make_int2(-1, blank);
+    A[0] = TbHyp{0, blank, 0.0f, 1, -1, -1, 0};
+    s_na = 1, s_nb = 0, s_status = 0, s_nodes = 1, s_stamp = 1, s_total = 0;
+  }
+  __syncthreads();
+
+  for (int t = 0; t < a.g.T; ++t) {
+    if (t > 0) {  // A = the previous B, B = {}
+      const int n = s_nb;
+      for (int i = tid; i < n; i += kTdThreads) A[i] = Bl[i];
+      __syncthreads();
+      if (tid == 0) s_na = n, s_nb = 0;
+    }
+    for (int i = tid; i < a.n_slots; i += kTdThreads) s_used[i] = 0;
+    __syncthreads();
+    for (int i = tid; i < s_na; i += kTdThreads) {
+      if (A[i].state >= 0) s_used[A[i].state] = 1;
+      if (A[i].pn >= 0) s_used[A[i].pn] = 1;
+    }
+    __syncthreads();
+
+    int n_exp = 0;
+    while (true) {
+      // ---- the three exits and the selection (wave 0; lane 0 decides)
+      if (wave == 0) {
+        const int na = s_na, nb = s_nb;
+        const int ai = na > 0 ? tb_best(A, na) : -1;
+        const int bi = nb > 0 ? tb_best(Bl, nb) : -1;
+        int fr = 0x7fffffff;  // the first free slot
+        for (int i = lane; i < a.n_slots; i += 64)
+          if (!s_used[i]) {
+            fr = i;
+            break;
+          }
+        for (int m = 32; m >= 1; m >>= 1) fr = min(fr, shfl_xor(fr, m));
+        if (lane == 0) {
+          int act = 0;
+          if (nb < a.beam && ai >= 0 && !(bi >= 0 && Bl[bi].score >= a.state_beam + A[ai].score)) {
+            if (n_exp >= a.max_exp || (A[ai].pn < 0 && fr == 0x7fffffff))
+              s_status |= SBK_TBEAM_CAPPED;  // (n_slots covers max_exp new states per frame: the second test never holds)
+            else
+              act = 1;
+          }
+          if (act) {
+            s_cur = A[ai];
+            s_slot = A[ai].pn >= 0 ? A[ai].pn : fr;
+            s_used[s_slot] = 1;
+            A[ai] = A[na - 1];  // (list order is the stamps')
+            s_na = na - 1;
+          }
+          s_act = act;
+        }
+      }
+      __syncthreads();
+      if (!s_act) break;
+
+      // ---- one PN step on a_best's last token from its state, or the copy an earlier expansion of the same pair left
+      const TbHyp cur = s_cur;
+      const int slot = s_slot;
+      float* sl = slots + (size_t)slot * a.slot_floats;
+      if (cur.pn >= 0) {
+        for (int j = tid; j < J; j += kTdThreads) s_pn[j] = sl[j];
+        __syncthreads();
+      } else {
+        if (cur.state >= 0) {
+          const float* src = slots + (size_t)cur.state * a.slot_floats + J;
+          for (int i = tid; i < LH; i += kTdThreads) s_h[i] = src[i], s_c[i] = src[LH + i];
+        } else {
+          for (int i = tid; i < LH; i += kTdThreads) s_h[i] = 0.0f, s_c[i] = 0.0f;
+        }
+        __syncthreads();
+        pn_step(a.g, cur.tok, s_pn, s_h, s_c, s_g, s_gh);
+        for (int j = tid; j < J; j += kTdThreads) sl[j] = s_pn[j];
+        for (int i = tid; i < LH; i += kTdThreads) sl[J + i] = s_h[i], sl[J + LH + i] = s_c[i];
+      }
+      // ---- the joint with tn[b, t], the classifier, log-softmax and top-k
+      const float* tnf = tnb + (size_t)t * J;
+      for (int k = tid; k < J; k += kTdThreads) s_z[k] = joint_act(tnf[k] + s_pn[k], a.g.act);
+      __syncthreads();
+      gemv_rows<1, 8>(W.out, W.out_b, s_z, J, 1, J, V, s_logit, V);
+      __syncthreads();
+      if (wave == 0) {
+        float m, ls;
+        log_softmax_stats(s_logit, V, m, ls);
+        float pv = 0.0f;
+        int pi = -1;  // the previous pick: round r takes the best of what ranks below it (torch.topk's order)
+        for (int r = 0; r < a.beam; ++r) {
+          float bv = NAN;
+          int bi = 0x7fffffff;
+          for (int v = lane; v < V; v += 64) {
+            const float lp = (s_logit[v] - m) - ls;
+            if (pi >= 0 && !arg_better(pv, pi, lp, v)) continue;
+            if (bi == 0x7fffffff || arg_better(lp, v, bv, bi)) bv = lp, bi = v;
+          }
+          for (int s = 32; s >= 1; s >>= 1) {
+            const float w = shfl_xor(bv, s);
+            const int j = shfl_xor(bi, s);
+            if (j != 0x7fffffff && (bi == 0x7fffffff || arg_better(w, j, bv, bi))) bv = w, bi = j;
+          }
+          pv = bv, pi = bi;
+          if (lane == 0) s_topv[r] = bv, s_topi[r] = bi;
+        }
+        // ---- the candidates in top-k order: blank joins B with the old state, the others join A with the new one
+        if (lane == 0) {
+          const float best = s_topi[0] != blank ? s_topv[0] : s_topv[1];
+          const float thr = best - a.expand_beam;
+          int na = s_na, nb = s_nb, nn = s_nodes, st = s_stamp;
+          for (int j = 0; j < a.beam; ++j) {
+            const float lp = s_topv[j];
+            const int tok = s_topi[j];
+            if (tok == blank) {
+              if (nb < a.beam) Bl[nb++] = TbHyp{cur.node, cur.tok, cur.score + lp, cur.len, cur.state, slot, st++};
+            } else if (lp >= thr && na < a.cap_a && nn < a.node_cap) {
+              nodes[nn] = make_int2(cur.node, tok);
+              A[na++] = TbHyp{nn++, tok, cur.score + lp, cur.len + 1, slot, -1, st++};
+            }
+          }
+          s_na = na, s_nb = nb, s_nodes = nn, s_stamp = st, s_total = s_total + 1;
+        }
+      }
+      ++n_exp;
+      __syncthreads();
+    }
+
+    // ---- a frame that stopped with an empty B (the cap, or non-finite scores): the beam best of A go on as they are
+    if (wave == 0 && s_nb == 0) {
+      int na = s_na, nb = 0;
+      if (na == 0) {
+        if (lane == 0) Bl[0] = s_cur, s_status |= SBK_TBEAM_EXHAUSTED;
+        nb = 1;
+      }
+      for (; nb < a.beam && na > 0; ++nb, --na) {
+        const int i = tb_best(A, na);
+        if (lane == 0) Bl[nb] = A[i], A[i] = A[na - 1];
+        wave_sync();
+      }
+      wave_sync();
+      if (lane == 0) s_na = na, s_nb = nb;
+    }
+    __syncthreads();
+  }
+
+  // ---- B sorted by key (descending, stable: list order among equal keys), the first nbest of it
+  int count = 0;
+  if (wave == 0) {
+    int nb = s_nb;
+    for (; count < a.nbest && nb > 0; ++count, --nb) {
+      const int i = tb_best(Bl, nb);
+      if (lane == 0) A[count] = Bl[i], Bl[i] = Bl[nb - 1];
+      wave_sync();
+    }
+    if (lane == 0) s_act = count;
+  }
+  __syncthreads();
+  count = s_act;
+  for (int r = tid; r < a.nbest; r += kTdThreads) {
+    const size_t row = (size_t)b * a.nbest + r;
+    if (r >= count) {
+      a.out_len[row] = 0, a.out_score[row] = 0.0f;
+      continue;
+    }
+    const TbHyp h = A[r];
+    const int n = h.len - 1;  // without the leading blank
+    a.out_len[row] = min(n, a.max_tokens);
+    a.out_score[row] = h.score / (float)h.len;
+    int32_t* dst = a.out_tokens + row * a.max_tokens;
+    int node = h.node;
+    for (int p = n - 1; p >= 0 && node > 0; --p) {
+      const int2 e = nodes[node];
+      if (p < a.max_tokens) dst[p] = e.y;
+      node = e.x;
+    }
+  }
+  if (tid == 0) {
+    int status = s_status;
+    for (int r = 0; r < count; ++r)
+      if (A[r].len - 1 > a.max_tokens) status |= SBK_TBEAM_TRUNCATED;
+    a.out_count[b] = count, a.out_status[b] = status, a.expansions[b] = s_total;
+  }
+}
+
 size_t td_lds_bytes(const sbk_transducer_weights& W, int F) {
   return sizeof(float) * ((size_t)F * W.joint + (size_t)F * W.vocab + W.joint + 2 * (size_t)W.n_layers * W.hidden +
                           8 * (size_t)W.hidden);
@@ -329,6 +598,114 @@ extern "C" int sbk_transducer_greedy_f32(const sbk_transducer_weights* W, const 
                                                4.0 * G * W->hidden * W->n_layers * B, st);
   SBK_LAUNCH(transducer_greedy_kernel, dim3(B), dim3(kTdThreads), lds, st, a);
   return launch_status("transducer_greedy");
+}
+
+namespace {
+
+constexpr size_t kTbStaticLds = 256;  // the beam kernel's counters and s_cur
+
+struct TbSizes {
+  long long cap_a, n_slots, slot_floats, node_cap;
+  size_t lds, head_bytes, node_bytes, slot_bytes, total;
+};
+
+// The sizes of one beam search; `why` names the limit a refused size breaks.
+bool tb_sizes(const sbk_transducer_weights& W, const sbk_transducer_beam_config& c, int B, int T, TbSizes& z, const char** why) {
+  const long long beam = c.beam_size, me = c.max_expansions;
+  z.cap_a = beam + me * beam;   // the previous B plus at most beam children per expansion
+  z.n_slots = 2 * beam + me;    // the states and cached steps B carries in, plus one new state per expansion
+  z.slot_floats = ((long long)W.joint + 2LL * W.n_layers * W.hidden + 3) / 4 * 4;
+  z.node_cap = 1 + (long long)T * me * beam;
+  *why = "max_expansions * beam_size * T too large";
+  if (z.node_cap >= (1LL << 31) || z.cap_a >= (1LL << 24)) return false;
+  z.lds = sizeof(float) * (2 * (size_t)W.joint + W.vocab + 2 * (size_t)W.n_layers * W.hidden + 8 * (size_t)W.hidden) +
+          sizeof(int) * (2 * (size_t)beam + (size_t)z.n_slots) + sizeof(TbHyp) * (size_t)(z.cap_a + beam);
+  *why = "the hypothesis lists (beam_size * max_expansions) and the network's vectors do not fit in LDS";
+  if (z.lds > kTdLdsMax - kTbStaticLds) return false;
+  z.head_bytes = ((size_t)B * sizeof(int32_t) + 15) / 16 * 16;
+  z.node_bytes = (size_t)B * (size_t)z.node_cap * sizeof(int2);
+  z.slot_bytes = (size_t)B * (size_t)z.n_slots * (size_t)z.slot_floats * sizeof(float);
+  z.total = z.head_bytes + z.node_bytes + z.slot_bytes;
+  return true;
+}
+
+int tb_check(const sbk_transducer_weights* W, const sbk_transducer_beam_config* cfg, int B, int T) {
+  SBK_REQUIRE(W && cfg, "transducer_beam_search: weights or cfg is NULL");
+  SBK_REQUIRE(B > 0 && T > 0, "transducer_beam_search: bad arguments (B=%d T=%d)", B, T);
+  SBK_REQUIRE(W->n_layers >= 1 && W->n_layers <= SBK_TRANSDUCER_MAX_LAYERS,
+              "transducer_beam_search: %d LSTM layers (1..%d supported)", W->n_layers, SBK_TRANSDUCER_MAX_LAYERS);
+  SBK_REQUIRE(W->hidden > 0 && W->joint > 0 && W->vocab > 0 && W->n_emb >= W->vocab,
+              "transducer_beam_search: bad sizes (hidden=%d joint=%d vocab=%d n_emb=%d; vocab <= n_emb)", W->hidden, W->joint,
+              W->vocab, W->n_emb);
+  SBK_REQUIRE(W->emb_ih && W->proj && W->out, "transducer_beam_search: emb_ih, proj and out are required");
+  for (int l = 0; l < W->n_layers; ++l)
+    SBK_REQUIRE(W->w_hh[l] && (l == 0 || W->w_ih[l]), "transducer_beam_search: weights of LSTM layer %d missing", l);
+  SBK_REQUIRE(cfg->blank >= 0 && cfg->blank < W->vocab, "transducer_beam_search: blank %d outside [0, %d)", cfg->blank,
+              W->vocab);
+  SBK_REQUIRE(cfg->beam_size >= 2, "transducer_beam_search: beam_size %d < 2 (the greedy entry decodes beam_size 1)",
+              cfg->beam_size);
+  SBK_REQUIRE(cfg->beam_size <= SBK_TRANSDUCER_MAX_BEAM, "transducer_beam_search: beam_size %d above the maximum %d",
+              cfg->beam_size, SBK_TRANSDUCER_MAX_BEAM);
+  SBK_REQUIRE(cfg->beam_size <= W->vocab, "transducer_beam_search: beam_size %d above the vocabulary %d", cfg->beam_size,
+              W->vocab);
+  SBK_REQUIRE(cfg->nbest >= 1, "transducer_beam_search: nbest %d < 1", cfg->nbest);
+  SBK_REQUIRE(cfg->max_expansions >= 1, "transducer_beam_search: max_expansions %d < 1", cfg->max_expansions);
+  SBK_REQUIRE(cfg->max_tokens >= 1, "transducer_beam_search: max_tokens %d < 1", cfg->max_tokens);
+  SBK_REQUIRE((long long)B * cfg->nbest * cfg->max_tokens < (1LL << 40), "transducer_beam_search: output too large");
+  SBK_REQUIRE(cfg->act == SBK_ACT_GELU || cfg->act == SBK_ACT_LEAKY_RELU || cfg->act == SBK_ACT_RELU ||
+                  cfg->act == SBK_ACT_TANH,
+              "transducer_beam_search: joint activation %d is not supported", cfg->act);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" size_t sbk_transducer_beam_workspace_bytes(const sbk_transducer_weights* W, const sbk_transducer_beam_config* cfg,
+                                                      int B, int T) {
+  TbSizes z;
+  const char* why;
+  if (B == 0) return 0;
+  if (tb_check(W, cfg, B, T) != 0) return 0;
+  if (!tb_sizes(*W, *cfg, B, T, z, &why)) {
+    fail(SBK_EINVAL, "transducer_beam_search: %s (beam_size=%d max_expansions=%d T=%d)", why, cfg->beam_size,
+         cfg->max_expansions, T);
+    return 0;
+  }
+  return z.total;
+}
+
+extern "C" int sbk_transducer_beam_search_f32(const sbk_transducer_weights* W, const sbk_transducer_beam_config* cfg,
+                                              const float* tn, void* workspace, size_t workspace_bytes, int32_t* out_tokens,
+                                              int32_t* out_len, float* out_score, int32_t* out_count, int32_t* out_status,
+                                              int B, int T, sbk_stream_t stream) {
+  if (B == 0) return 0;
+  if (const int rc = tb_check(W, cfg, B, T)) return rc;
+  SBK_REQUIRE(tn && workspace && out_tokens && out_len && out_score && out_count && out_status,
+              "transducer_beam_search: a NULL pointer among tn, workspace and the outputs");
+  TbSizes z;
+  const char* why;
+  SBK_REQUIRE(tb_sizes(*W, *cfg, B, T, z, &why), "transducer_beam_search: %s (beam_size=%d max_expansions=%d T=%d)", why,
+              cfg->beam_size, cfg->max_expansions, T);
+  SBK_REQUIRE(aligned16(workspace), "transducer_beam_search: the workspace is not 16-byte aligned");
+  SBK_REQUIRE(workspace_bytes >= z.total, "transducer_beam_search: workspace of %zu bytes, %zu needed", workspace_bytes, z.total);
+  TbArgs a;
+  memset(&a, 0, sizeof(a));
+  a.g.W = *W;
+  a.g.tn = tn, a.g.B = B, a.g.T = T, a.g.blank = cfg->blank, a.g.act = cfg->act;
+  char* ws = static_cast<char*>(workspace);
+  a.expansions = reinterpret_cast<int32_t*>(ws);
+  a.nodes = reinterpret_cast<int2*>(ws + z.head_bytes);
+  a.slots = reinterpret_cast<float*>(ws + z.head_bytes + z.node_bytes);
+  a.out_tokens = out_tokens, a.out_len = out_len, a.out_score = out_score, a.out_count = out_count, a.out_status = out_status;
+  a.beam = cfg->beam_size, a.nbest = cfg->nbest, a.max_exp = cfg->max_expansions, a.max_tokens = cfg->max_tokens;
+  a.cap_a = (int)z.cap_a, a.n_slots = (int)z.n_slots, a.slot_floats = (int)z.slot_floats, a.node_cap = (int)z.node_cap;
+  a.state_beam = cfg->state_beam, a.expand_beam = cfg->expand_beam;
+  hipStream_t st = as_stream(stream);
+  if (z.lds > 64 * 1024 && (int)SBK_ALLOW_DYN_LDS(transducer_beam_kernel, z.lds) != 0)
+    return fail(SBK_EINVAL, "transducer_beam_search: %zu bytes of LDS not available", z.lds);
+  ProfScope prof("transducer_beam", 0.0, 4.0 * B * T * W->joint + 4.0 * (double)W->joint * W->vocab * B * T, st);
+  SBK_LAUNCH(transducer_beam_kernel, dim3(B), dim3(kTdThreads), z.lds, st, a);
+  return launch_status("transducer_beam_search");
 }
 
 extern "C" int sbk_lstm_f32(const float* xp, const float* w_hh, const float* b_ih, const float* b_hh, float* h, float* c,

@@ -1,11 +1,17 @@
-"""speechbrain.decoders.transducer mirror: TransducerBeamSearcher's greedy search (decoders/transducer.py:25-345) on the
-device.
+"""speechbrain.decoders.transducer mirror: TransducerBeamSearcher's greedy search and beam search (decoders/transducer.py:
+25-476) on the device.
 
-The whole search of a batch -- prediction network (PN) steps, joint, classifier, log-softmax and arg-max for every frame --
-is ONE launch of sbk_transducer_greedy_f32 (csrc/transducer.hip), one workgroup per utterance.  Supported: the PN
-[Embedding (dense or one-hot), LSTM (unidirectional, 1..4 layers), Linear], Transducer_joint(joint="sum") with GELU,
-LeakyReLU, Tanh or ReLU, and one classifier Linear.  Transducer beam search (beam_size > 1), LM fusion and other PN layers
-raise NotImplementedError when the searcher is called."""
+The whole search of a batch -- prediction network (PN) steps, joint, classifier, log-softmax and arg-max or top-k for every
+frame -- is ONE launch of sbk_transducer_greedy_f32 (``beam_size <= 1``) or sbk_transducer_beam_search_f32 (``beam_size >
+1``; csrc/transducer.hip), one workgroup per utterance.  Supported: the PN [Embedding (dense or one-hot), LSTM
+(unidirectional, 1..4 layers), Linear], Transducer_joint(joint="sum") with GELU, LeakyReLU, Tanh or ReLU, and one classifier
+Linear.  LM fusion and other PN layers raise NotImplementedError when the searcher is called; so does a beam above
+native.TRANSDUCER_MAX_BEAM.
+
+The reference's beam search has no bound on the expansions of a frame (it never leaves a frame whose blank stays out of the
+top ``beam_size``); here ``max_expansions`` (default ``4 * beam_size``) bounds them.  A search that reaches the bound ends,
+warns and names the utterances; its tokens for those are unspecified."""
+import warnings
 from dataclasses import dataclass
 from typing import Any, Optional
 
@@ -22,8 +28,8 @@ class TransducerGreedySearcherStreamingContext(torch.nn.Module):
 
 
 class TransducerBeamSearcher(torch.nn.Module):
-    """decoders/transducer.py:25-145.  Constructs for any beam size (reference YAMLs define a beam searcher with an LM
-    beside the greedy one); only a call with ``beam_size > 1`` raises."""
+    """decoders/transducer.py:25-145.  Constructs with any arguments (reference YAMLs define a beam searcher with an LM
+    beside the greedy one); what is not built raises when the searcher is called."""
 
     def __init__(self, decode_network_lst, tjoint, classifier_network, blank_id, beam_size=4, nbest=5, lm_module=None,
                  lm_weight=0.0, state_beam=2.3, expand_beam=2.3):
@@ -50,8 +56,46 @@ class TransducerBeamSearcher(torch.nn.Module):
     def forward(self, tn_output):
         return self.searcher(tn_output)
 
-    def transducer_beam_search_decode(self, tn_output):
-        raise NotImplementedError(f"transducer beam search (beam_size={self.beam_size}) is not implemented; use beam_size=1")
+    def transducer_beam_search_decode(self, tn_output, max_expansions=None, return_status=False):
+        """decoders/transducer.py:320-476.  Returns (best hypothesis per utterance, exp(best scores).mean(), nbest_batch,
+        nbest_batch_score): token lists without the leading blank, and logp_score / len(prediction) (the leading blank counts)
+        as Python floats.  ``max_expansions``: the bound on the expansions of one frame (default 4 * beam_size; the reference
+        has none).  Utterances that reach it, or whose log-probabilities are not finite, are named in a warning and their
+        result is unspecified.  ``return_status`` appends (status word, number of expansions) per utterance, as lists.  (No
+        hypothesis is truncated: the kernel is given room for T * max_expansions tokens, which none can exceed.)"""
+        if self.lm is not None and self.lm_weight > 0:
+            raise NotImplementedError("transducer beam search with LM fusion is not implemented")
+        if self.beam_size > native.TRANSDUCER_MAX_BEAM:
+            raise NotImplementedError(f"transducer beam search with beam_size={self.beam_size} is not implemented "
+                                      f"(at most {native.TRANSDUCER_MAX_BEAM})")
+        tn = tn_output.detach().float().contiguous()
+        prep = self._prepare(tn.device)
+        if self.beam_size > prep.W.vocab:
+            raise ValueError(f"beam_size={self.beam_size} is larger than the {prep.W.vocab} outputs of the classifier")
+        if tn.shape[0] == 0:  # (the reference's mean over no utterances)
+            ret = ([], torch.tensor(float("nan")), [], [])
+            return ret + (([], []),) if return_status else ret
+        if max_expansions is None:
+            max_expansions = native.transducer_beam_max_expansions(self.beam_size)
+        tokens, length, score, count, status, expansions = native.transducer_beam_search(
+            prep, tn, self.blank_id, self.beam_size, self.nbest, state_beam=self.state_beam, expand_beam=self.expand_beam,
+            max_expansions=max_expansions, act=self.tjoint.act_code)
+        length, counts, status = length.cpu(), count.cpu().tolist(), status.cpu().tolist()
+        rows = tokens[:, :, :max(1, int(length.max()))].cpu().tolist()
+        length, scores = length.tolist(), score.cpu().tolist()
+        capped = [b for b, st in enumerate(status) if st & native.TBEAM_CAPPED]
+        if capped:
+            warnings.warn(f"transducer beam search: utterances {capped} reached the bound on the expansions of one frame "
+                          f"(max_expansions={max_expansions}); their hypotheses are unspecified")
+        exhausted = [b for b, st in enumerate(status) if st & native.TBEAM_EXHAUSTED]
+        if exhausted:
+            warnings.warn(f"transducer beam search: utterances {exhausted} ran out of hypotheses to expand (log-probabilities "
+                          "that are not finite); their hypotheses are unspecified")
+        nbest_batch = [[rows[b][k][:length[b][k]] for k in range(counts[b])] for b in range(len(counts))]
+        nbest_batch_score = [scores[b][:counts[b]] for b in range(len(counts))]
+        best = torch.tensor([s[0] for s in nbest_batch_score], dtype=torch.float32)
+        ret = ([n[0] for n in nbest_batch], best.exp().mean(), nbest_batch, nbest_batch_score)
+        return ret + ((status, expansions.cpu().tolist()),) if return_status else ret
 
     # ------------------------------------------------------------------ the network, in the kernel's layout
     def _networks(self):

@@ -90,6 +90,15 @@ class TransducerConfig(ctypes.Structure):  # sbk_transducer_config
     _fields_ = [(n, c_int32) for n in ("blank", "max_symbols_per_step", "start_from_blank", "frame_block", "act")]
 
 
+TRANSDUCER_MAX_BEAM = 32  # SBK_TRANSDUCER_MAX_BEAM
+TBEAM_CAPPED, TBEAM_TRUNCATED, TBEAM_EXHAUSTED = 1, 2, 4  # SBK_TBEAM_*: the bits of the beam search's status word
+
+
+class TransducerBeamConfig(ctypes.Structure):  # sbk_transducer_beam_config
+    _fields_ = [("blank", c_int32), ("beam_size", c_int32), ("nbest", c_int32), ("state_beam", c_float),
+                ("expand_beam", c_float), ("max_expansions", c_int32), ("max_tokens", c_int32), ("act", c_int32)]
+
+
 def _declare(lib):
     p, i, f = c_void_p, c_int, c_float
     sig = {
@@ -162,6 +171,10 @@ def _declare(lib):
         "sbk_transducer_greedy_f32": ([POINTER(TransducerWeights), POINTER(TransducerConfig), p, p, p, p, p, p, p, i, i, p],
                                       c_int),
         "sbk_lstm_f32": ([p, p, p, p, p, p, p, i, i, i, p], c_int),
+        "sbk_transducer_beam_workspace_bytes": ([POINTER(TransducerWeights), POINTER(TransducerBeamConfig), i, i],
+                                                ctypes.c_size_t),
+        "sbk_transducer_beam_search_f32": ([POINTER(TransducerWeights), POINTER(TransducerBeamConfig), p, p, ctypes.c_size_t,
+                                            p, p, p, p, p, i, i, p], c_int),
         "sbk_beam_search_workspace_bytes": ([POINTER(DecoderWeights), POINTER(SearchConfig), i, i], ctypes.c_size_t),
         "sbk_beam_search_f32": ([POINTER(DecoderWeights), POINTER(SearchConfig), p, p, p, p, p, ctypes.c_size_t, p, p,
                                  p, p, p, p, p, POINTER(c_int32), i, i, p], c_int),
@@ -1690,6 +1703,50 @@ def transducer_greedy(prep: TransducerPrepared, tn, out_pn, h, c, blank, max_sym
     _chk(lib.sbk_transducer_greedy_f32(ctypes.byref(prep.W), ctypes.byref(cfg), _p(tn), _p(out_pn), _p(h), _p(c), _p(tokens),
                                        _p(count), _p(score), B, T, _stream(tn)), "sbk_transducer_greedy_f32")
     return tokens, count, score
+
+
+def transducer_beam_max_expansions(beam_size) -> int:
+    """The default bound on the expansions of one frame of the transducer beam search."""
+    return 4 * int(beam_size)
+
+
+def transducer_beam_search(prep: TransducerPrepared, tn, blank, beam_size, nbest, state_beam=2.3, expand_beam=2.3,
+                           max_expansions=None, max_tokens=None, act=ACT_GELU):
+    """sbk_transducer_beam_search_f32: tn [B,T,J] fp32 -> (tokens [B,nbest,max_tokens] int32, length [B,nbest] int32,
+    score [B,nbest] fp32 (logp_score / len(prediction)), count [B] int32, status [B] int32 (TBEAM_* bits), expansions [B]
+    int32).  max_expansions: the bound on a frame's expansions (default 4 * beam_size); max_tokens: the room per hypothesis
+    (default T * max_expansions, which no hypothesis can exceed).  The workspace is the search workspace of the current
+    stream (grow-only, one per device and stream)."""
+    lib = load()
+    _f32(tn)
+    B, T, J = tn.shape
+    tn = tn.contiguous()
+    _dev_ok(tn)
+    if max_expansions is None:
+        max_expansions = transducer_beam_max_expansions(beam_size)
+    if max_tokens is None:
+        max_tokens = T * int(max_expansions)
+    cfg = TransducerBeamConfig(blank=int(blank), beam_size=int(beam_size), nbest=int(nbest), state_beam=float(state_beam),
+                               expand_beam=float(expand_beam), max_expansions=int(max_expansions),
+                               max_tokens=int(max_tokens), act=int(act))
+    dev = tn.device
+    tokens = torch.empty(B, max(cfg.nbest, 1), max(cfg.max_tokens, 1), dtype=torch.int32, device=dev)
+    length = torch.empty(B, max(cfg.nbest, 1), dtype=torch.int32, device=dev)
+    score = torch.empty(B, max(cfg.nbest, 1), dtype=torch.float32, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    nbytes = lib.sbk_transducer_beam_workspace_bytes(ctypes.byref(prep.W), ctypes.byref(cfg), B, T)
+    ws, ws_key = _search_workspace(max(nbytes, 16) + 16, dev)
+    off = (-ws.data_ptr()) % 16
+    try:
+        # (a refused configuration gives 0 bytes above; the entry then reports the reason)
+        _chk(lib.sbk_transducer_beam_search_f32(ctypes.byref(prep.W), ctypes.byref(cfg), _p(tn), c_void_p(ws.data_ptr() + off),
+                                                nbytes, _p(tokens), _p(length), _p(score), _p(count), _p(status), B, T,
+                                                _stream(tn)), "sbk_transducer_beam_search_f32")
+        expansions = ws[off:off + 4 * B].view(torch.int32).clone()
+    finally:
+        _search_workspace_done(ws_key)
+    return tokens, length, score, count, status, expansions
 
 
 # ------------------------------------------------------------------ HIP-event profiler

@@ -2,9 +2,11 @@
 d_ffn 2 048, 12 layers, joint 640, LSTM 512, 1 000 tokens, one-hot embedding, GELU joint) with random weights and a
 sharpened classifier: EncoderDecoderASR.transcribe_batch of 32 x 10 s from 16-bit PCM (encoder + greedy decoding), the
 decode kernel's own time (HIP events), and streaming-style decoding at B = 1 (one 8-frame chunk per call, the state carried
-in a TransducerGreedySearcherStreamingContext).  One JSON line.
+in a TransducerGreedySearcherStreamingContext).  With --beam N (N > 1) the same batch is then decoded by beam search
+(beam_size N, nbest 5) in the same process: ms per batch, the beam kernel's own time, its ratio to the greedy kernel's, the
+mean expansions per frame and the number of utterances that reached max_expansions.  One JSON line.
 
-    python tools/transducer_bench.py [--steps 10] [--warmup 3]
+    python tools/transducer_bench.py [--steps 10] [--warmup 3] [--beam 10]
 """
 import argparse
 import json
@@ -67,6 +69,7 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--chunk-frames", type=int, default=8)
+    ap.add_argument("--beam", type=int, default=0, help="also measure beam search with this beam_size (> 1)")
     args = ap.parse_args()
     native.load()
     B, n = args.batch, int(args.seconds * 16000)
@@ -114,6 +117,37 @@ def main():
         dt = time.perf_counter() - t0
     res["stream_b1_chunk_frames"] = args.chunk_frames
     res["stream_b1_decode_ms_per_chunk"] = round(dt * 1e3 / len(chunks), 4)
+    if args.beam > 1:
+        import warnings
+
+        warnings.simplefilter("ignore")  # (capped utterances are counted below)
+        searcher.beam_size, searcher.nbest, searcher.searcher = args.beam, 5, searcher.transducer_beam_search_decode
+        times = []
+        for i in range(args.warmup + args.steps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            wav = pcm.cuda(non_blocking=True).float() / 32768.0
+            _, toks = asr.transcribe_batch(wav, lens)
+            torch.cuda.synchronize()
+            if i >= args.warmup:
+                times.append(time.perf_counter() - t0)
+        times.sort()
+        res["beam"] = args.beam
+        res["beam_p50_ms"] = round(times[len(times) // 2] * 1e3, 3)
+        res["beam_tokens_per_utterance_mean"] = round(sum(len(t) for t in toks) / B, 1)
+        native.prof_reset()
+        native.prof_enable(True)
+        for _ in range(args.steps):
+            out = native.transducer_beam_search(searcher._prepare(tn.device), tn, 0, args.beam, 5, searcher.state_beam,
+                                                searcher.expand_beam, act=searcher.tjoint.act_code)
+        torch.cuda.synchronize()
+        native.prof_enable(False)
+        rep = native.prof_report()
+        res["transducer_beam_kernel_ms"] = round(rep["transducer_beam"]["ms"] / rep["transducer_beam"]["count"], 4)
+        res["beam_kernel_over_greedy_kernel"] = round(res["transducer_beam_kernel_ms"] / res["transducer_greedy_kernel_ms"], 2)
+        res["beam_kernel_share_of_batch"] = round(res["transducer_beam_kernel_ms"] / res["beam_p50_ms"], 3)
+        res["beam_expansions_per_frame_mean"] = round(float(out[5].float().mean()) / tn.shape[1], 3)
+        res["beam_utterances_capped"] = int((out[4] != 0).sum())
     print(json.dumps(res))
 
 
