@@ -16,6 +16,18 @@
 #include "common.h"
 #include "internal.h"
 
+#define SBK_HIP(expr)                                                              \
+  do {                                                                             \
+    hipError_t e__ = (expr);                                                       \
+    if (e__ != hipSuccess) return sbk::fail((int)e__, "%s: %s", #expr, hipGetErrorString(e__)); \
+  } while (0)
+
+#define SBK_TRY(expr)        \
+  do {                       \
+    int rc__ = (expr);       \
+    if (rc__) return rc__;   \
+  } while (0)
+
 namespace {
 // Stop-rule polling without a pipeline bubble.  Every `check_every` steps the search enqueues a 4-byte device->host
 // copy of its "finished" counter plus an event and goes on enqueuing steps; it reads a copy back once its event has
@@ -981,41 +993,119 @@ void carve_decoder(Carver& c, DecoderBufs& d, const sbk_decoder_weights* W, int 
   }
 }
 
-#define SBK_HIP(expr)                                                              \
-  do {                                                                             \
-    hipError_t e__ = (expr);                                                       \
-    if (e__ != hipSuccess) return sbk::fail((int)e__, "%s: %s", #expr, hipGetErrorString(e__)); \
-  } while (0)
-
 // row pitch (floats) of the CTC posteriors the search keeps: whole 128-byte lines, so that a score workgroup's 1 KB segment of a
 // frame row is 8 lines (20 000-byte rows at V = 5 000 are not line-aligned: 9 lines, 1.25 x the bytes at the fabric counter)
 static inline int ctc_pitch(int V) { return (V + 31) & ~31; }
 
-#define SBK_TRY(expr)        \
-  do {                       \
-    int rc__ = (expr);       \
-    if (rc__) return rc__;   \
-  } while (0)
+// ---------------------------------------------------------------- projection routing
+// A projection y = act(x W^T + b) [+ R] and the images of its weights that exist (NULL = absent).
+struct Proj {
+  const float *w, *b;         // fp32 [N, K], [N]
+  const uint16_t *w3, *wp;    // images of w: sbk_split_bf16x3, panels (sbk_split_x3p)
+  const float *wf, *bf;       // w, b with the preceding LayerNorm's affine folded in
+  const uint16_t* wfp;        // panel image of wf
+  const float *ln_g, *ln_b;   // that LayerNorm
+};
+struct LayerProjs {
+  Proj sa_in, sa_out, ca_q, ca_kv, ca_out, ff1, ff2;  // ca_q / ca_kv: rows [0, d) / [d, 3d) of the cross-attention in_proj
+};
+LayerProjs layer_projs(const sbk_decoder_layer& L, int dm) {
+  return {{L.sa_in_w, L.sa_in_b, nullptr, L.sa_in_wp, L.sa_in_wf, L.sa_in_bf, L.sa_in_wfp, L.ln1_g, L.ln1_b},
+          {L.sa_out_w, L.sa_out_b, nullptr, L.sa_out_wp},
+          {L.ca_in_w, L.ca_in_b, nullptr, L.ca_q_wp, L.ca_q_wf, L.ca_q_bf, L.ca_q_wfp, L.ln2_g, L.ln2_b},
+          {L.ca_in_w + (size_t)dm * dm, L.ca_in_b + dm, L.ca_kv_w3},
+          {L.ca_out_w, L.ca_out_b, nullptr, L.ca_out_wp},
+          {L.ff1_w, L.ff1_b, nullptr, L.ff1_wp, L.ff1_wf, L.ff1_bf, L.ff1_wfp, L.ln3_g, L.ln3_b},
+          {L.ff2_w, L.ff2_b, nullptr, L.ff2_wp}};
+}
+Proj seq_proj(const sbk_decoder_weights* W) {
+  return {W->seq_w, W->seq_b, W->seq_w3, W->seq_wp, W->seq_wf, W->seq_bf, W->seq_wfp, W->final_ln_g, W->final_ln_b};
+}
+
+// THE ROUTE TABLE of the search's projections: nothing outside this block chooses among the contraction kernels.
+// Decode step, per LAYER (layer_route) -- never per projection: the panel kernels and the fp32-MFMA kernels are not bit-equal,
+// so a layer runs whole on one of them:
+//   kX3r, kX3rLn  all six panels exist, x3r_routed(n, d, d) and x3r_routed(n, d, d_ffn), and all nine bias pointers are 16-byte
+//                 aligned (the routed kernels move bias rows as 16-byte vectors: a layer with an unaligned bias view takes the
+//                 fp32 kernels instead of failing inside the route).  Every projection is gemm_nt_x3r (fp32 result
+//                 on the bf16 matrix pipe; its -1 is an error here).  norm1 / norm2 / norm3 run inside the projection they feed
+//                 (kX3rLn: gemm_ln_nt_x3r) when x3r_ln_routed(d) and the three folded panels and folded biases exist (ABI 9;
+//                 knob 45), else as launches into d.h (kX3r).
+//   kFp32         any other layer: gemm_nt_ws; after a LayerNorm gemm_ln_nt where *_wf exists -- exactly -1 ("shape not taken")
+//                 falls to layernorm into d.h + gemm_nt_ws, any other non-zero return is an error.
+// Vocabulary projection (kVocab): every rung on its own gate, -1 = try the next rung, the last always runs
+//   1. gemm_ln_nt on seq_wf
+//   2. gemm_ln_nt_x3r on seq_wfp -- narrow vocabularies only (vocab < 4096, or knob 45 = 2): every column tile's workgroup
+//      repeats the row statistics, which at V = 5 000 (79 column tiles) costs what the LayerNorm launch does (58.6 vs 59.0 us
+//      at 1 280 rows, 105 vs 117 at 2 560: profiles/r04_s_*); with handed-over statistics (3) the prologue reads 128 B per row
+//   3. layernorm into d.h, then gemm_nt_x3r on seq_wp   4. gemm_nt_x3 on seq_w3 when x3_routed   5. gemm_nt_ws
+//   Without want_logits: layernorm into d.h only (sbk_decoder_prefix_f32 reads it).
+// Encoder memory and CTC head (project_rows): gemm_nt_x3 when the image exists and x3_routed; -1 (no workspace for this stream
+//   yet: first use inside a graph capture) falls to gemm_nt.
+// The persistent single-launch step (csrc/decoder_persist.hip) is tried before any of this: decoder_step.
+enum Route { kFp32, kX3r, kX3rLn, kVocab };
+Route layer_route(const sbk_decoder_weights* W, const sbk_decoder_layer& L, int n) {
+  const int dm = W->d_model;
+  const bool panels = L.sa_in_wp && L.sa_out_wp && L.ca_q_wp && L.ca_out_wp && L.ff1_wp && L.ff2_wp;
+  const bool biases_aligned = sbk::aligned16(L.sa_in_b) && sbk::aligned16(L.sa_out_b) && sbk::aligned16(L.ca_in_b) &&
+                              sbk::aligned16(L.ca_out_b) && sbk::aligned16(L.ff1_b) && sbk::aligned16(L.ff2_b) &&
+                              sbk::aligned16(L.sa_in_bf) && sbk::aligned16(L.ca_q_bf) && sbk::aligned16(L.ff1_bf);
+  if (!(panels && sbk::x3r_routed(n, dm, dm) && sbk::x3r_routed(n, dm, W->d_ffn) && biases_aligned)) return kFp32;
+  const bool lnf = sbk::x3r_ln_routed(dm) && L.sa_in_wfp && L.sa_in_bf && L.ca_q_wfp && L.ca_q_bf && L.ff1_wfp && L.ff1_bf;
+  return lnf ? kX3rLn : kX3r;
+}
+
+// The projections of one decode step: n rows, results with row pitch N.
+struct StepRouter {
+  const DecoderBufs& d;
+  int n;
+  float eps;  // of every LayerNorm
+  hipStream_t st;
+  // C[n, N] = act(A[n, K] W^T + b) [+ R]
+  int project(const Proj& P, const float* A, int lda, const float* R, float* C, int N, int K, int act, Route route) const {
+    if (route != kFp32) {
+      const int rc = P.wp && sbk::x3r_routed(n, N, K) ? sbk::gemm_nt_x3r(A, lda, P.wp, P.b, R, N, C, N, n, N, K, act, 1.0f, st) : -1;
+      if (route != kVocab || rc != -1) return rc;
+      if (P.w3 && sbk::x3_routed(n, N, K)) {
+        const int rc3 = sbk::gemm_nt_x3(A, lda, P.w3, P.b, R, R ? N : 0, C, N, n, N, K, act, 1.0f, nullptr, 0, st);
+        if (rc3 != -1) return rc3;
+      }
+    }
+    return sbk::gemm_nt_ws(A, lda, P.w, K, P.b, R, R ? N : 0, C, N, n, N, K, act, 1.0f, nullptr, 0, d.splitk, d.splitk_floats, st);
+  }
+  // C[n, N] = act(LayerNorm(x[n, K]) W^T + b); tmp [n, K] takes the LayerNorm's output where it is a launch of its own
+  int ln_project(const Proj& P, const float* x, float* tmp, float* C, int N, int K, int act, Route route) const {
+    if ((route == kFp32 || route == kVocab) && P.wf) {
+      const int rc = sbk::gemm_ln_nt(x, K, P.wf, K, P.bf, nullptr, 0, C, N, n, N, K, eps, act, 1.0f, st);
+      if (rc != -1) return rc;
+    }
+    if (route == kX3rLn || (route == kVocab && P.wfp && P.bf && sbk::x3r_ln_routed(K) && sbk::x3r_routed(n, N, K) &&
+                            (N < 4096 || sbk::g_x3r_ln == 2))) {
+      const int rc = sbk::gemm_ln_nt_x3r(x, K, P.wfp, P.bf, nullptr, 0, C, N, n, N, K, eps, act, 1.0f, st);
+      if (route == kX3rLn || rc != -1) return rc;
+    }
+    SBK_TRY(sbk::layernorm(x, P.ln_g, P.ln_b, tmp, n, K, eps, SBK_ACT_NONE, st));
+    return project(P, tmp, K, nullptr, C, N, K, act, route);
+  }
+};
+
+// C[M, N] (row pitch ldc) = A[M, K] W^T + b for the once-per-batch projections of the encoder output
+int project_rows(const Proj& P, const float* A, float* C, int ldc, int M, int N, int K, hipStream_t st) {
+  int rc = -1;
+  if (P.w3 && sbk::x3_routed(M, N, K))
+    rc = sbk::gemm_nt_x3(A, K, P.w3, P.b, nullptr, 0, C, ldc, M, N, K, SBK_ACT_NONE, 1.0f, nullptr, 0, st);
+  if (rc == -1) rc = sbk::gemm_nt(A, K, P.w, K, P.b, nullptr, 0, C, ldc, M, N, K, SBK_ACT_NONE, 1.0f, nullptr, 0, st);
+  return rc;
+}
 
 // Project the encoder memory to the cross-attention K/V of every layer, once per batch.
-int project_memory(const sbk_decoder_weights* W, const DecoderBufs& d, const float* enc, int B, int T,
-                   hipStream_t st) {
+int project_memory(const sbk_decoder_weights* W, const DecoderBufs& d, const float* enc, int B, int T, hipStream_t st) {
   const int dm = W->d_model;
   SBK_HIP(hipMemsetAsync(d.pbar, 0, (64 + 512 + 256) * sizeof(int32_t), st));
   d.pseq = 0;
   d.pgrid = 0;
-  for (int l = 0; l < W->n_layers; ++l) {
-    const sbk_decoder_layer& L = W->layers[l];
-    float* dst = d.ckv[l];
-    int rc = -1;
-    if (L.ca_kv_w3 && sbk::x3_routed(B * T, 2 * dm, dm))
-      rc = sbk::gemm_nt_x3(enc, dm, L.ca_kv_w3, L.ca_in_b + dm, nullptr, 0, dst, 2 * dm, B * T, 2 * dm, dm, SBK_ACT_NONE, 1.0f,
-                           nullptr, 0, st);
-    if (rc == -1)  // (not routed, or no workspace for this stream yet: first use inside a graph capture)
-      rc = sbk::gemm_nt(enc, dm, L.ca_in_w + (size_t)dm * dm, dm, L.ca_in_b + dm, nullptr, 0, dst, 2 * dm, B * T, 2 * dm, dm,
-                        SBK_ACT_NONE, 1.0f, nullptr, 0, st);
-    SBK_TRY(rc);
-  }
+  for (int l = 0; l < W->n_layers; ++l)
+    SBK_TRY(project_rows(layer_projs(W->layers[l], dm).ca_kv, enc, d.ckv[l], 2 * dm, B * T, 2 * dm, dm, st));
   return 0;
 }
 
@@ -1025,7 +1115,7 @@ int project_memory(const sbk_decoder_weights* W, const DecoderBufs& d, const flo
 int decoder_step(const sbk_decoder_weights* W, const DecoderBufs& d, const int32_t* tokens, const int32_t* kv_slot,
                  const int32_t* enc_len, int step, int n, int B, int T, int beam, int Lmax, bool want_logits,
                  hipStream_t st) {
-  const int dm = W->d_model, H = W->nhead;
+  const int dm = W->d_model, H = W->nhead, dff = W->d_ffn;
   // a beam's worth of rows (<= 16): the whole stack of the step as ONE cooperative launch (csrc/decoder_persist.hip)
   if (!sbk::g_step_ptr && sbk::persist_eligible(W, n, B, beam, Lmax)) {
     const int rc = sbk::decoder_step_persist(W, tokens, kv_slot, enc_len, d.x, d.qkv, d.ctx, d.q, d.ff, d.h, d.logits, d.kcache,
@@ -1038,105 +1128,23 @@ int decoder_step(const sbk_decoder_weights* W, const DecoderBufs& d, const int32
   }
   const float emb_scale = W->emb_scale > 0.0f ? W->emb_scale : sqrtf((float)dm);  // NormalizedEmbedding: sqrt(d_model)
   SBK_TRY(sbk::embed_pos(tokens, W->emb, W->pe + (size_t)step * dm, d.x, n, dm, emb_scale, st));
-  // a projection with a panel image of its weights and enough hypothesis rows: sbk_gemm_nt_x3r (fp32 result on the bf16
-  // matrix pipe); -1 = not routed (the register-operand / LDS-tiled fp32-MFMA kernels below)
-  auto x3r = [&](const float* A, int lda, const uint16_t* WP, const float* b, const float* R, float* C, int N, int K, int act) -> int {
-    if (!WP || !sbk::x3r_routed(n, N, K)) return -1;
-    return sbk::gemm_nt_x3r(A, lda, WP, b, R, N, C, N, n, N, K, act, 1.0f, st);
-  };
-  // the routed kernels move bias rows as 16-byte vectors: a layer with an unaligned bias view takes the fp32 kernels below
-  // instead of failing inside the route
-  auto biases_aligned = [](const sbk_decoder_layer& L) {
-    return sbk::aligned16(L.sa_in_b) && sbk::aligned16(L.sa_out_b) && sbk::aligned16(L.ca_in_b) && sbk::aligned16(L.ca_out_b) &&
-           sbk::aligned16(L.ff1_b) && sbk::aligned16(L.ff2_b) && sbk::aligned16(L.sa_in_bf) && sbk::aligned16(L.ca_q_bf) &&
-           sbk::aligned16(L.ff1_bf);
-  };
+  const StepRouter r{d, n, W->ln_eps, st};
   for (int l = 0; l < W->n_layers; ++l) {
     const sbk_decoder_layer& L = W->layers[l];
-    if (L.sa_in_wp && L.sa_out_wp && L.ca_q_wp && L.ca_out_wp && L.ff1_wp && L.ff2_wp && sbk::x3r_routed(n, dm, dm) &&
-        sbk::x3r_routed(n, dm, W->d_ffn) && biases_aligned(L)) {
-      // norm1 / norm2 / norm3 inside the projection they feed (folded panel images, ABI 9; knob 45), else as launches
-      const bool lnf = sbk::x3r_ln_routed(dm) && L.sa_in_wfp && L.sa_in_bf && L.ca_q_wfp && L.ca_q_bf && L.ff1_wfp && L.ff1_bf;
-      auto ln_proj = [&](const float* g_, const float* b_, const uint16_t* WFP, const float* bfold, const uint16_t* WP, const float* bias,
-                         float* C, int N, int act) -> int {
-        if (lnf) return sbk::gemm_ln_nt_x3r(d.x, dm, WFP, bfold, nullptr, 0, C, N, n, N, dm, W->ln_eps, act, 1.0f, st);
-        SBK_TRY(sbk::layernorm(d.x, g_, b_, d.h, n, dm, W->ln_eps, SBK_ACT_NONE, st));
-        return x3r(d.h, dm, WP, bias, nullptr, C, N, dm, act);
-      };
-      SBK_TRY(ln_proj(L.ln1_g, L.ln1_b, L.sa_in_wfp, L.sa_in_bf, L.sa_in_wp, L.sa_in_b, d.qkv, 3 * dm, SBK_ACT_NONE));
-      SBK_TRY(sbk::self_attn_step(d.qkv, d.kcache[l], d.vcache[l], kv_slot, d.ctx, n, dm, H, step, n, Lmax, st, nullptr, 0, 0,
-                                  0, 0, beam));
-      SBK_TRY(x3r(d.ctx, dm, L.sa_out_wp, L.sa_out_b, d.x, d.x, dm, dm, SBK_ACT_NONE));
-      SBK_TRY(ln_proj(L.ln2_g, L.ln2_b, L.ca_q_wfp, L.ca_q_bf, L.ca_q_wp, L.ca_in_b, d.q, dm, SBK_ACT_NONE));
-      SBK_TRY(sbk::cross_attn_step(d.q, d.ckv[l], enc_len, d.ctx, d.xpart, B, T, dm, H, beam, st));
-      SBK_TRY(x3r(d.ctx, dm, L.ca_out_wp, L.ca_out_b, d.x, d.x, dm, dm, SBK_ACT_NONE));
-      SBK_TRY(ln_proj(L.ln3_g, L.ln3_b, L.ff1_wfp, L.ff1_bf, L.ff1_wp, L.ff1_b, d.ff, W->d_ffn, W->ffn_act));
-      SBK_TRY(x3r(d.ff, W->d_ffn, L.ff2_wp, L.ff2_b, d.x, d.x, dm, W->d_ffn, SBK_ACT_NONE));
-      continue;
-    }
-    int frc = L.sa_in_wf ? sbk::gemm_ln_nt(d.x, dm, L.sa_in_wf, dm, L.sa_in_bf, nullptr, 0, d.qkv, 3 * dm, n, 3 * dm, dm,
-                                           W->ln_eps, SBK_ACT_NONE, 1.0f, st)
-                         : -1;
-    if (frc > 0 || frc < -1) return frc;
-    if (frc == -1) {
-      SBK_TRY(sbk::layernorm(d.x, L.ln1_g, L.ln1_b, d.h, n, dm, W->ln_eps, SBK_ACT_NONE, st));
-      SBK_TRY(sbk::gemm_nt_ws(d.h, dm, L.sa_in_w, dm, L.sa_in_b, nullptr, 0, d.qkv, 3 * dm, n, 3 * dm, dm, SBK_ACT_NONE,
-                              1.0f, nullptr, 0, d.splitk, d.splitk_floats, st));
-    }
+    const Route route = layer_route(W, L, n);
+    const LayerProjs P = layer_projs(L, dm);
+    SBK_TRY(r.ln_project(P.sa_in, d.x, d.h, d.qkv, 3 * dm, dm, SBK_ACT_NONE, route));
     SBK_TRY(sbk::self_attn_step(d.qkv, d.kcache[l], d.vcache[l], kv_slot, d.ctx, n, dm, H, step, n, Lmax, st, nullptr, 0, 0,
                                 0, 0, beam));
-    SBK_TRY(sbk::gemm_nt_ws(d.ctx, dm, L.sa_out_w, dm, L.sa_out_b, d.x, dm, d.x, dm, n, dm, dm, SBK_ACT_NONE, 1.0f, nullptr,
-                         0, d.splitk, d.splitk_floats, st));
-    frc = L.ca_q_wf ? sbk::gemm_ln_nt(d.x, dm, L.ca_q_wf, dm, L.ca_q_bf, nullptr, 0, d.q, dm, n, dm, dm, W->ln_eps,
-                                      SBK_ACT_NONE, 1.0f, st)
-                    : -1;
-    if (frc > 0 || frc < -1) return frc;
-    if (frc == -1) {
-      SBK_TRY(sbk::layernorm(d.x, L.ln2_g, L.ln2_b, d.h, n, dm, W->ln_eps, SBK_ACT_NONE, st));
-      SBK_TRY(sbk::gemm_nt_ws(d.h, dm, L.ca_in_w, dm, L.ca_in_b, nullptr, 0, d.q, dm, n, dm, dm, SBK_ACT_NONE, 1.0f, nullptr,
-                              0, d.splitk, d.splitk_floats, st));
-    }
+    SBK_TRY(r.project(P.sa_out, d.ctx, dm, d.x, d.x, dm, dm, SBK_ACT_NONE, route));
+    SBK_TRY(r.ln_project(P.ca_q, d.x, d.h, d.q, dm, dm, SBK_ACT_NONE, route));
     SBK_TRY(sbk::cross_attn_step(d.q, d.ckv[l], enc_len, d.ctx, d.xpart, B, T, dm, H, beam, st));
-    SBK_TRY(sbk::gemm_nt_ws(d.ctx, dm, L.ca_out_w, dm, L.ca_out_b, d.x, dm, d.x, dm, n, dm, dm, SBK_ACT_NONE, 1.0f, nullptr,
-                         0, d.splitk, d.splitk_floats, st));
-    frc = L.ff1_wf ? sbk::gemm_ln_nt(d.x, dm, L.ff1_wf, dm, L.ff1_bf, nullptr, 0, d.ff, W->d_ffn, n, W->d_ffn, dm, W->ln_eps,
-                                     W->ffn_act, 1.0f, st)
-                   : -1;
-    if (frc > 0 || frc < -1) return frc;
-    if (frc == -1) {
-      SBK_TRY(sbk::layernorm(d.x, L.ln3_g, L.ln3_b, d.h, n, dm, W->ln_eps, SBK_ACT_NONE, st));
-      SBK_TRY(sbk::gemm_nt_ws(d.h, dm, L.ff1_w, dm, L.ff1_b, nullptr, 0, d.ff, W->d_ffn, n, W->d_ffn, dm, W->ffn_act, 1.0f,
-                              nullptr, 0, d.splitk, d.splitk_floats, st));
-    }
-    SBK_TRY(sbk::gemm_nt_ws(d.ff, W->d_ffn, L.ff2_w, W->d_ffn, L.ff2_b, d.x, dm, d.x, dm, n, dm, W->d_ffn, SBK_ACT_NONE, 1.0f,
-                         nullptr, 0, d.splitk, d.splitk_floats, st));
+    SBK_TRY(r.project(P.ca_out, d.ctx, dm, d.x, d.x, dm, dm, SBK_ACT_NONE, route));
+    SBK_TRY(r.ln_project(P.ff1, d.x, d.h, d.ff, dff, dm, W->ffn_act, route));
+    SBK_TRY(r.project(P.ff2, d.ff, dff, d.x, d.x, dm, dff, SBK_ACT_NONE, route));
   }
-  if (want_logits && W->seq_wf) {  // final LayerNorm fused into seq_lin
-    const int frc = sbk::gemm_ln_nt(d.x, dm, W->seq_wf, dm, W->seq_bf, nullptr, 0, d.logits, W->vocab, n, W->vocab, dm,
-                                    W->ln_eps, SBK_ACT_NONE, 1.0f, st);
-    if (frc != -1) return frc;
-  }
-  // decoder.norm inside the vocabulary projection -- for narrow vocabularies only: every column tile's workgroup repeats the
-  // row statistics, which at V = 5 000 (79 column tiles) costs what the LayerNorm launch does (58.6 vs 59.0 us at 1 280 rows,
-  // 105 vs 117 at 2 560: profiles/r04_s_*); knob 45 = 2 forces it; with handed-over statistics (3) the prologue reads 128 B per row
-  if (want_logits && W->seq_wfp && W->seq_bf && sbk::x3r_ln_routed(dm) && sbk::x3r_routed(n, W->vocab, dm) &&
-      (W->vocab < 4096 || sbk::g_x3r_ln == 2)) {
-    const int rc = sbk::gemm_ln_nt_x3r(d.x, dm, W->seq_wfp, W->seq_bf, nullptr, 0, d.logits, W->vocab, n, W->vocab, dm, W->ln_eps,
-                                       SBK_ACT_NONE, 1.0f, st);
-    if (rc != -1) return rc;
-  }
-  SBK_TRY(sbk::layernorm(d.x, W->final_ln_g, W->final_ln_b, d.h, n, dm, W->ln_eps, SBK_ACT_NONE, st));
-  if (want_logits) {
-    int rc = x3r(d.h, dm, W->seq_wp, W->seq_b, nullptr, d.logits, W->vocab, dm, SBK_ACT_NONE);
-    if (rc == -1 && W->seq_w3 && sbk::x3_routed(n, W->vocab, dm))
-      rc = sbk::gemm_nt_x3(d.h, dm, W->seq_w3, W->seq_b, nullptr, 0, d.logits, W->vocab, n, W->vocab, dm, SBK_ACT_NONE, 1.0f,
-                           nullptr, 0, st);
-    if (rc == -1)
-      rc = sbk::gemm_nt_ws(d.h, dm, W->seq_w, dm, W->seq_b, nullptr, 0, d.logits, W->vocab, n, W->vocab, dm, SBK_ACT_NONE, 1.0f,
-                           nullptr, 0, d.splitk, d.splitk_floats, st);
-    SBK_TRY(rc);
-  }
-  return 0;
+  if (!want_logits) return sbk::layernorm(d.x, W->final_ln_g, W->final_ln_b, d.h, n, dm, W->ln_eps, SBK_ACT_NONE, st);
+  return r.ln_project(seq_proj(W), d.x, d.h, d.logits, W->vocab, dm, SBK_ACT_NONE, kVocab);
 }
 
 // ---------------------------------------------------------------- TransformerLM scorer (a20)
@@ -1325,22 +1333,68 @@ void carve_beam(Carver& c, BeamBufs& b, int B, int beam, int T, int V, int Lmax,
   }
 }
 
-}  // namespace
+// ---------------------------------------------------------------- workspace layouts
+// Every entry point's workspace is laid out ONCE, by its layout's carve(): sbk_X_workspace_bytes is a dry carve (workspace =
+// NULL: sizes only); the entry carves its buffer and requires the size this returns -- the two cannot drift apart.
+template <typename Layout, typename... Args>
+size_t carve_layout(Layout& lay, void* workspace, Args... args) {
+  Carver c{static_cast<char*>(workspace), 0, workspace == nullptr};
+  lay.carve(c, args...);
+  return c.used + 256;
+}
 
-extern "C" size_t sbk_beam_search_workspace_bytes(const sbk_decoder_weights* W, const sbk_search_config* cfg, int B,
-                                                  int T) {
-  if (!W || !cfg) return 0;
-  Carver c{nullptr, 0, true};
+// decoder position of search step 0 (the prompt but its last token primes the KV cache) / pitch of the per-hypothesis tables
+int beam_pos_off(const sbk_search_config* cfg) { return cfg->prompt && cfg->prompt_len > 1 ? cfg->prompt_len - 1 : 0; }
+int beam_lmax(const sbk_search_config* cfg) { return (cfg->max_steps > 0 ? cfg->max_steps : 1) + beam_pos_off(cfg); }
+const sbk_lm_weights* beam_lm(const sbk_search_config* cfg) { return (cfg->lm && cfg->lm_weight != 0.0f) ? cfg->lm : nullptr; }
+
+struct BeamLayout {  // sbk_beam_search_f32
   DecoderBufs d;
   BeamBufs bb;
-  const int Lmax = (cfg->max_steps > 0 ? cfg->max_steps : 1) + (cfg->prompt && cfg->prompt_len > 1 ? cfg->prompt_len - 1 : 0);
-  carve_decoder(c, d, W, B * cfg->beam, B, T, Lmax);
-  carve_beam(c, bb, B, cfg->beam, T, W->vocab, Lmax, cfg->ctc_weight > 0.0f, cfg->ctc_window_size);
-  if (cfg->lm && cfg->lm_weight != 0.0f) {
-    LmBufs lb;
-    carve_lm(c, lb, cfg->lm, B * cfg->beam, Lmax);
+  LmBufs lb;  // only with an LM scorer
+  void carve(Carver& c, const sbk_decoder_weights* W, const sbk_search_config* cfg, int B, int T) {
+    const int n = B * cfg->beam, Lmax = beam_lmax(cfg);
+    carve_decoder(c, d, W, n, B, T, Lmax);
+    carve_beam(c, bb, B, cfg->beam, T, W->vocab, Lmax, cfg->ctc_weight > 0.0f, cfg->ctc_window_size);
+    if (beam_lm(cfg)) carve_lm(c, lb, beam_lm(cfg), n, Lmax);
   }
-  return c.used + 256;
+};
+
+// the per-row tables of the entries that step one column of tokens at a time
+struct StepTail {
+  int32_t* kv_slot;                // [n][L] ancestry table: every row reads its own cache slot
+  int32_t* col;                    // [n] token column of a teacher-forced / prompt position (entries that have one)
+  int32_t *n_ended, *tok, *ended;  // [64] counters, [n] next input token, [n] ended flag: one block
+  void carve(Carver& c, int n, int L, bool with_col) {
+    kv_slot = c.take<int32_t>((size_t)n * L);
+    col = with_col ? c.take<int32_t>((size_t)n) : nullptr;
+    n_ended = c.take<int32_t>(64 + 2 * (size_t)n);
+    if (!c.dry) tok = n_ended + 64, ended = tok + n;
+  }
+};
+struct DecoderLayout {  // sbk_decoder_prefix_f32, sbk_greedy_search_f32 (no column), sbk_prompted_greedy_search_f32
+  DecoderBufs d;
+  StepTail t;
+  void carve(Carver& c, const sbk_decoder_weights* W, int n, int T, int L, bool with_col) {
+    carve_decoder(c, d, W, n, n, T, L);
+    t.carve(c, n, L, with_col);
+  }
+};
+struct LmLayout {  // sbk_lm_prefix_f32
+  LmBufs d;
+  StepTail t;
+  void carve(Carver& c, const sbk_lm_weights* LM, int n, int L) {
+    carve_lm(c, d, LM, n, L);
+    t.carve(c, n, L, true);
+  }
+};
+
+}  // namespace
+
+extern "C" size_t sbk_beam_search_workspace_bytes(const sbk_decoder_weights* W, const sbk_search_config* cfg, int B, int T) {
+  if (!W || !cfg) return 0;
+  BeamLayout lay;
+  return carve_layout(lay, nullptr, W, cfg, B, T);
 }
 
 extern "C" int sbk_beam_search_f32(const sbk_decoder_weights* W, const sbk_search_config* cfg, const float* enc,
@@ -1357,7 +1411,7 @@ extern "C" int sbk_beam_search_f32(const sbk_decoder_weights* W, const sbk_searc
   SBK_REQUIRE(W->seq_w && W->seq_b, "beam_search: seq_lin weights missing");
   SBK_REQUIRE(cfg->beam >= 1 && cfg->beam <= kMaxBeamLarge, "beam_search: beam %d outside [1,%d]", cfg->beam,
               kMaxBeamLarge);
-  const int pos_off = cfg->prompt && cfg->prompt_len > 1 ? cfg->prompt_len - 1 : 0;  // decoder position of search step 0
+  const int pos_off = beam_pos_off(cfg);
   SBK_REQUIRE(pos_off + cfg->max_steps <= W->max_len, "beam_search: %d prompt + %d steps exceed the positional table (%d)",
               pos_off, cfg->max_steps, W->max_len);
   SBK_REQUIRE(!cfg->prompt || (cfg->prompt_len >= 1 && !(cfg->lm && cfg->lm_weight != 0.0f) && !cfg->utt_max_steps &&
@@ -1371,38 +1425,29 @@ extern "C" int sbk_beam_search_f32(const sbk_decoder_weights* W, const sbk_searc
   SBK_REQUIRE(!ctc || (ctc_w && ctc_b), "beam_search: ctc_weight > 0 needs the ctc_lin weights");
   SBK_REQUIRE(!ctc || (cfg->bos != cfg->eos && cfg->bos != cfg->blank && cfg->eos != cfg->blank),
               "Set blank, eos and bos to different indexes for joint ATT/CTC or CTC decoding");
-  SBK_REQUIRE(workspace_bytes >= sbk_beam_search_workspace_bytes(W, cfg, B, T), "beam_search: workspace too small");
+  BeamLayout lay;
+  SBK_REQUIRE(workspace_bytes >= carve_layout(lay, workspace, W, cfg, B, T), "beam_search: workspace too small");
   SBK_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "beam_search: workspace must be 256-byte aligned");
   hipStream_t st = sbk::as_stream(stream);
-  const int beam = cfg->beam, V = W->vocab, n = B * beam, dm = W->d_model;
-  const int Lmax = (cfg->max_steps > 0 ? cfg->max_steps : 1) + pos_off;
+  const int beam = cfg->beam, V = W->vocab, n = B * beam, dm = W->d_model, Lmax = beam_lmax(cfg);
   if (steps_run) *steps_run = 0;
-  if (B == 0) return 0;
 
-  Carver c{static_cast<char*>(workspace), 0, false};
-  DecoderBufs d;
-  BeamBufs bb;
-  carve_decoder(c, d, W, n, B, T, Lmax);
-  carve_beam(c, bb, B, beam, T, V, Lmax, ctc, cfg->ctc_window_size);
-  const sbk_lm_weights* LM = (cfg->lm && cfg->lm_weight != 0.0f) ? cfg->lm : nullptr;
-  LmBufs lb;
+  const sbk_lm_weights* LM = beam_lm(cfg);
   if (LM) {
     SBK_TRY(check_lm(LM));
     SBK_REQUIRE(LM->vocab == V, "beam_search: the LM scores %d tokens, the decoder %d", LM->vocab, V);
     SBK_REQUIRE(cfg->max_steps <= LM->max_len, "beam_search: %d steps exceed the LM positional table", cfg->max_steps);
     SBK_REQUIRE(cfg->lm_temperature > 0.0f, "beam_search: lm_temperature must be positive");
-    carve_lm(c, lb, LM, n, Lmax);
   }
+  const DecoderBufs& d = lay.d;
+  BeamBufs& bb = lay.bb;
+  const LmBufs& lb = lay.lb;
   const float* extra = LM ? lb.logits : nullptr;  // weighted LM log-probs of the step
 
   const int Vp = ctc_pitch(V);  // row pitch of the CTC posteriors
   SBK_TRY(project_memory(W, d, enc, B, T, st));
   if (ctc) {  // CTCScorer.reset_mem (scorer.py:239-255): log_softmax(ctc_lin(enc)), then the frame mask
-    int rc = -1;
-    if (cfg->ctc_w3 && sbk::x3_routed(B * T, V, dm))
-      rc = sbk::gemm_nt_x3(enc, dm, cfg->ctc_w3, ctc_b, nullptr, 0, bb.ctc_x, Vp, B * T, V, dm, SBK_ACT_NONE, 1.0f, nullptr, 0, st);
-    if (rc == -1) rc = sbk::gemm_nt(enc, dm, ctc_w, dm, ctc_b, nullptr, 0, bb.ctc_x, Vp, B * T, V, dm, SBK_ACT_NONE, 1.0f, nullptr, 0, st);
-    SBK_TRY(rc);
+    SBK_TRY(project_rows(Proj{ctc_w, ctc_b, cfg->ctc_w3}, enc, bb.ctc_x, Vp, B * T, V, dm, st));
     SBK_TRY(sbk::log_softmax_rows(bb.ctc_x, bb.ctc_x, B * T, V, 1.0f, 1.0f, st, nullptr, nullptr, Vp));
     SBK_HIP(hipMemsetAsync(bb.phi[1], 0, sbk::ctc_state_floats(B, beam, T) * sizeof(float), st));  // zero table padding
     SBK_TRY(sbk::ctc_prepare(bb.ctc_x, bb.ctc_xb, enc_len, bb.phi[0], bb.psi_prev[0], B, T, V, beam, cfg->blank, st, Vp));
@@ -1638,22 +1683,61 @@ extern "C" int sbk_beam_search_f32(const sbk_decoder_weights* W, const sbk_searc
   return 0;
 }
 
+__global__ void gather_col_kernel(const int32_t* __restrict__ tokens, int32_t* __restrict__ col, int n, int L, int p) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) col[i] = tokens[(size_t)i * L + p];
+}
+
+// Teacher-forced run of a KV-cached step over the prefix tokens [n, L]: per position, its token column -> step(p) -> the
+// step's `width`-wide result rows `src` to out[:, p, :].
+template <typename Step>
+static int prefix_loop(const int32_t* tokens, const StepTail& t, int n, int L, Step step, const float* src, int width,
+                       float* out, const char* init_label, const char* copy_label, hipStream_t st) {
+  SBK_LAUNCH(greedy_init_kernel, dim3(sbk::cdiv(n, 256)), dim3(256), 0, st, t.tok, t.ended, t.n_ended, t.kv_slot, n, L, 0);
+  SBK_TRY(sbk::launch_status(init_label));
+  for (int p = 0; p < L; ++p) {
+    SBK_LAUNCH(gather_col_kernel, dim3(sbk::cdiv(n, 256)), dim3(256), 0, st, tokens, t.col, n, L, p);
+    SBK_TRY(step(p));
+    SBK_LAUNCH(copy_rows_kernel, dim3(n), dim3(256), 0, st, src, out + (size_t)p * width, n, width, (long)L * width);
+    SBK_TRY(sbk::launch_status(copy_label));
+  }
+  return 0;
+}
+
+// Arg-max decoding of `steps` tokens from decoder position `first_pos` on: step -> (probe at the first step) -> greedy_pick ->
+// stop-rule poll every `check_every` steps.  Returns the steps issued in *steps_run.
+static int greedy_loop(const sbk_decoder_weights* W, const DecoderBufs& d, const StepTail& t, const int32_t* enc_len,
+                       int first_pos, int steps, int L, int out_stride, int32_t* out_tokens, float* out_scores,
+                       const float* logit_bias, const float* first_bias, float* first_probe, int probe_token,
+                       int32_t* host_flag, int check_every, int eos, int B, int T, int32_t* steps_run, hipStream_t st) {
+  int k = 0;
+  const bool polling = host_flag && check_every > 0 && g_poll.begin();
+  for (; k < steps; ++k) {
+    SBK_TRY(decoder_step(W, d, t.tok, t.kv_slot, enc_len, first_pos + k, B, B, T, 1, L, true, st));
+    if (k == 0 && first_probe)
+      SBK_LAUNCH(softmax_prob_kernel, dim3(B), dim3(256), 0, st, (const float*)d.logits, first_probe, W->vocab, probe_token);
+    SBK_LAUNCH(greedy_pick_kernel, dim3(B), dim3(256), 0, st, (const float*)d.logits, t.tok, t.ended, out_tokens, out_scores,
+               t.n_ended, W->vocab, k, out_stride, eos, logit_bias, k == 0 ? first_bias : (const float*)nullptr);
+    SBK_TRY(sbk::launch_status("greedy_pick"));
+    if (polling && ((k + 1) % check_every == 0)) {
+      const int r = g_poll.poll(t.n_ended, B, st);
+      if (r < 0) return sbk::fail(1, "greedy_search: stop-rule poll failed");
+      if (r == 1) {
+        ++k;
+        break;
+      }
+    }
+  }
+  if (steps_run) *steps_run = k;
+  return 0;
+}
+
 // Teacher-forced run of the KV-cached decoder over a given prefix: the TransformerASR.decode
 // surface (TransformerASR.py:426-473).  tokens [n,L] -> pred [n,L,d] (final LayerNorm output).
 extern "C" size_t sbk_decoder_prefix_workspace_bytes(const sbk_decoder_weights* W, int n, int T, int L) {
   if (!W) return 0;
-  Carver c{nullptr, 0, true};
-  DecoderBufs d;
-  carve_decoder(c, d, W, n, n, T, L);
-  c.take<int32_t>((size_t)n * L);  // kv_slot
-  c.take<int32_t>((size_t)n);      // tok column
-  c.take<int32_t>(64 + 2 * (size_t)n);
-  return c.used + 256;
-}
-
-__global__ void gather_col_kernel(const int32_t* __restrict__ tokens, int32_t* __restrict__ col, int n, int L, int p) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) col[i] = tokens[(size_t)i * L + p];
+  DecoderLayout lay;
+  return carve_layout(lay, nullptr, W, n, T, L, true);
 }
 
 extern "C" int sbk_decoder_prefix_f32(const sbk_decoder_weights* W, const int32_t* tokens, const float* enc,
@@ -1663,38 +1747,19 @@ extern "C" int sbk_decoder_prefix_f32(const sbk_decoder_weights* W, const int32_
   if (n == 0 || L == 0) return 0;  // empty batch: nothing to launch, the data pointers may be NULL
   SBK_REQUIRE(tokens && enc && enc_len && workspace && pred, "decoder_prefix: null");
   SBK_REQUIRE(L <= W->max_len, "decoder_prefix: prefix longer than the positional table");
-  SBK_REQUIRE(workspace_bytes >= sbk_decoder_prefix_workspace_bytes(W, n, T, L), "decoder_prefix: workspace too small");
+  DecoderLayout lay;
+  SBK_REQUIRE(workspace_bytes >= carve_layout(lay, workspace, W, n, T, L, true), "decoder_prefix: workspace too small");
   hipStream_t st = sbk::as_stream(stream);
-  if (n == 0 || L == 0) return 0;
-  Carver c{static_cast<char*>(workspace), 0, false};
-  DecoderBufs d;
-  carve_decoder(c, d, W, n, n, T, L);
-  int32_t* kv_slot = c.take<int32_t>((size_t)n * L);
-  int32_t* col = c.take<int32_t>((size_t)n);
-  int32_t* misc = c.take<int32_t>(64 + 2 * (size_t)n);
-  SBK_TRY(project_memory(W, d, enc, n, T, st));
-  SBK_LAUNCH(greedy_init_kernel, dim3(sbk::cdiv(n, 256)), dim3(256), 0, st, misc + 64, misc + 64 + n, misc, kv_slot, n, L, 0);
-  SBK_TRY(sbk::launch_status("prefix_init"));
-  for (int p = 0; p < L; ++p) {
-    SBK_LAUNCH(gather_col_kernel, dim3(sbk::cdiv(n, 256)), dim3(256), 0, st, tokens, col, n, L, p);
-    SBK_TRY(decoder_step(W, d, col, kv_slot, enc_len, p, n, n, T, 1, L, false, st));
-    SBK_LAUNCH(copy_rows_kernel, dim3(n), dim3(256), 0, st, (const float*)d.h, pred + (size_t)p * W->d_model, n,
-               W->d_model, (long)L * W->d_model);
-    SBK_TRY(sbk::launch_status("prefix_copy"));
-  }
-  return 0;
+  SBK_TRY(project_memory(W, lay.d, enc, n, T, st));
+  auto step = [&](int p) { return decoder_step(W, lay.d, lay.t.col, lay.t.kv_slot, enc_len, p, n, n, T, 1, L, false, st); };
+  return prefix_loop(tokens, lay.t, n, L, step, lay.d.h, W->d_model, pred, "prefix_init", "prefix_copy", st);
 }
 
 // TransformerLM.forward (TransformerLM.py:116-158) through the KV-cached step.
 extern "C" size_t sbk_lm_prefix_workspace_bytes(const sbk_lm_weights* LM, int n, int L) {
   if (!LM) return 0;
-  Carver c{nullptr, 0, true};
-  LmBufs d;
-  carve_lm(c, d, LM, n, L > 0 ? L : 1);
-  c.take<int32_t>((size_t)n * (L > 0 ? L : 1));
-  c.take<int32_t>((size_t)n);
-  c.take<int32_t>(64 + 2 * (size_t)n);
-  return c.used + 256;
+  LmLayout lay;
+  return carve_layout(lay, nullptr, LM, n, L > 0 ? L : 1);
 }
 
 extern "C" int sbk_lm_prefix_f32(const sbk_lm_weights* LM, const int32_t* tokens, void* workspace,
@@ -1703,37 +1768,18 @@ extern "C" int sbk_lm_prefix_f32(const sbk_lm_weights* LM, const int32_t* tokens
   if (n == 0 || L == 0) return 0;  // empty batch: nothing to launch, the data pointers may be NULL
   SBK_REQUIRE(tokens && workspace && logits, "lm_prefix: null");
   SBK_REQUIRE(L <= LM->max_len, "lm_prefix: prefix longer than the positional table");
-  SBK_REQUIRE(workspace_bytes >= sbk_lm_prefix_workspace_bytes(LM, n, L), "lm_prefix: workspace too small");
+  LmLayout lay;
+  SBK_REQUIRE(workspace_bytes >= carve_layout(lay, workspace, LM, n, L), "lm_prefix: workspace too small");
   hipStream_t st = sbk::as_stream(stream);
-  if (n == 0 || L == 0) return 0;
-  Carver c{static_cast<char*>(workspace), 0, false};
-  LmBufs d;
-  carve_lm(c, d, LM, n, L);
-  int32_t* kv_slot = c.take<int32_t>((size_t)n * L);
-  int32_t* col = c.take<int32_t>((size_t)n);
-  int32_t* misc = c.take<int32_t>(64 + 2 * (size_t)n);
-  SBK_LAUNCH(greedy_init_kernel, dim3(sbk::cdiv(n, 256)), dim3(256), 0, st, misc + 64, misc + 64 + n, misc, kv_slot, n, L, 0);
-  SBK_TRY(sbk::launch_status("lm_prefix_init"));
-  for (int p = 0; p < L; ++p) {
-    SBK_LAUNCH(gather_col_kernel, dim3(sbk::cdiv(n, 256)), dim3(256), 0, st, tokens, col, n, L, p);
-    SBK_TRY(lm_step(LM, d, col, kv_slot, tokens, L, 0, 0, p, n, L, st));
-    SBK_LAUNCH(copy_rows_kernel, dim3(n), dim3(256), 0, st, (const float*)d.logits, logits + (size_t)p * LM->vocab, n,
-               LM->vocab, (long)L * LM->vocab);
-    SBK_TRY(sbk::launch_status("lm_prefix_copy"));
-  }
-  return 0;
+  auto step = [&](int p) { return lm_step(LM, lay.d, lay.t.col, lay.t.kv_slot, tokens, L, 0, 0, p, n, L, st); };
+  return prefix_loop(tokens, lay.t, n, L, step, lay.d.logits, LM->vocab, logits, "lm_prefix_init", "lm_prefix_copy", st);
 }
 
 // S2STransformerGreedySearcher (seq2seq.py:176-367, temperature 0).
 extern "C" size_t sbk_greedy_search_workspace_bytes(const sbk_decoder_weights* W, int B, int T, int max_steps) {
   if (!W) return 0;
-  Carver c{nullptr, 0, true};
-  DecoderBufs d;
-  const int L = max_steps > 0 ? max_steps : 1;
-  carve_decoder(c, d, W, B, B, T, L);
-  c.take<int32_t>((size_t)B * L);
-  c.take<int32_t>(64 + 2 * (size_t)B);
-  return c.used + 256;
+  DecoderLayout lay;
+  return carve_layout(lay, nullptr, W, B, T, max_steps > 0 ? max_steps : 1, false);
 }
 
 extern "C" int sbk_greedy_search_f32(const sbk_decoder_weights* W, const float* enc, const int32_t* enc_len,
@@ -1747,55 +1793,28 @@ extern "C" int sbk_greedy_search_f32(const sbk_decoder_weights* W, const float* 
   }
   SBK_REQUIRE(enc && enc_len && workspace && out_tokens && out_scores && W->seq_w && W->seq_b, "greedy_search: null");
   SBK_REQUIRE(max_steps <= W->max_len, "greedy_search: too many steps for the positional table");
-  SBK_REQUIRE(workspace_bytes >= sbk_greedy_search_workspace_bytes(W, B, T, max_steps), "greedy: workspace too small");
+  const int L = max_steps > 0 ? max_steps : 1;
+  DecoderLayout lay;
+  SBK_REQUIRE(workspace_bytes >= carve_layout(lay, workspace, W, B, T, L, false), "greedy: workspace too small");
   hipStream_t st = sbk::as_stream(stream);
   if (steps_run) *steps_run = 0;
-  const int L = max_steps > 0 ? max_steps : 1;
-  if (B == 0) return 0;
-  Carver c{static_cast<char*>(workspace), 0, false};
-  DecoderBufs d;
-  carve_decoder(c, d, W, B, B, T, L);
-  int32_t* kv_slot = c.take<int32_t>((size_t)B * L);
-  int32_t* misc = c.take<int32_t>(64 + 2 * (size_t)B);
-  int32_t *n_ended = misc, *tok = misc + 64, *ended = misc + 64 + B;
-  SBK_TRY(project_memory(W, d, enc, B, T, st));
-  SBK_LAUNCH(greedy_init_kernel, dim3(sbk::cdiv(B, 256)), dim3(256), 0, st, tok, ended, n_ended, kv_slot, B, L, bos);
+  SBK_TRY(project_memory(W, lay.d, enc, B, T, st));
+  SBK_LAUNCH(greedy_init_kernel, dim3(sbk::cdiv(B, 256)), dim3(256), 0, st, lay.t.tok, lay.t.ended, lay.t.n_ended, lay.t.kv_slot,
+             B, L, bos);
   SBK_TRY(sbk::launch_status("greedy_init"));
   SBK_HIP(hipMemsetAsync(out_tokens, 0, (size_t)B * L * sizeof(int32_t), st));
   SBK_HIP(hipMemsetAsync(out_scores, 0, (size_t)B * L * sizeof(float), st));
-  int k = 0;
-  const bool polling = host_flag && check_every > 0 && g_poll.begin();
-  for (int step = min_steps; step < max_steps; ++step, ++k) {  // positions count from 0 (seq2seq.py:227)
-    SBK_TRY(decoder_step(W, d, tok, kv_slot, enc_len, k, B, B, T, 1, L, true, st));
-    SBK_LAUNCH(greedy_pick_kernel, dim3(B), dim3(256), 0, st, (const float*)d.logits, tok, ended, out_tokens,
-               out_scores, n_ended, W->vocab, k, L, eos, (const float*)nullptr, (const float*)nullptr);
-    SBK_TRY(sbk::launch_status("greedy_pick"));
-    if (polling && ((k + 1) % check_every == 0)) {
-      const int r = g_poll.poll(n_ended, B, st);
-      if (r < 0) return sbk::fail(1, "greedy_search: stop-rule poll failed");
-      if (r == 1) {
-        ++k;
-        break;
-      }
-    }
-  }
-  if (steps_run) *steps_run = k;
-  return 0;
+  // (the reference's step counter starts at min_steps, positions at 0, seq2seq.py:227; rows of L columns; no masks, no probe)
+  return greedy_loop(W, lay.d, lay.t, enc_len, 0, max_steps - min_steps, L, L, out_tokens, out_scores, nullptr, nullptr, nullptr, 0,
+                     host_flag, check_every, eos, B, T, steps_run, st);
 }
 
 // S2SWhisperGreedySearcher.forward (seq2seq.py:176-327 + :421-636): a token prompt common in length to the batch
 // primes the KV cache, then arg-max decoding with additive logit masks.
-extern "C" size_t sbk_prompted_greedy_search_workspace_bytes(const sbk_decoder_weights* W, int B, int T, int P,
-                                                             int max_new) {
+extern "C" size_t sbk_prompted_greedy_search_workspace_bytes(const sbk_decoder_weights* W, int B, int T, int P, int max_new) {
   if (!W) return 0;
-  Carver c{nullptr, 0, true};
-  DecoderBufs d;
-  const int L = (P > 0 ? P - 1 : 0) + (max_new > 0 ? max_new : 1);
-  carve_decoder(c, d, W, B, B, T, L);
-  c.take<int32_t>((size_t)B * L);
-  c.take<int32_t>((size_t)B);
-  c.take<int32_t>(64 + 2 * (size_t)B);
-  return c.used + 256;
+  DecoderLayout lay;
+  return carve_layout(lay, nullptr, W, B, T, (P > 0 ? P - 1 : 0) + (max_new > 0 ? max_new : 1), true);
 }
 
 extern "C" int sbk_prompted_greedy_search_f32(const sbk_decoder_weights* W, const float* enc, const int32_t* enc_len,
@@ -1815,47 +1834,26 @@ extern "C" int sbk_prompted_greedy_search_f32(const sbk_decoder_weights* W, cons
               W->max_len);
   SBK_REQUIRE(!out_probe || (probe_pos >= 0 && probe_pos < P && probe_token >= 0 && probe_token < W->vocab),
               "prompted_greedy_search: probe position / token out of range");
-  SBK_REQUIRE(workspace_bytes >= sbk_prompted_greedy_search_workspace_bytes(W, B, T, P, max_new),
-              "prompted_greedy_search: workspace too small");
+  DecoderLayout lay;
+  SBK_REQUIRE(workspace_bytes >= carve_layout(lay, workspace, W, B, T, L, true), "prompted_greedy_search: workspace too small");
   hipStream_t st = sbk::as_stream(stream);
-  Carver c{static_cast<char*>(workspace), 0, false};
-  DecoderBufs d;
-  carve_decoder(c, d, W, B, B, T, L);
-  int32_t* kv_slot = c.take<int32_t>((size_t)B * L);
-  int32_t* col = c.take<int32_t>((size_t)B);
-  int32_t* misc = c.take<int32_t>(64 + 2 * (size_t)B);
-  int32_t *n_ended = misc, *tok = misc + 64, *ended = misc + 64 + B;
+  const DecoderBufs& d = lay.d;
   SBK_TRY(project_memory(W, d, enc, B, T, st));
-  SBK_LAUNCH(greedy_init_kernel, dim3(sbk::cdiv(B, 256)), dim3(256), 0, st, tok, ended, n_ended, kv_slot, B, L, 0);
+  SBK_LAUNCH(greedy_init_kernel, dim3(sbk::cdiv(B, 256)), dim3(256), 0, st, lay.t.tok, lay.t.ended, lay.t.n_ended, lay.t.kv_slot,
+             B, L, 0);
   SBK_TRY(sbk::launch_status("greedy_init"));
   SBK_HIP(hipMemsetAsync(out_tokens, 0, (size_t)B * max_new * sizeof(int32_t), st));
   SBK_HIP(hipMemsetAsync(out_scores, 0, (size_t)B * max_new * sizeof(float), st));
   for (int p = 0; p + 1 < P; ++p) {  // the prompt but its last token: K/V only (logits where the probe sits)
     const bool probe = out_probe && p == probe_pos;
-    SBK_LAUNCH(gather_col_kernel, dim3(sbk::cdiv(B, 256)), dim3(256), 0, st, prompt, col, B, P, p);
-    SBK_TRY(decoder_step(W, d, col, kv_slot, enc_len, p, B, B, T, 1, L, probe, st));
+    SBK_LAUNCH(gather_col_kernel, dim3(sbk::cdiv(B, 256)), dim3(256), 0, st, prompt, lay.t.col, B, P, p);
+    SBK_TRY(decoder_step(W, d, lay.t.col, lay.t.kv_slot, enc_len, p, B, B, T, 1, L, probe, st));
     if (probe) SBK_LAUNCH(softmax_prob_kernel, dim3(B), dim3(256), 0, st, (const float*)d.logits, out_probe, W->vocab, probe_token);
   }
-  SBK_LAUNCH(gather_col_kernel, dim3(sbk::cdiv(B, 256)), dim3(256), 0, st, prompt, tok, B, P, P - 1);
+  SBK_LAUNCH(gather_col_kernel, dim3(sbk::cdiv(B, 256)), dim3(256), 0, st, prompt, lay.t.tok, B, P, P - 1);
   SBK_TRY(sbk::launch_status("prompt"));
-  int k = 0;
-  const bool polling = host_flag && check_every > 0 && g_poll.begin();
-  for (; k < max_new; ++k) {
-    SBK_TRY(decoder_step(W, d, tok, kv_slot, enc_len, P - 1 + k, B, B, T, 1, L, true, st));
-    if (k == 0 && out_probe && probe_pos == P - 1)
-      SBK_LAUNCH(softmax_prob_kernel, dim3(B), dim3(256), 0, st, (const float*)d.logits, out_probe, W->vocab, probe_token);
-    SBK_LAUNCH(greedy_pick_kernel, dim3(B), dim3(256), 0, st, (const float*)d.logits, tok, ended, out_tokens, out_scores,
-               n_ended, W->vocab, k, max_new, eos, logit_bias, k == 0 ? first_bias : (const float*)nullptr);
-    SBK_TRY(sbk::launch_status("greedy_pick"));
-    if (polling && ((k + 1) % check_every == 0)) {
-      const int r = g_poll.poll(n_ended, B, st);
-      if (r < 0) return sbk::fail(1, "greedy_search: stop-rule poll failed");
-      if (r == 1) {
-        ++k;
-        break;
-      }
-    }
-  }
-  if (steps_run) *steps_run = k < max_new ? k : max_new;
-  return 0;
+  // (from the last prompt position on; rows of max_new columns; the probe where it sits on the last prompt token)
+  return greedy_loop(W, lay.d, lay.t, enc_len, P - 1, max_new, L, max_new, out_tokens, out_scores, logit_bias, first_bias,
+                     out_probe && probe_pos == P - 1 ? out_probe : nullptr, probe_token, host_flag, check_every, eos, B, T,
+                     steps_run, st);
 }

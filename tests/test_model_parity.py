@@ -418,6 +418,182 @@ def test_decoder_on_the_x3r_route_vs_oracle(backend, ln):
             nat.prof_enable(False)
 
 
+# test_decode_step_launch_plan_per_route: profiler launch name -> count of (decoder_prefix over 3 positions, beam-4 CTC search of
+# 8 steps), recorded from the commit BEFORE search.hip's projection router existed (the hand-written ladders of decoder_step)
+# on the CPU emulator, which runs the same host code and the same profiler scopes as the GPU build.
+_STEP = dict(cross_attn_step=2, embed_pos=1, self_attn_step=2)  # per position / step of a two-layer decoder
+_SEARCH = dict(beam_update=8, ctc_advance=7, ctc_score_step=8, log_softmax=1, score_topk=8)
+
+
+def _plan(prefix, search, persist=False):
+    step = {} if persist else _STEP
+    return (dict({k: 3 * v for k, v in step.items()}, gemm_nt_32x64=2, **prefix),
+            dict({k: 8 * v for k, v in step.items()}, gemm_nt_32x64=3, **_SEARCH, **search))
+
+
+_LAUNCH_PLANS = {
+    # x3r layers with norm1/2/3 inside the projections; decoder.norm: a launch (prefix) / the few-row fused kernel (search)
+    "a": _plan(dict(gemm_ln_x3r=18, gemm_x3r=18, layernorm=3), dict(gemm_ln_x3r=48, gemm_x3r=48, gemm_skinny_ln=8)),
+    # x3r layers, every LayerNorm of a layer as a launch
+    "b": _plan(dict(gemm_x3r=36, layernorm=21), dict(gemm_x3r=96, layernorm=48, gemm_skinny_ln=8)),
+    # fp32 layers, LayerNorm folded
+    "c": _plan(dict(gemm_skinny=18, gemm_skinny_ln=18, layernorm=3), dict(gemm_skinny=48, gemm_skinny_ln=56)),
+    # fp32 layers, no folded weights: every LayerNorm a launch
+    "d": _plan(dict(gemm_skinny=36, layernorm=21), dict(gemm_skinny=104, layernorm=56)),
+    # d_ffn 384: ff2 has no panel, both layers whole on the fp32 route
+    "e": _plan(dict(gemm_skinny=18, gemm_skinny_ln=18, layernorm=3), dict(gemm_skinny=48, gemm_skinny_ln=56)),
+    # (a) with decoder.norm inside the panel vocabulary projection
+    "f": _plan(dict(gemm_ln_x3r=18, gemm_x3r=18, layernorm=3), dict(gemm_ln_x3r=56, gemm_x3r=48)),
+    # the single-launch step
+    "g": _plan(dict(decoder_step_persist=3), dict(decoder_step_persist=8), persist=True),
+}
+_ROUTE_KNOBS = dict(x3r_min_rows=1, persist=0, x3r_ln=1)
+_ROUTE_CONFIGS = {  # tag -> (d_ffn, fold, knobs)
+    "a": (512, True, _ROUTE_KNOBS),
+    "b": (512, True, dict(_ROUTE_KNOBS, x3r_ln=0)),
+    "c": (512, True, dict(_ROUTE_KNOBS, x3r_mode=0)),
+    "d": (512, False, dict(_ROUTE_KNOBS, x3r_mode=0)),
+    "e": (384, True, _ROUTE_KNOBS),
+    "f": (512, True, dict(_ROUTE_KNOBS, skinny_off=1)),
+    "g": (512, True, dict(x3r_min_rows=1, x3r_ln=1)),
+}
+_ROUTE_REFS = {}
+
+
+def _route_model(d_ffn):
+    """The decoder of test_decoder_on_the_x3r_route_vs_oracle (d_ffn 512) or one whose ff2 has no panel image (384), its
+    inputs and the oracle's results -- computed once per width, shared by the cases, never modified."""
+    if d_ffn not in _ROUTE_REFS:
+        from speechbrain_amd.inference.builders import build_modules
+
+        m = build_modules(dict(d_model=256, nhead=4, d_ffn=d_ffn, n_enc=1, n_dec=2, n_fft=512, win_length=32), vocab=60, seed=7)
+        mods = torch.nn.ModuleDict({k: m[k] for k in ("CNN", "Transformer", "seq_lin", "ctc_lin")})
+        gen = torch.Generator().manual_seed(19)
+        with torch.no_grad():
+            for name, p in mods.named_parameters():
+                if p.dim() == 1:
+                    p.add_(0.1 * torch.randn(p.shape, generator=gen))
+            mods["seq_lin"].w.weight.mul_(4.0)
+            mods["ctc_lin"].w.weight.mul_(4.0)
+        sd = {k: v.detach().clone() for k, v in mods.state_dict().items()}
+        cfg = O.ModelCfg(d_model=256, nhead=4, num_encoder_layers=1, num_decoder_layers=2, d_ffn=d_ffn, vocab=60)
+        enc = torch.randn(3, 30, 256, generator=gen)
+        wl = torch.tensor([1.0, 0.7, 0.9])
+        enc_len = torch.round(30 * wl).int()
+        tgt = torch.randint(0, 60, (3, 3), generator=gen)
+        pred = O.decode(tgt, enc, enc_len, sd, cfg, "Transformer.")
+        hyps, _, sc, _ = O.beam_search(enc, wl, sd, cfg, O.SearchCfg(beam=4, ctc_weight=0.4, max_decode_ratio=8.5 / 30))
+        _ROUTE_REFS[d_ffn] = (mods, enc, wl, enc_len, tgt, pred, hyps, sc)
+    return _ROUTE_REFS[d_ffn]
+
+
+@pytest.mark.parametrize("config", sorted(_ROUTE_CONFIGS))
+def test_decode_step_launch_plan_per_route(backend, config):
+    """Which kernels a decode step launches is decided in ONE place (csrc/search.hip, the route table above StepRouter); this
+    pins the decision for every route at the smallest decoder that reaches them all (d_model 256, 4 heads, 2 layers, vocabulary
+    60, 3 utterances x 30 frames): the exact launch names and counts of a 3-position decoder_prefix and of a beam-4 search with
+    CTC 0.4 (_LAUNCH_PLANS: recorded before the router existed), and the outputs against the oracle (prefix 5e-5, ids exact,
+    scores 1e-4).  (a) panel kernels with the LayerNorms inside, (b) with LayerNorm launches, (c) fp32 with folded LayerNorms,
+    (d) fp32 without folded weights, (e) a layer that lacks one panel (ff2 at d_ffn 384) takes the fp32 route WHOLE, (f) decoder.norm
+    inside the panel vocabulary projection, (g) the persistent single-launch step at 12 rows."""
+    nat, dev = backend
+    from speechbrain_amd.decoders import CTCScorer, S2STransformerBeamSearcher, ScorerBuilder
+
+    d_ffn, fold, knobs = _ROUTE_CONFIGS[config]
+    mods, enc, wl, enc_len, tgt, pred_ref, hyps_ref, sc_ref = _route_model(d_ffn)
+    mods = mods.to(dev).eval()
+
+    def run(fn):
+        nat.prof_reset()
+        nat.prof_enable(True)
+        try:
+            out = fn()
+        finally:
+            nat.prof_enable(False)
+        return out, {k: v["count"] for k, v in nat.prof_report().items()}
+
+    with nat.knobs(**knobs):
+        h = nat.DecoderHandle(mods["Transformer"], mods["seq_lin"], fold=fold)
+        assert bool(h.layers[0].ff2_wp) == (d_ffn == 512) and bool(h.layers[0].sa_in_wf) == fold
+        pred, plan_prefix = run(lambda: nat.decoder_prefix(h, tgt.int().to(dev), enc.to(dev), enc_len.to(dev)))
+        scorer = ScorerBuilder(full_scorers=[CTCScorer(ctc_fc=mods["ctc_lin"], blank_index=0, eos_index=2)], weights={"ctc": 0.4})
+        bs = S2STransformerBeamSearcher(modules=[mods["Transformer"], mods["seq_lin"]], bos_index=1, eos_index=2,
+                                        min_decode_ratio=0.0, max_decode_ratio=8.5 / 30, beam_size=4,
+                                        using_eos_threshold=False, length_normalization=True, scorer=scorer)
+        bs._dec_handle = h  # (the searcher would build a folded handle of its own)
+        (hyps, _, sc, _), plan_search = run(lambda: bs(enc.to(dev), wl.to(dev)))
+    print(config, plan_prefix, plan_search, float((pred.cpu() - pred_ref).abs().max()), float((sc.cpu() - sc_ref).abs().max()))
+    want_prefix, want_search = _LAUNCH_PLANS[config]
+    assert plan_prefix == want_prefix
+    assert plan_search == want_search
+    if config == "e":
+        assert not any(k.startswith("gemm_x3r") or k.startswith("gemm_ln_x3r") for k in list(plan_prefix) + list(plan_search))
+    assert float((pred.cpu() - pred_ref).abs().max()) <= 5e-5
+    assert hyps == hyps_ref
+    assert float((sc.cpu() - sc_ref).abs().max()) <= 1e-4
+
+
+def test_search_entries_take_exactly_their_workspace(backend, monkeypatch):
+    """Every search entry lays its workspace out once (csrc/search.hip, the *Layout structs): the same carve gives
+    sbk_X_workspace_bytes and the entry's pointers.  For each entry -- decoder_prefix, lm_prefix, greedy_search,
+    prompted_greedy_search, beam_search with CTC and beam_search with CTC and an LM -- at one tiny shape: a workspace of
+    exactly sbk_X_workspace_bytes succeeds; 256 bytes (one carving granule) less fails with the entry's "workspace too small"."""
+    nat, dev = backend
+    from speechbrain_amd.decoders import (CTCScorer, S2STransformerBeamSearcher, ScorerBuilder, TransformerLMScorer)
+
+    from speechbrain_amd.inference.builders import build_modules
+
+    g = np.load(os.path.join(GOLD, "model_tiny_lm_ctc.npz"))
+    d_model, nhead, d_ffn, n_enc, n_dec, vocab, beam, _ = [int(v) for v in g["cfg"]]
+    m = build_modules(dict(d_model=d_model, nhead=nhead, d_ffn=d_ffn, n_enc=n_enc, n_dec=n_dec, n_fft=512, win_length=32), vocab=vocab)
+    mods = torch.nn.ModuleDict({k: m[k] for k in ("CNN", "Transformer", "seq_lin", "ctc_lin")})
+    mods.load_state_dict({k[3:]: torch.from_numpy(g[k]) for k in g.files if k.startswith("sd/") and not k.startswith("sd/LM.")}, strict=True)
+    mods = mods.to(dev).eval()
+    lm = build_lm(g, dev)
+    enc = torch.from_numpy(g["enc_out"]).to(dev)[:2, :9].contiguous()
+    enc_len = torch.tensor([9, 6], dtype=torch.int32, device=dev)
+    wl = torch.tensor([1.0, 0.7], device=dev)
+    tok = torch.tensor([[1, 5, 7], [1, 4, 3]], dtype=torch.int32, device=dev)
+    h = nat.DecoderHandle(mods["Transformer"], mods["seq_lin"])
+    lmh = nat.LMHandle(lm)
+
+    def searcher(with_lm):
+        full, weights = [CTCScorer(ctc_fc=mods["ctc_lin"], blank_index=0, eos_index=2)], {"ctc": 0.4}
+        if with_lm:
+            full, weights = [TransformerLMScorer(language_model=lm, temperature=1.0)] + full, dict(weights, transformerlm=0.3)
+        return S2STransformerBeamSearcher(modules=[mods["Transformer"], mods["seq_lin"]], bos_index=1, eos_index=2,
+                                          min_decode_ratio=0.0, max_decode_ratio=0.34, beam_size=2, using_eos_threshold=False,
+                                          length_normalization=True, scorer=ScorerBuilder(full_scorers=full, weights=weights))
+
+    bs_ctc, bs_lm = searcher(False), searcher(True)
+    entries = [
+        ("sbk_decoder_prefix_workspace_bytes", "decoder_prefix: workspace too small", lambda: nat.decoder_prefix(h, tok, enc, enc_len)),
+        ("sbk_lm_prefix_workspace_bytes", "lm_prefix: workspace too small", lambda: nat.lm_prefix(lmh, tok)),
+        ("sbk_greedy_search_workspace_bytes", "greedy: workspace too small", lambda: nat.greedy_search(h, enc, enc_len, 0, 3, 1, 2)),
+        ("sbk_prompted_greedy_search_workspace_bytes", "prompted_greedy_search: workspace too small",
+         lambda: nat.prompted_greedy_search(h, enc, enc_len, tok[:, :2].contiguous(), 2, 2)),
+        ("sbk_beam_search_workspace_bytes", "beam_search: workspace too small", lambda: bs_ctc(enc, wl)),
+        ("sbk_beam_search_workspace_bytes", "beam_search: workspace too small", lambda: bs_lm(enc, wl)),
+    ]
+    lib = nat.load()
+    with torch.no_grad():
+        for sizer, message, call in entries:
+            real = getattr(lib, sizer)
+            asked = []
+
+            def exact(*a, _real=real):
+                asked.append(_real(*a))
+                return asked[-1]
+
+            monkeypatch.setattr(lib, sizer, exact, raising=False)
+            call()  # the binding hands the entry exactly what the sizer returned
+            assert asked and asked[-1] > 256 and asked[-1] % 256 == 0, (sizer, asked)
+            monkeypatch.setattr(lib, sizer, lambda *a, _real=real: _real(*a) - 256, raising=False)
+            with pytest.raises(nat.SbkError, match=message):
+                call()
+            monkeypatch.setattr(lib, sizer, real, raising=False)
+
+
 def build_lm(g, dev):
     from speechbrain_amd.lobes.models.transformer.TransformerLM import TransformerLM
 
