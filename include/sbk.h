@@ -515,6 +515,48 @@ int sbk_transducer_beam_search_f32(const sbk_transducer_weights* W, const sbk_tr
                                    float* out_score, int32_t* out_count, int32_t* out_status, int B, int T,
                                    sbk_stream_t stream);
 
+/* ---- transducer beam search with RNNLM shallow fusion (csrc/transducer.hip; additive entries, ABI 11 unchanged) -----------
+ * The same search with lm_module = speechbrain.lobes.models.RNNLM.RNNLM and lm_weight > 0 (decoders/transducer.py:413-453,
+ * 492-515; DESIGN.md section 5, "Transducer beam search with an RNNLM").  A hypothesis also carries the LM's (h, c); it moves
+ * exactly with the PN state.  At every expansion the LM takes the PN's input token and that state: the folded embedding row,
+ * the LSTM layers, n_dnn blocks of [Linear + bias, LayerNorm (eps from the struct), activation], the output Linear, and a
+ * log-softmax over the LM's WHOLE output (vocab entries).  The LM changes neither the top-k, nor best_logp, nor the
+ * expand_beam threshold; a non-blank candidate that passes the threshold gets
+ *     (score + logp) + (lm_weight * lm_logp[token])     -- two fp32 roundings, never an fma
+ * and the new LM state; a blank candidate keeps the old PN and LM state and gets no LM term.  A (token, state) pair expanded
+ * again at a later frame reads the LM's log-probabilities its first step left in the workspace.
+ *   emb_ih   [n_emb, 4H]  the LM's Embedding folded into layer 0's input weights (as sbk_transducer_weights.emb_ih)
+ *   w_ih[l]  [4H, H] for l >= 1;  w_hh[l] [4H, H];  b_ih[l], b_hh[l] [4H] (NULL = none)        H = hidden
+ *   dnn_w[i] [dnn, H] for block 0, [dnn, dnn] after;  dnn_b[i] [dnn] or NULL;  ln_g[i], ln_b[i] [dnn];  ln_eps[i]
+ *   out      [vocab, dnn];  out_b [vocab] or NULL;  act: SBK_ACT_LEAKY_RELU, SBK_ACT_RELU, SBK_ACT_GELU or SBK_ACT_TANH
+ * vocab >= W->vocab and n_emb >= W->vocab (token ids are shared with the classifier; further LM outputs only enter the
+ * log-softmax).  The LM's state and vectors share the 160 KiB of LDS with the search's: a size that does not fit is refused
+ * with a message that says LDS.  Workspace: as above plus, per slot, the LM's h / c and [W->vocab] log-probabilities; its head
+ * holds [B] int32 expansions, then [B] int32 LM steps taken (diagnostics).  Outputs, status bits and max_expansions: as
+ * sbk_transducer_beam_search_f32.  lm_weight must be finite and > 0 (without an LM term use that entry). */
+#define SBK_RNNLM_MAX_DNN 2
+typedef struct sbk_rnnlm_weights {
+  const float* emb_ih;
+  const float* w_ih[SBK_TRANSDUCER_MAX_LAYERS];
+  const float* w_hh[SBK_TRANSDUCER_MAX_LAYERS];
+  const float* b_ih[SBK_TRANSDUCER_MAX_LAYERS];
+  const float* b_hh[SBK_TRANSDUCER_MAX_LAYERS];
+  const float* dnn_w[SBK_RNNLM_MAX_DNN];
+  const float* dnn_b[SBK_RNNLM_MAX_DNN];
+  const float* ln_g[SBK_RNNLM_MAX_DNN];
+  const float* ln_b[SBK_RNNLM_MAX_DNN];
+  float ln_eps[SBK_RNNLM_MAX_DNN];
+  const float* out;
+  const float* out_b;
+  int32_t n_layers, hidden, n_dnn, dnn, vocab, n_emb, act;
+} sbk_rnnlm_weights;
+size_t sbk_transducer_beam_lm_workspace_bytes(const sbk_transducer_weights* W, const sbk_rnnlm_weights* LM,
+                                              const sbk_transducer_beam_config* cfg, int B, int T);
+int sbk_transducer_beam_search_lm_f32(const sbk_transducer_weights* W, const sbk_rnnlm_weights* LM, float lm_weight,
+                                      const sbk_transducer_beam_config* cfg, const float* tn, void* workspace,
+                                      size_t workspace_bytes, int32_t* out_tokens, int32_t* out_len, float* out_score,
+                                      int32_t* out_count, int32_t* out_status, int B, int T, sbk_stream_t stream);
+
 /* log_softmax(x / temperature) * weight over the last dimension, x [rows,V] (seq2seq.py:1933). */
 int sbk_log_softmax_f32(const float* x, float* out, int rows, int V, float temperature, float weight,
                         sbk_stream_t stream);

@@ -2,7 +2,8 @@
 // for the prediction network [Embedding, LSTM, Linear], Transducer_joint(joint="sum") and one classifier Linear.  One
 // workgroup per utterance runs every frame in ONE launch with the utterance's PN state in LDS; the weights stream from L2.
 // The semantics reproduced here are listed in DESIGN.md section 5 ("Transducer greedy decoding").  Further down: the beam
-// search of the same class (transducer_beam_search_decode, decoders/transducer.py:320-476) on the same step code.
+// search of the same class (transducer_beam_search_decode, decoders/transducer.py:320-476) on the same step code, without an LM
+// and with an RNNLM (lobes/models/RNNLM.py) fused into the scores.
 #include <math.h>
 #include <string.h>
 
@@ -161,6 +162,61 @@ __device__ __forceinline__ void log_softmax_stats(const float* x, int V, float& 
   ls = logf(se);
 }
 
+// block i's pointer from a per-block array of the RNNLM's struct (the same reason as layer_ptr)
+__device__ __forceinline__ const float* dnn_ptr(const float* const (&p)[SBK_RNNLM_MAX_DNN], int i) {
+  static_assert(SBK_RNNLM_MAX_DNN == 2, "dnn_ptr covers two blocks");
+  return i == 0 ? p[0] : p[1];
+}
+
+// One RNNLM step on token `tok` (lobes/models/RNNLM.py forward at inference): the folded embedding row, every LSTM layer on
+// s_h / s_c, the DNN blocks [Linear + bias, LayerNorm (two-pass mean / variance), activation] through s_d0 / s_d1, and the
+// output Linear into s_out [vocab].  s_g / s_gh hold 4 * hidden floats each; s_stat two.  The products are pn_step's (8 rows
+// per wave; with 16 the kernel spilled three times as much to scratch).  Ends with a barrier.
+__device__ void lm_step(const sbk_rnnlm_weights& M, int tok, float* s_h, float* s_c, float* s_g, float* s_gh, float* s_d0,
+                        float* s_d1, float* s_out, float* s_stat) {
+  const int H = M.hidden, G = 4 * H, D = M.dnn, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int l = 0; l < M.n_layers; ++l) {
+    float* hl = s_h + (size_t)l * H;
+    float* cl = s_c + (size_t)l * H;
+    if (l == 0) {
+      const float* row = M.emb_ih + (size_t)tok * G;
+      for (int n = tid; n < G; n += kTdThreads) s_g[n] = M.b_ih[0] ? row[n] + M.b_ih[0][n] : row[n];
+    } else {
+      gemv_rows<1, 8>(layer_ptr(M.w_ih, l), layer_ptr(M.b_ih, l), s_h + (size_t)(l - 1) * H, H, 1, H, G, s_g, G);
+    }
+    gemv_rows<1, 8>(layer_ptr(M.w_hh, l), layer_ptr(M.b_hh, l), hl, H, 1, H, G, s_gh, G);
+    __syncthreads();
+    lstm_update(s_g, s_gh, hl, cl, H);
+    __syncthreads();
+  }
+  const float* x = s_h + (size_t)(M.n_layers - 1) * H;
+  int K = H;
+  for (int i = 0; i < M.n_dnn; ++i) {
+    float* y = i == 0 ? s_d0 : s_d1;
+    gemv_rows<1, 8>(dnn_ptr(M.dnn_w, i), dnn_ptr(M.dnn_b, i), x, K, 1, K, D, y, D);
+    __syncthreads();
+    if (wave == 0) {
+      float s = 0.0f;
+      for (int k = lane; k < D; k += 64) s += y[k];
+      for (int m = 32; m >= 1; m >>= 1) s += shfl_xor(s, m);
+      const float mean = s / (float)D;
+      float q = 0.0f;
+      for (int k = lane; k < D; k += 64) q += (y[k] - mean) * (y[k] - mean);
+      for (int m = 32; m >= 1; m >>= 1) q += shfl_xor(q, m);
+      if (lane == 0) s_stat[0] = mean, s_stat[1] = 1.0f / sqrtf(q / (float)D + (i == 0 ? M.ln_eps[0] : M.ln_eps[1]));
+    }
+    __syncthreads();
+    const float mean = s_stat[0], rstd = s_stat[1];
+    const float* g = dnn_ptr(M.ln_g, i);
+    const float* be = dnn_ptr(M.ln_b, i);
+    for (int k = tid; k < D; k += kTdThreads) y[k] = joint_act((y[k] - mean) * rstd * g[k] + be[k], M.act);
+    __syncthreads();
+    x = y, K = D;
+  }
+  gemv_rows<1, 8>(M.out, M.out_b, x, K, 1, K, M.vocab, s_out, M.vocab);
+  __syncthreads();
+}
+
 __global__ __launch_bounds__(kTdThreads) void transducer_greedy_kernel(TdArgs a) {
   SBK_DYN_LDS(float, lds);
   const sbk_transducer_weights& W = a.W;
@@ -312,6 +368,12 @@ struct TbArgs {
   int32_t* out_status;  // [B]
   int beam, nbest, max_exp, max_tokens, cap_a, n_slots, slot_floats, node_cap;
   float state_beam, expand_beam;
+  // LM fusion (read by the LM instantiation only): a slot then also holds the LM's h / c [LM.n_layers * LM.hidden] each after
+  // the step and its log-probabilities over the classifier's V tokens
+  sbk_rnnlm_weights lm;
+  float lm_weight;
+  int gmax;            // floats of each gate buffer: 4 * max(PN hidden, LM hidden)
+  int32_t* lm_steps;   // [B]
 };
 
 // The sort key logp_score / len(prediction): an fp32 division.  (A NaN key ranks below everything, so that a search over
@@ -339,26 +401,38 @@ __device__ __forceinline__ int tb_best(const TbHyp* list, int n) {
   return bi;
 }
 
+// LM: shallow fusion with an RNNLM (rules 8-10 of that section); the instantiation without it is the search as it was.
+template <bool LM>
 __global__ __launch_bounds__(kTdThreads) void transducer_beam_kernel(TbArgs a) {
   SBK_DYN_LDS(float, lds);
   const sbk_transducer_weights& W = a.g.W;
   const int H = W.hidden, G = 4 * H, J = W.joint, V = W.vocab, L = W.n_layers, LH = L * H;
+  const int GM = LM ? a.gmax : G;                            // the gate buffers serve pn_step and lm_step
+  const int LLH = LM ? a.lm.n_layers * a.lm.hidden : 0;      // the LM's h (and c) of one state
   float* s_z = lds;             // [J] joint activations
   float* s_logit = s_z + J;     // [V]
   float* s_pn = s_logit + V;    // [J]
   float* s_h = s_pn + J;        // [L][H]
   float* s_c = s_h + LH;        // [L][H]
-  float* s_g = s_c + LH;        // [G]
-  float* s_gh = s_g + G;        // [G]
-  float* s_topv = s_gh + G;     // [beam] the top-k log-probabilities of an expansion ...
+  float* s_g = s_c + LH;        // [GM]
+  float* s_gh = s_g + GM;       // [GM]
+  float* s_lh = s_gh + GM;      // LM only: [LM layers][LM hidden]
+  float* s_lc = s_lh + LLH;     //          the same
+  float* s_d0 = s_lc + LLH;     //          [dnn], [dnn]: the DNN blocks' outputs
+  float* s_d1 = s_d0 + (LM ? a.lm.dnn : 0);
+  float* s_lout = s_d1 + (LM ? a.lm.dnn : 0);       //   [LM vocab] the LM's logits
+  float* s_topv = s_lout + (LM ? a.lm.vocab : 0);   // [beam] the top-k log-probabilities of an expansion ...
   int* s_topi = reinterpret_cast<int*>(s_topv + a.beam);  // [beam] ... and their tokens
-  int* s_used = s_topi + a.beam;                          // [n_slots] slot is referenced by a hypothesis of this frame
+  float* s_toplm = reinterpret_cast<float*>(s_topi + a.beam);  // LM only: [beam] the LM's log-probabilities of those tokens
+  int* s_used = reinterpret_cast<int*>(s_toplm + (LM ? a.beam : 0));  // [n_slots] slot is referenced by a hypothesis of this frame
   TbHyp* A = reinterpret_cast<TbHyp*>(s_used + a.n_slots);  // [cap_a]
   TbHyp* Bl = A + a.cap_a;                                  // [beam]
-  __shared__ int s_na, s_nb, s_act, s_slot, s_status, s_nodes, s_stamp, s_total;
+  __shared__ int s_na, s_nb, s_act, s_slot, s_status, s_nodes, s_stamp, s_total, s_lmn;
   __shared__ TbHyp s_cur;
+  __shared__ float s_stat[2];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int blank = a.g.blank;
+  const int o_lh = J + 2 * LH, o_lc = o_lh + LLH, o_lp = o_lc + LLH;  // a slot's LM part: h, c, log-probabilities [V]
   const float* tnb = a.g.tn + (size_t)b * a.g.T * J;
   int2* nodes = a.nodes + (size_t)b * a.node_cap;
   float* slots = a.slots + (size_t)b * a.n_slots * a.slot_floats;
@@ -366,7 +440,7 @@ __global__ __launch_bounds__(kTdThreads) void transducer_beam_kernel(TbArgs a) {
   if (tid == 0) {
     nodes[0] = make_int2(-1, blank);
     A[0] = TbHyp{0, blank, 0.0f, 1, -1, -1, 0};
-    s_na = 1, s_nb = 0, s_status = 0, s_nodes = 1, s_stamp = 1, s_total = 0;
+    s_na = 1, s_nb = 0, s_status = 0, s_nodes = 1, s_stamp = 1, s_total = 0, s_lmn = 0;
   }
   __syncthreads();
 
@@ -431,13 +505,31 @@ __global__ __launch_bounds__(kTdThreads) void transducer_beam_kernel(TbArgs a) {
         if (cur.state >= 0) {
           const float* src = slots + (size_t)cur.state * a.slot_floats + J;
           for (int i = tid; i < LH; i += kTdThreads) s_h[i] = src[i], s_c[i] = src[LH + i];
+          if constexpr (LM) {
+            const float* lsrc = slots + (size_t)cur.state * a.slot_floats;
+            for (int i = tid; i < LLH; i += kTdThreads) s_lh[i] = lsrc[o_lh + i], s_lc[i] = lsrc[o_lc + i];
+          }
         } else {
           for (int i = tid; i < LH; i += kTdThreads) s_h[i] = 0.0f, s_c[i] = 0.0f;
+          if constexpr (LM)
+            for (int i = tid; i < LLH; i += kTdThreads) s_lh[i] = 0.0f, s_lc[i] = 0.0f;
         }
         __syncthreads();
         pn_step(a.g, cur.tok, s_pn, s_h, s_c, s_g, s_gh);
         for (int j = tid; j < J; j += kTdThreads) sl[j] = s_pn[j];
         for (int i = tid; i < LH; i += kTdThreads) sl[J + i] = s_h[i], sl[J + LH + i] = s_c[i];
+        if constexpr (LM) {
+          // the LM moves with the PN: the same input token, the same slot; its log-softmax runs over its whole output
+          lm_step(a.lm, cur.tok, s_lh, s_lc, s_g, s_gh, s_d0, s_d1, s_lout, s_stat);
+          for (int i = tid; i < LLH; i += kTdThreads) sl[o_lh + i] = s_lh[i], sl[o_lc + i] = s_lc[i];
+          if (wave == 0) {
+            float m, ls;
+            log_softmax_stats(s_lout, a.lm.vocab, m, ls);
+            for (int v = lane; v < V; v += 64) sl[o_lp + v] = (s_lout[v] - m) - ls;
+            if (lane == 0) s_lmn = s_lmn + 1;
+          }
+          __syncthreads();
+        }
       }
       // ---- the joint with tn[b, t], the classifier, log-softmax and top-k
       const float* tnf = tnb + (size_t)t * J;
@@ -466,6 +558,14 @@ __global__ __launch_bounds__(kTdThreads) void transducer_beam_kernel(TbArgs a) {
           pv = bv, pi = bi;
           if (lane == 0) s_topv[r] = bv, s_topi[r] = bi;
         }
+        if constexpr (LM) {  // the LM's log-probabilities of the picks, from the slot (this step's or the cached one's)
+          wave_sync();
+          for (int r = lane; r < a.beam; r += 64) {
+            const int ti = s_topi[r];
+            s_toplm[r] = (unsigned)ti < (unsigned)V ? sl[o_lp + ti] : 0.0f;
+          }
+          wave_sync();
+        }
         // ---- the candidates in top-k order: blank joins B with the old state, the others join A with the new one
         if (lane == 0) {
           const float best = s_topi[0] != blank ? s_topv[0] : s_topv[1];
@@ -478,7 +578,9 @@ __global__ __launch_bounds__(kTdThreads) void transducer_beam_kernel(TbArgs a) {
               if (nb < a.beam) Bl[nb++] = TbHyp{cur.node, cur.tok, cur.score + lp, cur.len, cur.state, slot, st++};
             } else if (lp >= thr && na < a.cap_a && nn < a.node_cap) {
               nodes[nn] = make_int2(cur.node, tok);
-              A[na++] = TbHyp{nn++, tok, cur.score + lp, cur.len + 1, slot, -1, st++};
+              float sc = cur.score + lp;
+              if constexpr (LM) sc = add_rn(sc, mul_rn(a.lm_weight, s_toplm[j]));  // (product rounded, then added: no fma)
+              A[na++] = TbHyp{nn++, tok, sc, cur.len + 1, slot, -1, st++};
             }
           }
           s_na = na, s_nb = nb, s_nodes = nn, s_stamp = st, s_total = s_total + 1;
@@ -542,6 +644,7 @@ __global__ __launch_bounds__(kTdThreads) void transducer_beam_kernel(TbArgs a) {
     for (int r = 0; r < count; ++r)
       if (A[r].len - 1 > a.max_tokens) status |= SBK_TBEAM_TRUNCATED;
     a.out_count[b] = count, a.out_status[b] = status, a.expansions[b] = s_total;
+    if constexpr (LM) a.lm_steps[b] = s_lmn;
   }
 }
 
@@ -606,23 +709,28 @@ constexpr size_t kTbStaticLds = 256;  // the beam kernel's counters and s_cur
 
 struct TbSizes {
   long long cap_a, n_slots, slot_floats, node_cap;
-  size_t lds, head_bytes, node_bytes, slot_bytes, total;
+  size_t lds, gmax, head_bytes, node_bytes, slot_bytes, total;
 };
 
-// The sizes of one beam search; `why` names the limit a refused size breaks.
-bool tb_sizes(const sbk_transducer_weights& W, const sbk_transducer_beam_config& c, int B, int T, TbSizes& z, const char** why) {
+// The sizes of one beam search (M: the RNNLM of a search with LM fusion, or NULL); `why` names the limit a refused size breaks.
+bool tb_sizes(const sbk_transducer_weights& W, const sbk_rnnlm_weights* M, const sbk_transducer_beam_config& c, int B, int T,
+              TbSizes& z, const char** why) {
   const long long beam = c.beam_size, me = c.max_expansions;
   z.cap_a = beam + me * beam;   // the previous B plus at most beam children per expansion
   z.n_slots = 2 * beam + me;    // the states and cached steps B carries in, plus one new state per expansion
-  z.slot_floats = ((long long)W.joint + 2LL * W.n_layers * W.hidden + 3) / 4 * 4;
+  const long long lm_state = M ? 2LL * M->n_layers * M->hidden : 0;  // with an LM a slot also holds its h / c and [V] log-probs
+  z.slot_floats = ((long long)W.joint + 2LL * W.n_layers * W.hidden + lm_state + (M ? W.vocab : 0) + 3) / 4 * 4;
   z.node_cap = 1 + (long long)T * me * beam;
   *why = "max_expansions * beam_size * T too large";
   if (z.node_cap >= (1LL << 31) || z.cap_a >= (1LL << 24)) return false;
-  z.lds = sizeof(float) * (2 * (size_t)W.joint + W.vocab + 2 * (size_t)W.n_layers * W.hidden + 8 * (size_t)W.hidden) +
+  z.gmax = 4 * (size_t)(M && M->hidden > W.hidden ? M->hidden : W.hidden);  // the gate buffers are shared by the PN and the LM
+  const size_t lm_floats = M ? (size_t)lm_state + 2 * (size_t)M->dnn + (size_t)M->vocab + (size_t)beam : 0;
+  z.lds = sizeof(float) * (2 * (size_t)W.joint + W.vocab + 2 * (size_t)W.n_layers * W.hidden + 2 * z.gmax + lm_floats) +
           sizeof(int) * (2 * (size_t)beam + (size_t)z.n_slots) + sizeof(TbHyp) * (size_t)(z.cap_a + beam);
-  *why = "the hypothesis lists (beam_size * max_expansions) and the network's vectors do not fit in LDS";
+  *why = M ? "the hypothesis lists (beam_size * max_expansions), the network's and the LM's vectors do not fit in LDS"
+           : "the hypothesis lists (beam_size * max_expansions) and the network's vectors do not fit in LDS";
   if (z.lds > kTdLdsMax - kTbStaticLds) return false;
-  z.head_bytes = ((size_t)B * sizeof(int32_t) + 15) / 16 * 16;
+  z.head_bytes = ((size_t)B * (M ? 2 : 1) * sizeof(int32_t) + 15) / 16 * 16;  // expansions [B], with an LM also LM steps [B]
   z.node_bytes = (size_t)B * (size_t)z.node_cap * sizeof(int2);
   z.slot_bytes = (size_t)B * (size_t)z.n_slots * (size_t)z.slot_floats * sizeof(float);
   z.total = z.head_bytes + z.node_bytes + z.slot_bytes;
@@ -658,6 +766,30 @@ int tb_check(const sbk_transducer_weights* W, const sbk_transducer_beam_config* 
   return 0;
 }
 
+int tb_lm_check(const sbk_transducer_weights* W, const sbk_rnnlm_weights* M, float lm_weight) {
+  SBK_REQUIRE(M, "transducer_beam_search_lm: the LM's weights are NULL");
+  SBK_REQUIRE(isfinite(lm_weight) && lm_weight > 0.0f, "transducer_beam_search_lm: lm_weight %g is not a finite value > 0",
+              (double)lm_weight);
+  SBK_REQUIRE(M->n_layers >= 1 && M->n_layers <= SBK_TRANSDUCER_MAX_LAYERS,
+              "transducer_beam_search_lm: %d LSTM layers in the LM (1..%d supported)", M->n_layers, SBK_TRANSDUCER_MAX_LAYERS);
+  SBK_REQUIRE(M->n_dnn >= 1 && M->n_dnn <= SBK_RNNLM_MAX_DNN, "transducer_beam_search_lm: n_dnn %d DNN blocks in the LM (1..%d supported)",
+              M->n_dnn, SBK_RNNLM_MAX_DNN);
+  SBK_REQUIRE(M->hidden > 0 && M->dnn > 0 && M->vocab > 0 && M->hidden < (1 << 24) && M->dnn < (1 << 24) && M->vocab < (1 << 24),
+              "transducer_beam_search_lm: bad LM sizes (hidden=%d dnn=%d vocab=%d)", M->hidden, M->dnn, M->vocab);
+  SBK_REQUIRE(M->vocab >= W->vocab && M->n_emb >= W->vocab,
+              "transducer_beam_search_lm: the LM's vocab %d (n_emb %d) is below the classifier's %d outputs", M->vocab, M->n_emb,
+              W->vocab);
+  SBK_REQUIRE(M->emb_ih && M->out, "transducer_beam_search_lm: the LM's emb_ih and out are required");
+  for (int l = 0; l < M->n_layers; ++l)
+    SBK_REQUIRE(M->w_hh[l] && (l == 0 || M->w_ih[l]), "transducer_beam_search_lm: weights of the LM's LSTM layer %d missing", l);
+  for (int i = 0; i < M->n_dnn; ++i)
+    SBK_REQUIRE(M->dnn_w[i] && M->ln_g[i] && M->ln_b[i] && M->ln_eps[i] >= 0.0f,
+                "transducer_beam_search_lm: weights of the LM's DNN block %d missing (w, ln_g, ln_b; ln_eps >= 0)", i);
+  SBK_REQUIRE(M->act == SBK_ACT_GELU || M->act == SBK_ACT_LEAKY_RELU || M->act == SBK_ACT_RELU || M->act == SBK_ACT_TANH,
+              "transducer_beam_search_lm: the LM's activation %d is not supported", M->act);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" size_t sbk_transducer_beam_workspace_bytes(const sbk_transducer_weights* W, const sbk_transducer_beam_config* cfg,
@@ -666,7 +798,7 @@ extern "C" size_t sbk_transducer_beam_workspace_bytes(const sbk_transducer_weigh
   const char* why;
   if (B == 0) return 0;
   if (tb_check(W, cfg, B, T) != 0) return 0;
-  if (!tb_sizes(*W, *cfg, B, T, z, &why)) {
+  if (!tb_sizes(*W, nullptr, *cfg, B, T, z, &why)) {
     fail(SBK_EINVAL, "transducer_beam_search: %s (beam_size=%d max_expansions=%d T=%d)", why, cfg->beam_size,
          cfg->max_expansions, T);
     return 0;
@@ -684,7 +816,7 @@ extern "C" int sbk_transducer_beam_search_f32(const sbk_transducer_weights* W, c
               "transducer_beam_search: a NULL pointer among tn, workspace and the outputs");
   TbSizes z;
   const char* why;
-  SBK_REQUIRE(tb_sizes(*W, *cfg, B, T, z, &why), "transducer_beam_search: %s (beam_size=%d max_expansions=%d T=%d)", why,
+  SBK_REQUIRE(tb_sizes(*W, nullptr, *cfg, B, T, z, &why), "transducer_beam_search: %s (beam_size=%d max_expansions=%d T=%d)", why,
               cfg->beam_size, cfg->max_expansions, T);
   SBK_REQUIRE(aligned16(workspace), "transducer_beam_search: the workspace is not 16-byte aligned");
   SBK_REQUIRE(workspace_bytes >= z.total, "transducer_beam_search: workspace of %zu bytes, %zu needed", workspace_bytes, z.total);
@@ -701,11 +833,64 @@ extern "C" int sbk_transducer_beam_search_f32(const sbk_transducer_weights* W, c
   a.cap_a = (int)z.cap_a, a.n_slots = (int)z.n_slots, a.slot_floats = (int)z.slot_floats, a.node_cap = (int)z.node_cap;
   a.state_beam = cfg->state_beam, a.expand_beam = cfg->expand_beam;
   hipStream_t st = as_stream(stream);
-  if (z.lds > 64 * 1024 && (int)SBK_ALLOW_DYN_LDS(transducer_beam_kernel, z.lds) != 0)
+  if (z.lds > 64 * 1024 && (int)SBK_ALLOW_DYN_LDS(transducer_beam_kernel<false>, z.lds) != 0)
     return fail(SBK_EINVAL, "transducer_beam_search: %zu bytes of LDS not available", z.lds);
   ProfScope prof("transducer_beam", 0.0, 4.0 * B * T * W->joint + 4.0 * (double)W->joint * W->vocab * B * T, st);
-  SBK_LAUNCH(transducer_beam_kernel, dim3(B), dim3(kTdThreads), z.lds, st, a);
+  SBK_LAUNCH(transducer_beam_kernel<false>, dim3(B), dim3(kTdThreads), z.lds, st, a);
   return launch_status("transducer_beam_search");
+}
+
+extern "C" size_t sbk_transducer_beam_lm_workspace_bytes(const sbk_transducer_weights* W, const sbk_rnnlm_weights* LM,
+                                                         const sbk_transducer_beam_config* cfg, int B, int T) {
+  TbSizes z;
+  const char* why;
+  if (B == 0) return 0;
+  if (tb_check(W, cfg, B, T) != 0) return 0;
+  if (tb_lm_check(W, LM, 1.0f) != 0) return 0;
+  if (!tb_sizes(*W, LM, *cfg, B, T, z, &why)) {
+    fail(SBK_EINVAL, "transducer_beam_search_lm: %s (beam_size=%d max_expansions=%d T=%d LM hidden=%d)", why, cfg->beam_size,
+         cfg->max_expansions, T, LM->hidden);
+    return 0;
+  }
+  return z.total;
+}
+
+extern "C" int sbk_transducer_beam_search_lm_f32(const sbk_transducer_weights* W, const sbk_rnnlm_weights* LM, float lm_weight,
+                                                 const sbk_transducer_beam_config* cfg, const float* tn, void* workspace,
+                                                 size_t workspace_bytes, int32_t* out_tokens, int32_t* out_len,
+                                                 float* out_score, int32_t* out_count, int32_t* out_status, int B, int T,
+                                                 sbk_stream_t stream) {
+  if (B == 0) return 0;
+  if (const int rc = tb_check(W, cfg, B, T)) return rc;
+  if (const int rc = tb_lm_check(W, LM, lm_weight)) return rc;
+  SBK_REQUIRE(tn && workspace && out_tokens && out_len && out_score && out_count && out_status,
+              "transducer_beam_search_lm: a NULL pointer among tn, workspace and the outputs");
+  TbSizes z;
+  const char* why;
+  SBK_REQUIRE(tb_sizes(*W, LM, *cfg, B, T, z, &why), "transducer_beam_search_lm: %s (beam_size=%d max_expansions=%d T=%d LM hidden=%d)",
+              why, cfg->beam_size, cfg->max_expansions, T, LM->hidden);
+  SBK_REQUIRE(aligned16(workspace), "transducer_beam_search_lm: the workspace is not 16-byte aligned");
+  SBK_REQUIRE(workspace_bytes >= z.total, "transducer_beam_search_lm: workspace of %zu bytes, %zu needed", workspace_bytes, z.total);
+  TbArgs a;
+  memset(&a, 0, sizeof(a));
+  a.g.W = *W;
+  a.g.tn = tn, a.g.B = B, a.g.T = T, a.g.blank = cfg->blank, a.g.act = cfg->act;
+  char* ws = static_cast<char*>(workspace);
+  a.expansions = reinterpret_cast<int32_t*>(ws);
+  a.lm_steps = a.expansions + B;
+  a.nodes = reinterpret_cast<int2*>(ws + z.head_bytes);
+  a.slots = reinterpret_cast<float*>(ws + z.head_bytes + z.node_bytes);
+  a.out_tokens = out_tokens, a.out_len = out_len, a.out_score = out_score, a.out_count = out_count, a.out_status = out_status;
+  a.beam = cfg->beam_size, a.nbest = cfg->nbest, a.max_exp = cfg->max_expansions, a.max_tokens = cfg->max_tokens;
+  a.cap_a = (int)z.cap_a, a.n_slots = (int)z.n_slots, a.slot_floats = (int)z.slot_floats, a.node_cap = (int)z.node_cap;
+  a.state_beam = cfg->state_beam, a.expand_beam = cfg->expand_beam;
+  a.lm = *LM, a.lm_weight = lm_weight, a.gmax = (int)z.gmax;
+  hipStream_t st = as_stream(stream);
+  if (z.lds > 64 * 1024 && (int)SBK_ALLOW_DYN_LDS(transducer_beam_kernel<true>, z.lds) != 0)
+    return fail(SBK_EINVAL, "transducer_beam_search_lm: %zu bytes of LDS not available", z.lds);
+  ProfScope prof("transducer_beam_lm", 0.0, 4.0 * B * T * W->joint + 4.0 * (double)W->joint * W->vocab * B * T, st);
+  SBK_LAUNCH(transducer_beam_kernel<true>, dim3(B), dim3(kTdThreads), z.lds, st, a);
+  return launch_status("transducer_beam_search_lm");
 }
 
 extern "C" int sbk_lstm_f32(const float* xp, const float* w_hh, const float* b_ih, const float* b_hh, float* h, float* c,

@@ -5,8 +5,10 @@ The whole search of a batch -- prediction network (PN) steps, joint, classifier,
 frame -- is ONE launch of sbk_transducer_greedy_f32 (``beam_size <= 1``) or sbk_transducer_beam_search_f32 (``beam_size >
 1``; csrc/transducer.hip), one workgroup per utterance.  Supported: the PN [Embedding (dense or one-hot), LSTM
 (unidirectional, 1..4 layers), Linear], Transducer_joint(joint="sum") with GELU, LeakyReLU, Tanh or ReLU, and one classifier
-Linear.  LM fusion and other PN layers raise NotImplementedError when the searcher is called; so does a beam above
-native.TRANSDUCER_MAX_BEAM.
+Linear.  The beam search fuses an LM (``lm_module`` with ``lm_weight > 0``) when it is a lobes.models.RNNLM.RNNLM with a 1..4
+layer unidirectional LSTM, 1..2 DNN blocks and LeakyReLU, ReLU, GELU or Tanh: sbk_transducer_beam_search_lm_f32, still one
+launch.  Any other LM, LM fusion in the greedy search and other PN layers raise NotImplementedError when the searcher is
+called; so does a beam above native.TRANSDUCER_MAX_BEAM.
 
 The reference's beam search has no bound on the expansions of a frame (it never leaves a frame whose blank stays out of the
 top ``beam_size``); here ``max_expansions`` (default ``4 * beam_size``) bounds them.  A search that reaches the bound ends,
@@ -52,6 +54,8 @@ class TransducerBeamSearcher(torch.nn.Module):
             self.searcher = self.transducer_beam_search_decode
         self._prepared = None
         self._prepared_key = None
+        self._lm_prepared = None
+        self._lm_prepared_key = None
 
     def forward(self, tn_output):
         return self.searcher(tn_output)
@@ -63,13 +67,17 @@ class TransducerBeamSearcher(torch.nn.Module):
         has none).  Utterances that reach it, or whose log-probabilities are not finite, are named in a warning and their
         result is unspecified.  ``return_status`` appends (status word, number of expansions) per utterance, as lists.  (No
         hypothesis is truncated: the kernel is given room for T * max_expansions tokens, which none can exceed.)"""
-        if self.lm is not None and self.lm_weight > 0:
-            raise NotImplementedError("transducer beam search with LM fusion is not implemented")
+        fuse = self.lm is not None and self.lm_weight > 0  # (with lm_weight <= 0 the reference never touches the LM)
+        if fuse:
+            self._lm_networks()  # (refuses what is not built before anything runs)
         if self.beam_size > native.TRANSDUCER_MAX_BEAM:
             raise NotImplementedError(f"transducer beam search with beam_size={self.beam_size} is not implemented "
                                       f"(at most {native.TRANSDUCER_MAX_BEAM})")
         tn = tn_output.detach().float().contiguous()
-        prep = self._prepare(tn.device)
+        prep = self._prepare(tn.device, beam=True)
+        lm = self._prepare_lm(tn.device) if fuse else None
+        if lm is not None and lm.M.vocab < prep.W.vocab:
+            raise ValueError(f"the LM has {lm.M.vocab} outputs, fewer than the {prep.W.vocab} of the classifier")
         if self.beam_size > prep.W.vocab:
             raise ValueError(f"beam_size={self.beam_size} is larger than the {prep.W.vocab} outputs of the classifier")
         if tn.shape[0] == 0:  # (the reference's mean over no utterances)
@@ -79,7 +87,7 @@ class TransducerBeamSearcher(torch.nn.Module):
             max_expansions = native.transducer_beam_max_expansions(self.beam_size)
         tokens, length, score, count, status, expansions = native.transducer_beam_search(
             prep, tn, self.blank_id, self.beam_size, self.nbest, state_beam=self.state_beam, expand_beam=self.expand_beam,
-            max_expansions=max_expansions, act=self.tjoint.act_code)
+            max_expansions=max_expansions, act=self.tjoint.act_code, lm=lm, lm_weight=float(self.lm_weight) if fuse else 0.0)
         length, counts, status = length.cpu(), count.cpu().tolist(), status.cpu().tolist()
         rows = tokens[:, :, :max(1, int(length.max()))].cpu().tolist()
         length, scores = length.tolist(), score.cpu().tolist()
@@ -98,12 +106,12 @@ class TransducerBeamSearcher(torch.nn.Module):
         return ret + ((status, expansions.cpu().tolist()),) if return_status else ret
 
     # ------------------------------------------------------------------ the network, in the kernel's layout
-    def _networks(self):
+    def _networks(self, beam=False):
         from speechbrain_amd.nnet.embedding import Embedding
         from speechbrain_amd.nnet.linear import Linear
         from speechbrain_amd.nnet.RNN import LSTM
 
-        if self.lm is not None and self.lm_weight > 0:
+        if self.lm is not None and self.lm_weight > 0 and not beam:
             raise NotImplementedError("transducer decoding with LM fusion is not implemented")
         layers = list(self.decode_network_lst)
         for layer in layers:
@@ -119,10 +127,51 @@ class TransducerBeamSearcher(torch.nn.Module):
                                       f"(got {[type(x).__name__ for x in cls]})")
         return layers[0], layers[1], layers[2], cls[0]
 
-    def _prepare(self, device):
+    _LM_ACTS = {"LeakyReLU": native.ACT_LEAKY_RELU, "ReLU": native.ACT_RELU, "GELU": native.ACT_GELU, "Tanh": native.ACT_TANH}
+
+    def _lm_networks(self):
+        """(embedding, LSTM, [(Linear, LayerNorm)] per DNN block, out Linear, activation code) of an LM the kernel fuses."""
+        from speechbrain_amd.lobes.models.RNNLM import RNNLM
+
+        lm = self.lm
+        refuse = lambda why: NotImplementedError(  # noqa: E731
+            f"transducer beam search with LM fusion is not implemented for {type(lm).__name__}{why} (an RNNLM with a 1..4 layer "
+            "unidirectional LSTM, 1..2 DNN blocks and LeakyReLU, ReLU, GELU or Tanh)")
+        if not isinstance(lm, RNNLM):
+            raise refuse("")
+        rnn = lm.rnn.rnn
+        if rnn.bidirectional or not 1 <= rnn.num_layers <= native.TRANSDUCER_MAX_LAYERS:
+            raise refuse(f" with {rnn.num_layers} {'bidirectional ' if rnn.bidirectional else ''}LSTM layers")
+        blocks = lm.blocks()
+        if not 1 <= len(blocks) <= native.RNNLM_MAX_DNN:
+            raise refuse(f" with {len(blocks)} DNN blocks")
+        acts = {type(b[2]) for b in blocks}
+        act = next(iter(acts))
+        if len(acts) != 1 or act not in (torch.nn.LeakyReLU, torch.nn.ReLU, torch.nn.GELU, torch.nn.Tanh):
+            raise refuse(f" with activation {sorted(a.__name__ for a in acts)}")
+        mod = blocks[0][2]
+        if (act is torch.nn.LeakyReLU and mod.negative_slope != 0.01) or (act is torch.nn.GELU and mod.approximate != "none"):
+            raise refuse(f" with {mod}")
+        return lm.embedding, lm.rnn, [(b[0], b[1]) for b in blocks], lm.out, self._LM_ACTS[act.__name__]
+
+    def _prepare_lm(self, device):
+        """The LM's weight layouts on ``device``, by the key rule of _prepare."""
+        emb, lstm, blocks, out, act = self._lm_networks()
+        params = [p for p in self.lm.parameters()]
+        key = (device, act) + tuple((p.data_ptr(), p._version, p.device) for p in params) + tuple(ln.eps for _, ln in blocks)
+        if self._lm_prepared is None or key != self._lm_prepared_key:
+            d = lambda t: None if t is None else t.detach().to(device)  # noqa: E731
+            layers = [tuple(d(t) for t in layer) for layer in lstm.layer_weights()]
+            dnn = [(d(lin.w.weight), d(lin.w.bias), d(ln.norm.weight), d(ln.norm.bias), ln.eps) for lin, ln in blocks]
+            self._lm_prepared = native.RNNLMPrepared(d(emb.Embedding.weight), layers, dnn, d(out.w.weight), d(out.w.bias), act)
+            self._lm_prepared_key = key
+        return self._lm_prepared
+
+    def _prepare(self, device, beam=False):
         """The kernel's weight layouts on ``device``, rebuilt when a parameter changes (the PN and classifier modules are
-        plain list members, as in the reference, so they are not moved with the searcher)."""
-        emb, lstm, proj, lin = self._networks()
+        plain list members, as in the reference, so they are not moved with the searcher).  ``beam``: called by the beam
+        search, which decodes with an LM; the greedy search refuses one."""
+        emb, lstm, proj, lin = self._networks(beam)
         params = [emb.Embedding.weight] + [p for p in lstm.parameters()] + [p for p in proj.parameters()] + [
             p for p in lin.parameters()]
         key = (device,) + tuple((p.data_ptr(), p._version, p.device) for p in params)

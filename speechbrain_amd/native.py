@@ -99,6 +99,16 @@ class TransducerBeamConfig(ctypes.Structure):  # sbk_transducer_beam_config
                 ("expand_beam", c_float), ("max_expansions", c_int32), ("max_tokens", c_int32), ("act", c_int32)]
 
 
+RNNLM_MAX_DNN = 2  # SBK_RNNLM_MAX_DNN
+
+
+class RNNLMWeights(ctypes.Structure):  # sbk_rnnlm_weights
+    _fields_ = [("emb_ih", c_void_p)] + [(n, c_void_p * TRANSDUCER_MAX_LAYERS) for n in ("w_ih", "w_hh", "b_ih", "b_hh")] + [
+        (n, c_void_p * RNNLM_MAX_DNN) for n in ("dnn_w", "dnn_b", "ln_g", "ln_b")] + [("ln_eps", c_float * RNNLM_MAX_DNN)] + [
+        (n, c_void_p) for n in ("out", "out_b")] + [
+        (n, c_int32) for n in ("n_layers", "hidden", "n_dnn", "dnn", "vocab", "n_emb", "act")]
+
+
 def _declare(lib):
     p, i, f = c_void_p, c_int, c_float
     sig = {
@@ -175,6 +185,11 @@ def _declare(lib):
                                                 ctypes.c_size_t),
         "sbk_transducer_beam_search_f32": ([POINTER(TransducerWeights), POINTER(TransducerBeamConfig), p, p, ctypes.c_size_t,
                                             p, p, p, p, p, i, i, p], c_int),
+        "sbk_transducer_beam_lm_workspace_bytes": ([POINTER(TransducerWeights), POINTER(RNNLMWeights),
+                                                    POINTER(TransducerBeamConfig), i, i], ctypes.c_size_t),
+        "sbk_transducer_beam_search_lm_f32": ([POINTER(TransducerWeights), POINTER(RNNLMWeights), f,
+                                               POINTER(TransducerBeamConfig), p, p, ctypes.c_size_t, p, p, p, p, p, i, i, p],
+                                              c_int),
         "sbk_beam_search_workspace_bytes": ([POINTER(DecoderWeights), POINTER(SearchConfig), i, i], ctypes.c_size_t),
         "sbk_beam_search_f32": ([POINTER(DecoderWeights), POINTER(SearchConfig), p, p, p, p, p, ctypes.c_size_t, p, p,
                                  p, p, p, p, p, POINTER(c_int32), i, i, p], c_int),
@@ -1656,6 +1671,46 @@ class TransducerPrepared:
         self.W, self._keep, self.device = W, keep, self.emb_ih.device
 
 
+class RNNLMPrepared:
+    """An RNNLM (lobes/models/RNNLM.py) in the layouts of sbk_rnnlm_weights (include/sbk.h): the Embedding folded into layer
+    0's input weights (one sbk_gemm_nt_f32), the other matrices as they are.  Built once per set of weights; the tensors are
+    kept alive here for as long as the struct points at them."""
+
+    def __init__(self, emb, lstm_layers, dnn_blocks, out_w, out_b, act):
+        """emb [n_emb, E]; lstm_layers: [(w_ih [4H, in], w_hh [4H, H], b_ih or None, b_hh or None)] * L; dnn_blocks:
+        [(w [D, in], b [D] or None, ln_weight [D], ln_bias [D], ln_eps)] * n_dnn; out_w [V, D], out_b [V] or None; act: one of
+        ACT_LEAKY_RELU, ACT_RELU, ACT_GELU, ACT_TANH (all fp32 on one device)."""
+        if not 1 <= len(lstm_layers) <= TRANSDUCER_MAX_LAYERS:
+            raise SbkError(f"RNNLM: {len(lstm_layers)} LSTM layers (1..{TRANSDUCER_MAX_LAYERS} supported)")
+        if not 1 <= len(dnn_blocks) <= RNNLM_MAX_DNN:
+            raise SbkError(f"RNNLM: {len(dnn_blocks)} DNN blocks (1..{RNNLM_MAX_DNN} supported)")
+        keep = []
+
+        def t(x):
+            x = x.detach().float().contiguous()
+            keep.append(x)
+            return x
+
+        ptr = lambda x: None if x is None else t(x).data_ptr()  # noqa: E731
+        w_ih0 = lstm_layers[0][0].detach().float().contiguous()
+        with precision_scope("fp32"):
+            self.emb_ih = t(gemm_nt(emb.detach().float().contiguous(), w_ih0))  # [n_emb, 4H] = E . W_ih^T
+        M = RNNLMWeights()
+        M.emb_ih = self.emb_ih.data_ptr()
+        for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(lstm_layers):
+            if l > 0:
+                M.w_ih[l] = ptr(w_ih)
+            M.w_hh[l], M.b_ih[l], M.b_hh[l] = ptr(w_hh), ptr(b_ih), ptr(b_hh)
+        for i, (w, b, g, beta, eps) in enumerate(dnn_blocks):
+            M.dnn_w[i], M.dnn_b[i], M.ln_g[i], M.ln_b[i], M.ln_eps[i] = ptr(w), ptr(b), ptr(g), ptr(beta), float(eps)
+        M.out, M.out_b = ptr(out_w), ptr(out_b)
+        M.n_layers, M.hidden, M.n_dnn, M.dnn = len(lstm_layers), lstm_layers[0][1].shape[1], len(dnn_blocks), out_w.shape[1]
+        M.vocab, M.n_emb, M.act = out_w.shape[0], emb.shape[0], int(act)
+        self.M, self._keep, self.device = M, keep, self.emb_ih.device
+        self.weight_bytes = 4 * sum(int(x.numel()) for x in keep) - 4 * int(self.emb_ih.numel()) + 4 * 4 * M.hidden
+        # (what one LM step reads: every matrix once, and one row of emb_ih)
+
+
 def lstm(x, layers, hx=None):
     """torch.nn.LSTM(batch_first=True, unidirectional) on the device: x [B,T,in]; layers [(w_ih, w_hh, b_ih, b_hh)] * L;
     hx (h0, c0) [L,B,H] or None -> (out [B,T,H], (h [L,B,H], c [L,B,H])).  Per layer: the input part of the gates for the
@@ -1711,12 +1766,15 @@ def transducer_beam_max_expansions(beam_size) -> int:
 
 
 def transducer_beam_search(prep: TransducerPrepared, tn, blank, beam_size, nbest, state_beam=2.3, expand_beam=2.3,
-                           max_expansions=None, max_tokens=None, act=ACT_GELU):
+                           max_expansions=None, max_tokens=None, act=ACT_GELU, lm: Optional["RNNLMPrepared"] = None,
+                           lm_weight=0.0, return_lm_steps=False):
     """sbk_transducer_beam_search_f32: tn [B,T,J] fp32 -> (tokens [B,nbest,max_tokens] int32, length [B,nbest] int32,
     score [B,nbest] fp32 (logp_score / len(prediction)), count [B] int32, status [B] int32 (TBEAM_* bits), expansions [B]
     int32).  max_expansions: the bound on a frame's expansions (default 4 * beam_size); max_tokens: the room per hypothesis
     (default T * max_expansions, which no hypothesis can exceed).  The workspace is the search workspace of the current
-    stream (grow-only, one per device and stream)."""
+    stream (grow-only, one per device and stream).  With ``lm`` (an RNNLMPrepared) the search is
+    sbk_transducer_beam_search_lm_f32 with ``lm_weight`` (> 0; the entry refuses anything else); ``return_lm_steps`` then
+    appends the LM steps each utterance took ([B] int32)."""
     lib = load()
     _f32(tn)
     B, T, J = tn.shape
@@ -1735,18 +1793,33 @@ def transducer_beam_search(prep: TransducerPrepared, tn, blank, beam_size, nbest
     score = torch.empty(B, max(cfg.nbest, 1), dtype=torch.float32, device=dev)
     count = torch.empty(B, dtype=torch.int32, device=dev)
     status = torch.empty(B, dtype=torch.int32, device=dev)
-    nbytes = lib.sbk_transducer_beam_workspace_bytes(ctypes.byref(prep.W), ctypes.byref(cfg), B, T)
+    if lm is None:
+        if return_lm_steps:
+            raise SbkError("transducer_beam_search: return_lm_steps without an LM")
+        nbytes = lib.sbk_transducer_beam_workspace_bytes(ctypes.byref(prep.W), ctypes.byref(cfg), B, T)
+    else:
+        if lm.device != prep.device:
+            raise SbkError(f"transducer_beam_search: the LM is prepared on {lm.device}, the network on {prep.device}")
+        nbytes = lib.sbk_transducer_beam_lm_workspace_bytes(ctypes.byref(prep.W), ctypes.byref(lm.M), ctypes.byref(cfg), B, T)
     ws, ws_key = _search_workspace(max(nbytes, 16) + 16, dev)
     off = (-ws.data_ptr()) % 16
     try:
         # (a refused configuration gives 0 bytes above; the entry then reports the reason)
-        _chk(lib.sbk_transducer_beam_search_f32(ctypes.byref(prep.W), ctypes.byref(cfg), _p(tn), c_void_p(ws.data_ptr() + off),
-                                                nbytes, _p(tokens), _p(length), _p(score), _p(count), _p(status), B, T,
-                                                _stream(tn)), "sbk_transducer_beam_search_f32")
+        if lm is None:
+            _chk(lib.sbk_transducer_beam_search_f32(ctypes.byref(prep.W), ctypes.byref(cfg), _p(tn),
+                                                    c_void_p(ws.data_ptr() + off), nbytes, _p(tokens), _p(length), _p(score),
+                                                    _p(count), _p(status), B, T, _stream(tn)), "sbk_transducer_beam_search_f32")
+        else:
+            _chk(lib.sbk_transducer_beam_search_lm_f32(ctypes.byref(prep.W), ctypes.byref(lm.M), float(lm_weight),
+                                                       ctypes.byref(cfg), _p(tn), c_void_p(ws.data_ptr() + off), nbytes,
+                                                       _p(tokens), _p(length), _p(score), _p(count), _p(status), B, T,
+                                                       _stream(tn)), "sbk_transducer_beam_search_lm_f32")
         expansions = ws[off:off + 4 * B].view(torch.int32).clone()
+        lm_steps = ws[off + 4 * B:off + 8 * B].view(torch.int32).clone() if lm is not None else None
     finally:
         _search_workspace_done(ws_key)
-    return tokens, length, score, count, status, expansions
+    ret = (tokens, length, score, count, status, expansions)
+    return ret + (lm_steps,) if return_lm_steps else ret
 
 
 # ------------------------------------------------------------------ HIP-event profiler

@@ -4,9 +4,14 @@ sharpened classifier: EncoderDecoderASR.transcribe_batch of 32 x 10 s from 16-bi
 decode kernel's own time (HIP events), and streaming-style decoding at B = 1 (one 8-frame chunk per call, the state carried
 in a TransducerGreedySearcherStreamingContext).  With --beam N (N > 1) the same batch is then decoded by beam search
 (beam_size N, nbest 5) in the same process: ms per batch, the beam kernel's own time, its ratio to the greedy kernel's, the
-mean expansions per frame and the number of utterances that reached max_expansions.  One JSON line.
+mean expansions per frame and the number of utterances that reached max_expansions.  With --lm as well, the beam search is
+measured a third time fused with an RNNLM of the recipe's shape (embedding 128, two LSTM layers of 2 048, one DNN block of
+512, random weights).  A random LM is noise of about -log(V) per token: at the recipe's lm_weight (0.5) it only suppresses
+every token and the search makes one LM step per utterance, so the default --lm-weight is 0.01, which leaves the search on
+(nearly) the path it takes without the LM and makes the difference of the two kernels the cost of the LM steps: ms per batch, the kernel's own time, the LM steps taken and the bytes of LM weights read
+per second; that result is also written to profiles/transducer_lm_bench.json.  One JSON line.
 
-    python tools/transducer_bench.py [--steps 10] [--warmup 3] [--beam 10]
+    python tools/transducer_bench.py [--steps 10] [--warmup 3] [--beam 10] [--lm [--lm-steps 3]]
 """
 import argparse
 import json
@@ -70,6 +75,9 @@ def main():
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--chunk-frames", type=int, default=8)
     ap.add_argument("--beam", type=int, default=0, help="also measure beam search with this beam_size (> 1)")
+    ap.add_argument("--lm", action="store_true", help="with --beam: also measure the beam search fused with an RNNLM")
+    ap.add_argument("--lm-weight", type=float, default=0.01, help="lm_weight of the LM leg (see the module's docstring)")
+    ap.add_argument("--lm-steps", type=int, default=3, help="timed batches of the LM leg (after one warm-up batch)")
     args = ap.parse_args()
     native.load()
     B, n = args.batch, int(args.seconds * 16000)
@@ -148,6 +156,54 @@ def main():
         res["beam_kernel_share_of_batch"] = round(res["transducer_beam_kernel_ms"] / res["beam_p50_ms"], 3)
         res["beam_expansions_per_frame_mean"] = round(float(out[5].float().mean()) / tn.shape[1], 3)
         res["beam_utterances_capped"] = int((out[4] != 0).sum())
+    if args.beam > 1 and args.lm:
+        from speechbrain_amd.lobes.models.RNNLM import RNNLM
+
+        torch.manual_seed(41)
+        lm = RNNLM(output_neurons=V, embedding_dim=128, rnn_layers=2, rnn_neurons=2048, dnn_blocks=1, dnn_neurons=512,
+                   dropout=0.0, return_hidden=True).to("cuda:0").eval()
+        searcher.lm, searcher.lm_weight = lm, args.lm_weight
+        times = []
+        for i in range(1 + args.lm_steps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            wav = pcm.cuda(non_blocking=True).float() / 32768.0
+            _, toks = asr.transcribe_batch(wav, lens)
+            torch.cuda.synchronize()
+            if i >= 1:
+                times.append(time.perf_counter() - t0)
+        times.sort()
+        res["beam_lm_p50_ms"] = round(times[len(times) // 2] * 1e3, 3)
+        res["beam_lm_tokens_per_utterance_mean"] = round(sum(len(t) for t in toks) / B, 1)
+        plm = searcher._prepare_lm(tn.device)
+        native.prof_reset()
+        native.prof_enable(True)
+        for _ in range(args.lm_steps):
+            out = native.transducer_beam_search(searcher._prepare(tn.device, beam=True), tn, 0, args.beam, 5, searcher.state_beam,
+                                                searcher.expand_beam, act=searcher.tjoint.act_code, lm=plm, lm_weight=args.lm_weight,
+                                                return_lm_steps=True)
+        torch.cuda.synchronize()
+        native.prof_enable(False)
+        rep = native.prof_report()
+        ms = rep["transducer_beam_lm"]["ms"] / rep["transducer_beam_lm"]["count"]
+        steps = out[6].cpu()
+        res["lm_weight"] = args.lm_weight
+        res["transducer_beam_lm_kernel_ms"] = round(ms, 3)
+        res["beam_lm_kernel_over_beam_kernel"] = round(ms / res["transducer_beam_kernel_ms"], 2)
+        res["beam_lm_expansions_per_frame_mean"] = round(float(out[5].float().mean()) / tn.shape[1], 3)
+        res["beam_lm_utterances_capped"] = int((out[4] != 0).sum())
+        res["lm_steps_total"], res["lm_steps_max_per_utterance"] = int(steps.sum()), int(steps.max())
+        res["lm_weight_bytes_per_step"] = int(plm.weight_bytes)
+        # the LM's share of the kernel: what the fused search takes beyond the plain one (one workgroup per utterance, so the
+        # kernel lasts as long as its slowest utterance; the aggregate rate counts every utterance's steps)
+        # (meaningful only where both searches make about the same expansions: compare the two expansions_per_frame_mean)
+        extra_s = (ms - res["transducer_beam_kernel_ms"]) * 1e-3
+        if extra_s > 0:
+            res["lm_step_ms_per_workgroup"] = round(extra_s * 1e3 / max(1, int(steps.max())), 4)
+            res["lm_gbytes_per_s_per_workgroup"] = round(plm.weight_bytes * int(steps.max()) / extra_s / 1e9, 2)
+            res["lm_gbytes_per_s_all_workgroups"] = round(plm.weight_bytes * int(steps.sum()) / extra_s / 1e9, 2)
+        with open(os.path.join(ROOT, "profiles", "transducer_lm_bench.json"), "w", encoding="utf-8") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
     print(json.dumps(res))
 
 
