@@ -426,6 +426,39 @@ int sbk_ctc_beam_search_f32(const float* x, const float* rel_len, const int32_t*
                             const sbk_ctc_beam_config* cfg, void* workspace, size_t workspace_bytes, int32_t* out_tokens,
                             float* out_score, int32_t* out_count, int B, int T, int V, sbk_stream_t stream);
 
+/* CTCBeamSearcher with an n-gram language model fused into the search (decoders/ctc.py:1203-1296 get_lm_beams with self.lm
+ * set, integrations/decoders/kenlm_scorer.py; additive entry, ABI 11 unchanged): the same kernel body as above with a larger
+ * beam record.  Every beam carries the raw LM score of its text (a double, as the reference adds Python floats), its n-gram
+ * context, the penalty of its partial word and lm_score = score + fp32(LM terms); ranking, the beam_prune_logp cut and the
+ * final order read lm_score, merging adds the CTC scores, and with prune_history the history key holds the last
+ * max(1, order - 1) words.  "</s>" is never scored (finalize_decoding passes is_eos = False).  Arguments as above, plus
+ *   out_lm_score [B,topk]: the fused score (out_score stays the CTC score), and the tables, all device memory:
+ *   strings [n_string_slots][4] int32, open addressing with linear probing, n_string_slots a power of two: every prefix
+ *     (proper or not) of every word of the unigram set and every word of the model, keyed by the hashes of the token table:
+ *     {h1, h2, length in characters (-1 = empty slot), (word id + 1) << 2 | known << 1 | prefix}.  word id + 1 = 0: not a
+ *     word of the model; known: in the unigram set AND in the model (no unk_score_offset); prefix: a prefix of a word of the
+ *     unigram set.  Slot of a key: mix(h1 ^ h2 * 0x9e3779b1 ^ length * 0x85ebca6b) with mix(x) = (x ^= x >> 15, x *=
+ *     0x2c1b3c6d, x ^ x >> 12) in uint32.
+ *   unigrams [n_words][2] fp32: log10 p and back-off by word id.
+ *   ngrams [n_ngram_slots][8] int32, the same addressing: the n-grams of order n >= 2 as {n (0 = empty slot), the n word ids
+ *     with the LAST word first and -1 behind them (5), log10 p, back-off (fp32 bits)}.  Slot: x = n, then for each id in
+ *     that order x = mix((x ^ id) * 0x9e3779b1).
+ *   order 1..5; unk_id = the id of "<unk>"; bos_id = the id of "<s>" (the start context when score_boundary != 0); alpha,
+ *   beta, unk_score_offset as KenlmScorer; log10_e = log10(e), the divisor of its conversion to natural logarithms.
+ * beam_size 1..256 as above (the four beam arrays take 4 * beam_size * 128 bytes of LDS). */
+typedef struct sbk_ctc_lm_tables {
+  const int32_t* strings;
+  const float* unigrams;
+  const int32_t* ngrams;
+  int32_t n_string_slots, n_words, n_ngram_slots;
+  int32_t order, unk_id, bos_id, score_boundary;
+  double alpha, beta, unk_score_offset, log10_e;
+} sbk_ctc_lm_tables;
+int sbk_ctc_beam_search_lm_f32(const float* x, const float* rel_len, const int32_t* token_table, int Vl,
+                               const sbk_ctc_beam_config* cfg, const sbk_ctc_lm_tables* lm, void* workspace,
+                               size_t workspace_bytes, int32_t* out_tokens, float* out_score, float* out_lm_score,
+                               int32_t* out_count, int B, int T, int V, sbk_stream_t stream);
+
 /* ---- transducer greedy decoding (csrc/transducer.hip; additive entries, ABI 11 unchanged) -------------------------------
  * TransducerBeamSearcher.transducer_greedy_decode (decoders/transducer.py:156-291) for the prediction network (PN)
  * [Embedding, LSTM (1..SBK_TRANSDUCER_MAX_LAYERS unidirectional layers, torch gate order i, f, g, o), Linear proj_dec], the

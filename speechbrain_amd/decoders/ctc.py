@@ -3,8 +3,9 @@
 
 The frame loop of the beam search runs on the MI355X in one launch per batch (include/sbk.h, sbk_ctc_beam_search_f32); the
 host only rebuilds each returned hypothesis' ``text`` and ``text_frames`` by replaying the token path the kernel reports
-through the reference's string rules (O(T) per hypothesis).  Language-model fusion (kenlm), CTCPrefixBeamSearcher and the
-streaming ``partial_decode_beams`` are not implemented."""
+through the reference's string rules (O(T) per hypothesis).  With ``kenlm_model_path`` an ARPA n-gram model (order 1..5,
+decoders/ngram.py) is fused into the same launch (sbk_ctc_beam_search_lm_f32).  CTCPrefixBeamSearcher and the streaming
+``partial_decode_beams`` are not implemented."""
 import dataclasses
 import math
 import warnings
@@ -77,8 +78,10 @@ def string_hash(s):
 
 
 class CTCBaseSearcher(torch.nn.Module):
-    """decoders/ctc.py:544-1153: same constructor arguments and defaults.  ``kenlm_model_path`` / ``unigrams`` (n-gram
-    shallow fusion) raise NotImplementedError."""
+    """decoders/ctc.py:544-1153: same constructor arguments and defaults.  ``kenlm_model_path`` names an ARPA text file
+    of order 1..5 (kenlm's binary formats raise NotImplementedError); ``unigrams``, ``alpha``, ``beta``,
+    ``unk_score_offset`` and ``score_boundary`` mean what they mean to the reference's KenlmScorer.  ``self.lm`` is then a
+    decoders.ngram.NgramLM (``.order``), whose tables are built once here and kept on the device."""
 
     def __init__(self, blank_index: int, vocab_list: List[str], space_token: str = " ",
                  kenlm_model_path: Union[None, str] = None, unigrams: Union[None, list, set] = None, alpha: float = 0.5,
@@ -86,9 +89,6 @@ class CTCBaseSearcher(torch.nn.Module):
                  beam_prune_logp: float = -10.0, token_prune_min_logp: float = -5.0, prune_history: bool = True,
                  blank_skip_threshold: float = 1.0, topk: int = 1, spm_token: str = "▁"):
         super().__init__()
-        if kenlm_model_path is not None or unigrams is not None:
-            raise NotImplementedError("CTC beam search with a kenlm n-gram model (kenlm_model_path / unigrams) is not "
-                                      "implemented: decode without a language model")
         self.blank_index = blank_index
         self.vocab_list = vocab_list
         self.space_token = space_token
@@ -110,7 +110,12 @@ class CTCBaseSearcher(torch.nn.Module):
             except ValueError:
                 self.space_index = -1
         self.kenlm_model = None
-        self.lm = None
+        self.lm = None  # (unigrams without a model are ignored, as in the reference)
+        if kenlm_model_path is not None:
+            from speechbrain_amd.decoders.ngram import NgramLM
+
+            self.lm = NgramLM(kenlm_model_path, unigrams=unigrams, alpha=alpha, beta=beta,
+                              unk_score_offset=unk_score_offset, score_boundary=score_boundary)
         self._table = None
 
     def normalize_whitespace(self, text: str) -> str:
@@ -153,9 +158,10 @@ class CTCBaseSearcher(torch.nn.Module):
             self._table = torch.tensor(rows, dtype=torch.int32).reshape(-1, 8)
         return self._table
 
-    def replay(self, path, score):
+    def replay(self, path, score, lm_score=None):
         """The hypothesis that follows ``path`` (the token expanded at each frame, -1 = none), through the rules of
-        CTCBeamSearcher.partial_decoding / get_lm_beams / finalize_decoding / decode_log_probs."""
+        CTCBeamSearcher.partial_decoding / get_lm_beams / finalize_decoding / decode_log_probs.  ``score`` is the CTC score;
+        ``lm_score`` the fused one (without a language model it is the CTC score)."""
         vocab, blank, spm = self.vocab_list, self.blank_index, self.spm_token
         text, partial, last, frames, pf = "", "", None, [], (-1, -1)
         for t, v in enumerate(path):
@@ -179,7 +185,8 @@ class CTCBaseSearcher(torch.nn.Module):
         text = self.merge_tokens(text, partial)
         score = np.float32(score)
         return CTCHypothesis(text=self.normalize_whitespace(text), last_lm_state=None,
-                             text_frames=list(zip(text.split(), frames)), score=score, lm_score=score)
+                             text_frames=list(zip(text.split(), frames)), score=score,
+                             lm_score=score if lm_score is None else np.float32(lm_score))
 
     def decode_beams(self, log_probs: torch.Tensor, wav_lens: Optional[torch.Tensor] = None,
                      lm_start_state: Any = None) -> List[List[CTCHypothesis]]:
@@ -190,8 +197,8 @@ class CTCBaseSearcher(torch.nn.Module):
 
 
 class CTCBeamSearcher(CTCBaseSearcher):
-    """decoders/ctc.py:1156-1487 without a language model: the whole search of a batch is one device launch
-    (sbk_ctc_beam_search_f32).  Beam sizes up to 256."""
+    """decoders/ctc.py:1156-1487: the whole search of a batch is one device launch (sbk_ctc_beam_search_f32; with an
+    n-gram model, sbk_ctc_beam_search_lm_f32).  Beam sizes up to 256 on both paths."""
 
     def config(self):
         from speechbrain_amd import native
@@ -209,7 +216,8 @@ class CTCBeamSearcher(CTCBaseSearcher):
         from speechbrain_amd import native
 
         if lm_start_state is not None:
-            raise NotImplementedError("lm_start_state: CTC beam search with a language model is not implemented")
+            raise NotImplementedError("lm_start_state: the search starts from the model's begin-of-sentence or null "
+                                      "context; resuming from a given language-model state is not implemented")
         if log_probs.size(2) != len(self.vocab_list):
             warnings.warn(f"Vocab size mismatch: log_probs vocab dim is {log_probs.size(2)} while vocab_list is "
                           f"{len(self.vocab_list)}. During decoding, going to truncate the log_probs vocab dim to match "
@@ -217,6 +225,12 @@ class CTCBeamSearcher(CTCBaseSearcher):
         if log_probs.size(2) < len(self.vocab_list):
             raise NotImplementedError("CTC beam search: a vocabulary longer than the posteriors' last dimension")
         x = log_probs if log_probs.dtype == torch.float32 else log_probs.float()
+        if self.lm is not None:
+            paths, scores, count, fused = native.ctc_beam_search(x, wav_lens, self.token_table(), len(self.vocab_list),
+                                                                 self.config(), lm=self.lm)
+            paths, scores, fused, count = paths.cpu().numpy(), scores.cpu().numpy(), fused.cpu().numpy(), count.cpu().tolist()
+            return [[self.replay(paths[b, k], scores[b, k], fused[b, k]) for k in range(count[b])]
+                    for b in range(len(count))]
         paths, scores, count = native.ctc_beam_search(x, wav_lens, self.token_table(), len(self.vocab_list),
                                                       self.config())
         paths, scores, count = paths.cpu().numpy(), scores.cpu().numpy(), count.cpu().tolist()

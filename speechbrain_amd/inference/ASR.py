@@ -113,8 +113,8 @@ class EncoderASR(Pretrained):
         else:
             raise ValueError("The tokenizer must be sentencepiece or CTCTextEncoder")
         opts = dict(getattr(self.hparams, "test_beam_search", None) or {})
-        if "kenlm_model_path" in opts:
-            raise NotImplementedError("CTC beam search with a kenlm n-gram model is not implemented")
+        # (kenlm_model_path, if any, is taken as given: the reference's from_hparams does not resolve it against the model
+        # directory either; it must name an ARPA text file, decoders/ngram.py)
         self.decoding_function = fn(**opts, vocab_list=vocab_list)
 
     def transcribe_file(self, path, **kwargs):

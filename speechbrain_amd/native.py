@@ -76,6 +76,13 @@ class CTCBeamConfig(ctypes.Structure):  # sbk_ctc_beam_config
                 ("char_base1", ctypes.c_uint32), ("char_base2", ctypes.c_uint32), ("space_code", ctypes.c_uint32)]
 
 
+class CTCLMTables(ctypes.Structure):  # sbk_ctc_lm_tables
+    _fields_ = [("strings", c_void_p), ("unigrams", c_void_p), ("ngrams", c_void_p), ("n_string_slots", c_int32),
+                ("n_words", c_int32), ("n_ngram_slots", c_int32), ("order", c_int32), ("unk_id", c_int32),
+                ("bos_id", c_int32), ("score_boundary", c_int32), ("alpha", ctypes.c_double), ("beta", ctypes.c_double),
+                ("unk_score_offset", ctypes.c_double), ("log10_e", ctypes.c_double)]
+
+
 TRANSDUCER_MAX_LAYERS = 4
 ACT_TANH = 5  # SBK_ACT_TANH (the transducer joint only)
 
@@ -178,6 +185,8 @@ def _declare(lib):
         "sbk_ctc_greedy_decode_f32": ([p, p, p, p, i, i, i, i, p], c_int),
         "sbk_ctc_beam_search_workspace_bytes": ([i, i, i, i, i], ctypes.c_size_t),
         "sbk_ctc_beam_search_f32": ([p, p, p, i, POINTER(CTCBeamConfig), p, ctypes.c_size_t, p, p, p, i, i, i, p], c_int),
+        "sbk_ctc_beam_search_lm_f32": ([p, p, p, i, POINTER(CTCBeamConfig), POINTER(CTCLMTables), p, ctypes.c_size_t, p, p, p,
+                                        p, i, i, i, p], c_int),
         "sbk_transducer_greedy_f32": ([POINTER(TransducerWeights), POINTER(TransducerConfig), p, p, p, p, p, p, p, i, i, p],
                                       c_int),
         "sbk_lstm_f32": ([p, p, p, p, p, p, p, i, i, i, p], c_int),
@@ -1609,9 +1618,11 @@ def ctc_greedy_decode(x, rel_len, blank):
     return tokens, count
 
 
-def ctc_beam_search(x, rel_len, table, n_vocab, cfg):
-    """CTCBeamSearcher without an LM on the device.  x [B,T,V] fp32 log-probabilities, table [n_vocab,8] int32 (the token
-    table of include/sbk.h), cfg a CTCBeamConfig -> (paths [B,topk,T] int32, scores [B,topk], count [B])."""
+def ctc_beam_search(x, rel_len, table, n_vocab, cfg, lm=None):
+    """CTCBeamSearcher on the device.  x [B,T,V] fp32 log-probabilities, table [n_vocab,8] int32 (the token table of
+    include/sbk.h), cfg a CTCBeamConfig -> (paths [B,topk,T] int32, scores [B,topk], count [B]).  With ``lm`` (an object
+    whose ``tables(device)`` gives a CTCLMTables over device tensors: decoders/ngram.py) the n-gram model is fused into the
+    search (sbk_ctc_beam_search_lm_f32) and the fused scores [B,topk] are returned as a fourth value."""
     lib = load()
     _f32(x)
     B, T, V = x.shape
@@ -1625,6 +1636,13 @@ def ctc_beam_search(x, rel_len, table, n_vocab, cfg):
     paths = torch.empty(B, max(cfg.topk, 1), T, dtype=torch.int32, device=x.device)
     scores = torch.empty(B, max(cfg.topk, 1), dtype=torch.float32, device=x.device)
     count = torch.empty(B, dtype=torch.int32, device=x.device)
+    if lm is not None:
+        tabs = lm.tables(x.device)
+        lm_scores = torch.empty_like(scores)
+        _chk(lib.sbk_ctc_beam_search_lm_f32(_p(x), _p(rel), _p(table), int(n_vocab), ctypes.byref(cfg), ctypes.byref(tabs),
+                                            c_void_p(ws.data_ptr() + off), nbytes, _p(paths), _p(scores), _p(lm_scores),
+                                            _p(count), B, T, V, _stream(x)), "sbk_ctc_beam_search_lm_f32")
+        return paths, scores, count, lm_scores
     _chk(lib.sbk_ctc_beam_search_f32(_p(x), _p(rel), _p(table), int(n_vocab), ctypes.byref(cfg),
                                      c_void_p(ws.data_ptr() + off), nbytes, _p(paths), _p(scores), _p(count), B, T, V,
                                      _stream(x)), "sbk_ctc_beam_search_f32")

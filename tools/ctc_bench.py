@@ -2,7 +2,12 @@
 transcribe_batch of 32 x 10 s from 16-bit PCM with greedy decoding and with CTCBeamSearcher (beam 100, beam_prune_logp
 -12, token_prune_min_logp -1.2, prune_history False), plus the decode kernels' own times (HIP events).  One JSON line.
 
-    python tools/ctc_bench.py [--steps 10] [--warmup 3]
+    python tools/ctc_bench.py [--steps 10] [--warmup 3] [--arpa PATH | --lm-order N] [--compare-lib libsbk_hip.so]
+
+With --arpa or --lm-order the same log-probabilities are also searched with an n-gram model fused in (--lm-order: a synthetic
+ARPA model of that order, whose size is recorded), and the plain and the fused beam-100 kernels are timed side by side in
+blocks of launches (HIP events around each block; the spread of the block means is reported).  --compare-lib times the plain
+kernel of another build of the library, such as the parent commit's, in the same blocks.
 """
 import argparse
 import functools
@@ -50,6 +55,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--seconds", type=float, default=10.0)
+    ap.add_argument("--arpa", default=None, help="an ARPA n-gram model to fuse into the beam search")
+    ap.add_argument("--lm-order", type=int, default=0, help="generate a synthetic ARPA model of this order instead")
+    ap.add_argument("--compare-lib", default=None, help="another libsbk_hip.so whose plain beam kernel is timed alongside")
     args = ap.parse_args()
     native.load()
     B, n = args.batch, int(args.seconds * 16000)
@@ -84,7 +92,79 @@ def main():
         key = "ctc_greedy_decode" if name == "greedy" else "ctc_beam_search"
         res[f"{key}_kernel_ms"] = round(rep[key]["ms"] / rep[key]["count"], 4)
         res[f"{name}_frames"] = int(logp.shape[1])
+    if args.arpa or args.lm_order:
+        res.update(lm_kernels(args, asr, logp, lens.cuda()))
     print(json.dumps(res))
+
+
+def lm_kernels(args, asr, logp, lens):
+    """The plain and the fused beam-100 kernels on the same log-probabilities, in alternating blocks of launches."""
+    import ctypes
+    import tempfile
+
+    import numpy as np
+
+    from speechbrain_amd import native
+    from speechbrain_amd.decoders.ctc import CTCBeamSearcher
+    from tools.arpa_synth import arpa_text
+
+    out = {}
+    path = args.arpa
+    if path is None:
+        rng = np.random.RandomState(5)
+        words = sorted({"".join(chr(97 + k) for k in rng.randint(0, 26, size=rng.randint(1, 9))) for _ in range(20000)})
+        path = os.path.join(tempfile.mkdtemp(), "synthetic.arpa")
+        with open(path, "w", encoding="utf-8") as f:
+            f.write(arpa_text(words, args.lm_order, seed=6, per_order=4 * len(words)))
+        out["lm_synthetic_words"], out["lm_file_bytes"] = len(words), os.path.getsize(path)
+    t0 = time.perf_counter()
+    s = CTCBeamSearcher(vocab_list=CHARS, kenlm_model_path=path, **BEAM)
+    out["lm_load_s"] = round(time.perf_counter() - t0, 3)
+    out["lm_order"], out["lm_ngrams_above_order_1"], out["lm_unigrams"] = s.lm.order, s.lm.n_ngrams, len(s.lm.unigrams)
+    hyp = s(logp, lens)
+    out["lm_first_text"] = hyp[0][0].text[:60]
+    plain = asr.decoding_function
+    B, T, V = logp.shape
+    cfg, table = plain.config(), plain.token_table().to(logp.device).contiguous()
+    lib = native.load()
+    nbytes = lib.sbk_ctc_beam_search_workspace_bytes(B, T, V, cfg.beam_size, cfg.topk)
+    ws = torch.empty(nbytes + 16, dtype=torch.uint8, device=logp.device)
+    wsp = ctypes.c_void_p(ws.data_ptr() + (-ws.data_ptr()) % 16)
+    paths = torch.empty(B, cfg.topk, T, dtype=torch.int32, device=logp.device)
+    sc, fused = torch.empty(B, cfg.topk, device=logp.device), torch.empty(B, cfg.topk, device=logp.device)
+    cnt = torch.empty(B, dtype=torch.int32, device=logp.device)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    tabs = s.lm.tables(logp.device)
+
+    def run_plain(lb):
+        assert lb.sbk_ctc_beam_search_f32(p(logp), p(lens), p(table), V, ctypes.byref(cfg), wsp, nbytes, p(paths), p(sc),
+                                          p(cnt), B, T, V, None) == 0
+
+    def run_fused(lb):
+        assert lb.sbk_ctc_beam_search_lm_f32(p(logp), p(lens), p(table), V, ctypes.byref(cfg), ctypes.byref(tabs), wsp, nbytes,
+                                             p(paths), p(sc), p(fused), p(cnt), B, T, V, None) == 0
+
+    legs = [("plain", run_plain, lib), ("fused", run_fused, lib)]
+    if args.compare_lib:
+        other = ctypes.CDLL(args.compare_lib)
+        other.sbk_ctc_beam_search_f32.argtypes = lib.sbk_ctc_beam_search_f32.argtypes
+        legs.insert(0, ("compare_lib_plain", run_plain, other))
+    blocks = {name: [] for name, _, _ in legs}
+    for rep in range(7):
+        for name, fn, lb in legs:
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            fn(lb)
+            a.record()
+            for _ in range(args.steps):
+                fn(lb)
+            b.record()
+            torch.cuda.synchronize()
+            if rep > 0:
+                blocks[name].append(a.elapsed_time(b) / args.steps)
+    for name, v in blocks.items():
+        out[f"{name}_kernel_ms_blocks"] = [round(t, 4) for t in v]
+        out[f"{name}_kernel_ms_median"] = round(sorted(v)[len(v) // 2], 4)
+    return out
 
 
 if __name__ == "__main__":
