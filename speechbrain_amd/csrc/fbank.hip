@@ -186,6 +186,13 @@ __global__ void __launch_bounds__(256) whisper_floor_kernel(const float* __restr
     if (m < M && t < T) out[((size_t)b * M + m) * T + t] = (fmaxf(tile[c][r], floor_v) + 4.0f) / 4.0f;
   }
 }
+
+// The frames kernel takes 72 B of dynamic LDS per FFT point: past the 64 KiB default window from n_fft ~ 800 on.
+int allow_frames_lds(const char* who, size_t lds, int n_fft) {
+  if (lds > 64 * 1024 && (int)SBK_ALLOW_DYN_LDS(fbank_frames_kernel, lds) != 0)
+    return sbk::fail(SBK_EINVAL, "%s: %zu bytes of LDS for n_fft=%d not available", who, lds, n_fft);
+  return 0;
+}
 }  // namespace
 
 extern "C" int sbk_fbank_f32(const float* wav, const float* window, const float* twiddle, const int32_t* radices,
@@ -217,6 +224,7 @@ extern "C" int sbk_fbank_f32(const float* wav, const float* window, const float*
   SBK_REQUIRE(lds <= 160 * 1024, "fbank: n_fft=%d needs %zu B of LDS", n_fft, lds);
   FbankArgs a{wav, window, twiddle, mel_w, mel_ptr, mel_bin, out, tile_max, B, N, T, n_fft, hop, n_mels, nnz, ntiles, amin, nullptr,
               0, 10.0f};
+  if (int rc = allow_frames_lds("fbank", lds, n_fft)) return rc;
   hipStream_t st = sbk::as_stream(stream);
   sbk::ProfScope prof("fbank", 5.0 * n_fft * 9.0 * B * T, 4.0 * ((double)B * N + 3.0 * B * T * n_mels), st);
   SBK_LAUNCH(fbank_frames_kernel, dim3(ntiles, B), dim3(256), lds, st, a, rad);
@@ -250,6 +258,7 @@ extern "C" int sbk_stft_f32(const float* wav, const float* window, const float* 
   const int T = 1 + N / hop, ntiles = sbk::cdiv(T, 4), n_stft = n_fft / 2 + 1;
   const size_t lds = (size_t)n_fft * 8 + (size_t)4 * 2 * n_fft * 8 + (size_t)4 * n_stft * 4 + 16;
   SBK_REQUIRE(lds <= 160 * 1024, "stft: n_fft=%d needs %zu B of LDS", n_fft, lds);
+  if (int rc = allow_frames_lds("stft", lds, n_fft)) return rc;
   FbankArgs a{wav, window, twiddle, nullptr, nullptr, nullptr, nullptr, nullptr, B, N, T, n_fft, hop, 0, 0, ntiles, 0.0f, spec};
   SBK_LAUNCH(fbank_frames_kernel, dim3(ntiles, B), dim3(256), lds, sbk::as_stream(stream), a, rad);
   return sbk::launch_status("sbk_stft_f32");
@@ -384,6 +393,7 @@ extern "C" int sbk_whisper_log_mel_f32(const float* wav, const float* window, co
   SBK_REQUIRE(lds <= 160 * 1024, "whisper_log_mel: n_fft=%d needs %zu B of LDS", n_fft, lds);
   FbankArgs a{wav, window, twiddle, mel_w, mel_ptr, mel_bin, tmp, tile_max, B, N, T, n_fft, hop, n_mels, nnz, ntiles, 1e-10f,
               nullptr, 1, 1.0f};
+  if (int rc = allow_frames_lds("whisper_log_mel", lds, n_fft)) return rc;
   hipStream_t st = sbk::as_stream(stream);
   sbk::ProfScope prof("whisper_log_mel", 5.0 * n_fft * 9.0 * B * T, 4.0 * ((double)B * N + 3.0 * B * T * n_mels), st);
   SBK_LAUNCH(fbank_frames_kernel, dim3(ntiles, B), dim3(256), lds, st, a, rad);

@@ -55,6 +55,8 @@ class STFT(torch.nn.Module):
         self.sample_rate, self.n_fft = sample_rate, n_fft
         self.win_length = int(round((sample_rate / 1000.0) * win_length))
         self.hop_length = int(round((sample_rate / 1000.0) * hop_length))
+        if self.win_length > n_fft:  # torch.stft refuses it too; the kernel would read a truncated, off-centre window
+            raise ValueError("win_length longer than n_fft")
         self.normalized_stft, self.center, self.pad_mode, self.onesided = normalized_stft, center, pad_mode, onesided
         window = window_fn(self.win_length)
         self.register_buffer("window", window, persistent=False)
