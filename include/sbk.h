@@ -393,6 +393,19 @@ int sbk_rope_attention_bf16(const float* qkv, const float* cosines, const float*
 int sbk_glu_dwconv_f32(const float* h, const float* w, const float* bias, float* y, int B, int T, int d, int ksize,
                        int chunk_size, sbk_stream_t stream);
 
+/* ---- Convolutional Spatial Gating Unit of the Branchformer cgMLP branch (csrc/csgu.hip; additive entry, ABI 11 unchanged)
+ * lobes/models/convolution.py:92-113 with nnet/CNN.py Conv1d(padding="same", padding_mode="reflect", groups = C):
+ *   h [B,T,2C] (the activated output of pre_channel_proj);  x1 = h[..., :C] gates,  x2 = h[..., C:] is filtered
+ *   n       = LayerNorm_C(x2; gamma[C], beta[C], eps)                 (biased variance, eps inside the root)
+ *   c[t,ch] = bias[ch] + sum_k w[ch,k] * n[refl(t + k - halo), ch],   halo = (ksize-1)/2, w [C,ksize] (torch conv1d orientation)
+ *   refl(i) = -i (i < 0), 2(T-1) - i (i >= T): the padding mirrors each batch row over the padded length T; nothing is
+ *   masked by utterance length (Branchformer.py:224-228 runs the branch unmasked)
+ *   y[t,ch] = gate_act(c[t,ch]) * x1[t,ch]                            -> y [B,T,C]
+ * stats: scratch of B*T*2 floats (mean and 1/std of every frame, written by the first of the two launches).
+ * ksize 3, 5, 7, 15 or 31; T > halo (SBK_EINVAL otherwise, as F.pad refuses it); gate_act SBK_ACT_NONE / _SWISH / _GELU / _RELU. */
+int sbk_csgu_f32(const float* h, const float* gamma, const float* beta, float eps, const float* w, const float* bias,
+                 float* y, float* stats, int B, int T, int C, int ksize, int gate_act, sbk_stream_t stream);
+
 /* ---- CTC decoding (csrc/ctc_decode.hip; additive entries, ABI 11 unchanged) ---------------------------------------------
  * ctc_greedy_decode (decoders/ctc.py:335-380): x [B,T,V] (log-)probabilities, rel_len [B] relative lengths (device; NULL =
  * 1.0).  Utterance b uses its first int(round(fp32(rel_len[b] * T))) frames (round half to even, as torch.round); per frame

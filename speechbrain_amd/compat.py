@@ -12,7 +12,8 @@ import types
 
 _MODULES = [
     "processing", "processing.features", "lobes", "lobes.features", "lobes.models", "lobes.models.convolution",
-    "lobes.models.transformer", "lobes.models.transformer.Conformer", "lobes.models.transformer.Transformer",
+    "lobes.models.transformer", "lobes.models.transformer.Conformer", "lobes.models.transformer.Branchformer",
+    "lobes.models.transformer.Transformer",
     "lobes.models.transformer.TransformerASR", "lobes.models.transformer.TransformerLM", "lobes.models.RNNLM", "nnet", "nnet.attention", "nnet.activations", "nnet.CNN",
     "nnet.containers", "nnet.embedding", "nnet.linear", "nnet.normalization", "decoders", "decoders.seq2seq",
     "decoders.scorer", "decoders.utils", "inference", "inference.ASR", "inference.interfaces", "utils",

@@ -12,6 +12,58 @@ class _NamedChildren(torch.nn.ModuleDict):
     pass
 
 
+def _gate_act_code(m) -> int:
+    """Act code of the CSGU gate: Identity (the recipes') and the activations csrc/csgu.hip applies on the way out."""
+    if isinstance(m, torch.nn.Identity):
+        return native.ACT_NONE
+    from speechbrain_amd.nnet.attention import _act_code
+
+    try:
+        code = _act_code(m)
+    except NotImplementedError:
+        code = None
+    if code not in native.CSGU_GATE_ACTS:
+        raise NotImplementedError(f"gate_activation {type(m).__name__}: Identity, Swish / SiLU, GELU and ReLU are fused into the CSGU kernel")
+    return code
+
+
+class ConvolutionalSpatialGatingUnit(torch.nn.Module):
+    """CSGU of the Branchformer cgMLP branch (convolution.py:22-113): x1, x2 = x.chunk(2, -1); act(conv(LayerNorm(x2))) * x1
+    with a depthwise reflect-padded convolution over time -- one fused kernel (native.csgu) after a per-frame statistics pass.
+    [B,T,D] -> [B,T,D/2]; state_dict: norm.norm.{weight,bias}, conv.conv.{weight [D/2,1,k], bias}."""
+
+    def __init__(self, input_size: int, kernel_size: int = 31, dropout: float = 0.0, use_linear_after_conv: bool = False,
+                 activation=torch.nn.Identity):
+        super().__init__()
+        from speechbrain_amd.nnet.CNN import Conv1d
+
+        if use_linear_after_conv:
+            raise NotImplementedError("use_linear_after_conv=True (a Linear between the CSGU convolution and its gate) is not implemented")
+        self.input_size, self.use_linear_after_conv = input_size, use_linear_after_conv
+        self.activation = activation()
+        self.act_code = _gate_act_code(self.activation)
+        if self.input_size % 2 != 0:
+            raise ValueError("Input size must be divisible by 2!")
+        n_channels = input_size // 2
+        if kernel_size not in native.CSGU_KERNEL_SIZES:
+            raise NotImplementedError(f"CSGU kernel_size {kernel_size}: the kernel is instantiated for {native.CSGU_KERNEL_SIZES}")
+        self.kernel_size = kernel_size
+        self.norm = LayerNorm(n_channels)
+        self.conv = Conv1d(input_shape=(None, None, n_channels), out_channels=n_channels, kernel_size=kernel_size, stride=1,
+                           padding="same", groups=n_channels, conv_init="normal", skip_transpose=False)
+        torch.nn.init.ones_(self.conv.conv.bias)
+        self.dropout = torch.nn.Dropout(dropout)
+
+    def forward(self, x, out=None):
+        C = self.input_size // 2
+        halo = (self.kernel_size - 1) // 2
+        if x.shape[-2] <= halo:  # (the reference's F.pad(mode="reflect") raises here too)
+            raise ValueError(f"CSGU: a sequence of T={x.shape[-2]} frames cannot be reflect-padded by {halo} (kernel_size={self.kernel_size})")
+        return native.csgu(x.contiguous(), self.norm.norm.weight, self.norm.norm.bias, self.norm.eps,
+                           self.conv.conv.weight.reshape(C, self.kernel_size), self.conv.conv.bias, self.kernel_size,
+                           self.act_code, out=out)
+
+
 class ConvBlock(torch.nn.Module):
     """conv(3x3, stride s, reflect 'same') -> LayerNorm(F',C') -> LeakyReLU -> Dropout, one HIP launch."""
 

@@ -117,8 +117,8 @@ class TransformerDecoder(nn.Module):
 
 
 class TransformerInterface(nn.Module):
-    """Transformer.py:35-250: encoder_module="conformer" + RelPosMHAXL (TransformerASR) or
-    encoder_module="transformer" + regularMHA (TransformerLM)."""
+    """Transformer.py:35-250: encoder_module="conformer" + RelPosMHAXL | RoPEMHA or encoder_module="branchformer" +
+    RelPosMHAXL (TransformerASR), or encoder_module="transformer" + regularMHA (TransformerLM)."""
 
     def __init__(self, d_model=512, nhead=8, num_encoder_layers=6, num_decoder_layers=6, d_ffn=2048, dropout=0.1,
                  activation=nn.ReLU, custom_src_module=None, custom_tgt_module=None,
@@ -138,10 +138,20 @@ class TransformerInterface(nn.Module):
         assert positional_encoding in ["fixed_abs_sine", None]
         assert num_encoder_layers + num_decoder_layers > 0
         lm_like = encoder_module == "transformer" and attention_type == "regularMHA"
-        if not lm_like and (encoder_module != "conformer" or attention_type not in ("RelPosMHAXL", "RoPEMHA") or causal):
+        branchformer = encoder_module == "branchformer"
+        if branchformer:
+            if attention_type != "RelPosMHAXL":
+                raise NotImplementedError(f"encoder_module='branchformer' with attention_type='{attention_type}': RelPosMHAXL "
+                                          "is implemented (regularMHA and hypermixing are not)")
+            if use_linear_after_conv:
+                raise NotImplementedError("encoder_module='branchformer' with use_linear_after_conv=True is not implemented")
+            if causal:
+                raise NotImplementedError("encoder_module='branchformer' with causal=True is not implemented")
+        elif not lm_like and (encoder_module != "conformer" or attention_type not in ("RelPosMHAXL", "RoPEMHA") or causal):
             raise NotImplementedError(
-                "implemented: encoder_module='conformer' with attention_type='RelPosMHAXL' | 'RoPEMHA', causal=False "
-                "(ASR) and encoder_module='transformer' with attention_type='regularMHA' (TransformerLM)")
+                "implemented: encoder_module='conformer' with attention_type='RelPosMHAXL' | 'RoPEMHA', causal=False and "
+                "encoder_module='branchformer' with attention_type='RelPosMHAXL' (ASR); encoder_module='transformer' with "
+                "attention_type='regularMHA' (TransformerLM)")
         if positional_encoding == "fixed_abs_sine":
             self.positional_encoding = PositionalEncoding(d_model, max_length)
         if attention_type == "RelPosMHAXL":
@@ -158,6 +168,15 @@ class TransformerInterface(nn.Module):
                                               attention_type=attention_type, kdim=encoder_kdim, vdim=encoder_vdim,
                                               output_hidden_states=output_hidden_states,
                                               layerdrop_prob=layerdrop_prob)
+        elif num_encoder_layers > 0 and branchformer:  # Transformer.py:213-227
+            from speechbrain_amd.lobes.models.transformer.Branchformer import BranchformerEncoder
+
+            self.encoder = BranchformerEncoder(nhead=nhead, num_layers=num_encoder_layers, d_model=d_model, dropout=dropout,
+                                               activation=branchformer_activation, kernel_size=kernel_size,
+                                               attention_type=attention_type, csgu_linear_units=csgu_linear_units,
+                                               gate_activation=gate_activation,
+                                               use_linear_after_conv=use_linear_after_conv,
+                                               output_hidden_states=output_hidden_states, layerdrop_prob=layerdrop_prob)
         elif num_encoder_layers > 0:
             self.encoder = ConformerEncoder(nhead=nhead, num_layers=num_encoder_layers, d_ffn=d_ffn, d_model=d_model,
                                             dropout=dropout, activation=conformer_activation, kernel_size=kernel_size,

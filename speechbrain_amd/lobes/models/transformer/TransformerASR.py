@@ -150,6 +150,8 @@ class TransformerASR(TransformerInterface):
 
     def encode_streaming(self, src, context: TransformerASRStreamingContext):
         """One chunk [B,chunk,F(,C)] -> [B,chunk,d] (TransformerASR.py:546-640); ``context`` is mutated."""
+        if not hasattr(self.encoder, "forward_streaming"):
+            raise NotImplementedError(f"{type(self.encoder).__name__} has no streaming path (the Conformer encoder has)")
         if src.dim() == 4:
             bz, t, ch1, ch2 = src.shape
             src = src.reshape(bz, t, ch1 * ch2)
@@ -168,6 +170,8 @@ class TransformerASR(TransformerInterface):
 
     def make_streaming_context(self, dynchunktrain_config, encoder_kwargs={}):
         """TransformerASR.py:642-670."""
+        if not hasattr(self.encoder, "make_streaming_context"):
+            raise NotImplementedError(f"{type(self.encoder).__name__} has no streaming path (the Conformer encoder has)")
         return TransformerASRStreamingContext(
             dynchunktrain_config=dynchunktrain_config,
             encoder_context=self.encoder.make_streaming_context(dynchunktrain_config, **encoder_kwargs))

@@ -180,6 +180,7 @@ def _declare(lib):
         "sbk_rope_attention_f32": ([p, p, p, p, p, p, i, i, i, i, i, f, i, i, p], c_int),
         "sbk_rope_attention_bf16": ([p, p, p, p, p, i, i, i, i, i, f, i, i, p], c_int),
         "sbk_glu_dwconv_f32": ([p, p, p, p, i, i, i, i, i, p], c_int),
+        "sbk_csgu_f32": ([p, p, p, f, p, p, p, p, i, i, i, i, i, p], c_int),
         "sbk_layernorm_f32": ([p, p, p, p, i, i, f, i, p], c_int),
         "sbk_log_softmax_f32": ([p, p, i, i, f, f, p], c_int),
         "sbk_ctc_greedy_decode_f32": ([p, p, p, p, i, i, i, i, p], c_int),
@@ -1151,6 +1152,29 @@ def glu_dwconv(h, w, bias, ksize, chunk_size=0, out=None):
     y = out if out is not None else torch.empty(B, T, d2 // 2, dtype=torch.float32, device=h.device)
     _chk(lib.sbk_glu_dwconv_f32(_p(h), _p(w), _p(bias), _p(y), B, T, d2 // 2, int(ksize), int(chunk_size), _stream(h)),
          "sbk_glu_dwconv_f32")
+    return y
+
+
+CSGU_KERNEL_SIZES = (3, 5, 7, 15, 31)  # the instantiations of csrc/csgu.hip
+CSGU_GATE_ACTS = (ACT_NONE, ACT_SWISH, ACT_GELU, ACT_RELU)
+
+
+def csgu(h, gamma, beta, eps, w, bias, ksize, gate_act=ACT_NONE, out=None):
+    """Convolutional Spatial Gating Unit: h [B,T,2C] -> gate_act(depthwise_conv_reflect(LayerNorm(h[..., C:]))) * h[..., :C]
+    [B,T,C]; gamma / beta [C], w [C,ksize], bias [C].  The reflect padding needs T > (ksize - 1) / 2."""
+    lib = load()
+    _dev_ok(h, gamma, beta, w, bias, out)
+    _f32(h)
+    B, T, C2 = h.shape
+    ksize, halo = int(ksize), (int(ksize) - 1) // 2
+    if ksize not in CSGU_KERNEL_SIZES:
+        raise SbkError(f"csgu: kernel size {ksize} not instantiated {CSGU_KERNEL_SIZES}")
+    if 0 < T <= halo:  # (F.pad(mode="reflect") refuses a padding that is not smaller than the sequence)
+        raise SbkError(f"csgu: T={T} frames cannot be reflect-padded by {halo} (ksize={ksize} needs T > (ksize-1)/2)")
+    y = out if out is not None else torch.empty(B, T, C2 // 2, dtype=torch.float32, device=h.device)
+    stats = torch.empty(B * T * 2, dtype=torch.float32, device=h.device)
+    _chk(lib.sbk_csgu_f32(_p(h), _p(gamma), _p(beta), float(eps), _p(w), _p(bias), _p(y), _p(stats), B, T, C2 // 2, ksize,
+                          int(gate_act), _stream(h)), "sbk_csgu_f32")
     return y
 
 
