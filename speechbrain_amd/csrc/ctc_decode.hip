@@ -6,6 +6,7 @@
 
 #include "argmax.h"
 #include "common.h"
+#include "device.h"
 
 namespace sbk {
 
@@ -646,7 +647,7 @@ extern "C" int sbk_ctc_beam_search_f32(const float* x, const float* rel_len, con
     return rc;
   hipStream_t st = as_stream(stream);
   const size_t lds = (size_t)4 * cfg->beam_size * sizeof(CtcBeam);
-  if (lds > 64 * 1024 && (int)SBK_ALLOW_DYN_LDS(ctc_beam_kernel, lds) != 0)
+  if (allow_dyn_lds(ctc_beam_kernel, lds) != hipSuccess)
     return fail(SBK_EINVAL, "ctc_beam_search: %zu bytes of LDS for beam_size %d not available", lds, cfg->beam_size);
   ProfScope prof("ctc_beam_search", 0.0, 4.0 * B * T * V + 4.0 * B * T * cfg->beam_size, st);
   SBK_LAUNCH(ctc_beam_kernel, dim3(B), dim3(kCtcThreads), lds, st, a);
@@ -681,7 +682,7 @@ extern "C" int sbk_ctc_beam_search_lm_f32(const float* x, const float* rel_len, 
   l.alpha = lm->alpha, l.beta = lm->beta, l.unk_offset = lm->unk_score_offset, l.log10e = lm->log10_e;
   hipStream_t st = as_stream(stream);
   const size_t lds = (size_t)4 * cfg->beam_size * sizeof(CtcBeamLm);
-  if (lds > 64 * 1024 && (int)SBK_ALLOW_DYN_LDS(ctc_beam_lm_kernel, lds) != 0)
+  if (allow_dyn_lds(ctc_beam_lm_kernel, lds) != hipSuccess)
     return fail(SBK_EINVAL, "ctc_beam_search_lm: %zu bytes of LDS for beam_size %d not available", lds, cfg->beam_size);
   ProfScope prof("ctc_beam_search_lm", 0.0, 4.0 * B * T * V + 4.0 * B * T * cfg->beam_size, st);
   SBK_LAUNCH(ctc_beam_lm_kernel, dim3(B), dim3(kCtcThreads), lds, st, a, l);

@@ -783,7 +783,7 @@ int ctc_psi_step(const float* P, const float* state, const int32_t* last_tok, co
   // utterances beyond ~39 s (T' > 990) need more than the default 64 KiB dynamic-LDS window
 #define SBK_CTC_LAUNCH_NT(NB, TP, NT)                                                                                   \
   do {                                                                                                                  \
-    if (lds > 64 * 1024 && SBK_ALLOW_DYN_LDS((ctc_score_step_kernel<NB, TP, NT>), lds) != hipSuccess)                    \
+    if (allow_dyn_lds(ctc_score_step_kernel<NB, TP, NT>, lds) != hipSuccess)                                            \
       return fail(SBK_EINVAL, "ctc_psi_step: cannot raise the LDS window to %zu B", lds);                               \
     SBK_LAUNCH((ctc_score_step_kernel<NB, TP, NT>), grid, block, lds, st, a, P, (const BF*)v.st, (const float*)v.sg,    \
                (const int*)v.se, psi);                                                                                  \

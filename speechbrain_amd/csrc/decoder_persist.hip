@@ -495,7 +495,7 @@ static int persist_max_grid(const sbk_decoder_weights* W, int Lmax, size_t* lds_
   // agent-scope relaxed accesses + a drained vmcnt as the hand-over between workgroups is outside the HIP memory model: it is
   // what gfx950 does (tools/persist_probe.hip, profiles/r05_a_*), so the path is offered on that architecture only
   if (hipGetDeviceProperties(&prop, dev) == hipSuccess && strncmp(prop.gcnArchName, "gfx950", 6) == 0 &&
-      SBK_ALLOW_DYN_LDS(decoder_step_persist_kernel, 160 * 1024 - 512) == hipSuccess) {
+      allow_dyn_lds(decoder_step_persist_kernel, 160 * 1024 - 512) == hipSuccess) {
     int maxg = 0;
     if (SBK_COOP_MAX_GRID(decoder_step_persist_kernel, 256, lds, maxg) == hipSuccess && maxg >= 1) p.maxg = maxg;
   }

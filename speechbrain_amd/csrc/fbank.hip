@@ -15,6 +15,7 @@
 //   10*log10(max(.,amin)); per-tile max for the per-utterance floor.
 // Kernel 2: floor at (utterance max - top_db) and optional (x-mean)/std.
 #include "common.h"
+#include "device.h"
 
 namespace {
 
@@ -189,7 +190,7 @@ __global__ void __launch_bounds__(256) whisper_floor_kernel(const float* __restr
 
 // The frames kernel takes 72 B of dynamic LDS per FFT point: past the 64 KiB default window from n_fft ~ 800 on.
 int allow_frames_lds(const char* who, size_t lds, int n_fft) {
-  if (lds > 64 * 1024 && (int)SBK_ALLOW_DYN_LDS(fbank_frames_kernel, lds) != 0)
+  if (sbk::allow_dyn_lds(fbank_frames_kernel, lds) != hipSuccess)
     return sbk::fail(SBK_EINVAL, "%s: %zu bytes of LDS for n_fft=%d not available", who, lds, n_fft);
   return 0;
 }

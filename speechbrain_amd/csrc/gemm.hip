@@ -12,8 +12,6 @@
 #include "common.h"
 #include "internal.h"
 
-#include <map>
-#include <mutex>
 #include <type_traits>
 
 namespace {
@@ -1059,10 +1057,6 @@ int g_tiled_splitk = 256;  // tuning knob (key 14): from this many rows on, K >=
 // its last-arriving workgroup (knob 36: 9 815 vs 10 416 audio-s/s, r03_last_arriver_reductions_ab.log -- an agent-scope
 // release is an L2 write-back on an 8-XCD part), 64 x 64 register-operand tiles (knob 11: 29 vs 23 us in situ), the looped
 // skinny schedule of round 1 (knob 10), the wider reach of the register-operand path (knob 12), other K splits (knob 15).)
-int gemm_nt(const float* A, int lda, const float* W, int ldw, const float* bias, const float* R, int ldr, float* C,
-            int ldc, int M, int N, int K, int act, float alpha, const int32_t* seq_len, int rows_per_seq, hipStream_t st);
-int* tile_tickets(hipStream_t st, long tiles);  // this stream's zeroed arrival counters (nullptr: no workspace registered for the stream, or too many tiles)
-int sk_route(int M, int N, int K, int* bt = nullptr);  // workgroups (and tile edge) of the persistent kernel for this shape (0: tile-grid / register-operand paths)
 // Internal C++ entry shared with the fused pipelines (decoder step, encoder).
 // Skinny path: M <= 512 rows, K a multiple of 64, 16-byte aligned rows.  `ws` (optional) holds the
 // split-K partials: SK * M * N floats.
@@ -1157,10 +1151,6 @@ int g_sk_min_rows = 2048;  // tuning knob (key 24): fewer rows than this never t
 // (Knobs 19 / 21 / 22 / 23 / 25 / 26 / 30 / 31 of rounds 3-4 -- grid size, units per workgroup, the measurement builds, the
 // tail-first stagger switch, 64-wide persistent tiles, panel pieces interleaved with the MFMA groups, the split-operand
 // kernel's grid -- are gone: their measured values are the constants below, their logs profiles/r03_*.)
-namespace {
-constexpr int kSkMaxGrid = 512, kSkMaxTiles = 1 << 16;
-int sk_cus();
-}
 // Workgroups of the persistent kernel for this shape, 0 = the tile-grid kernels.  Measured on MI355X (tools/microbench.py
 // --sk, profiles/r03_gemm_persistent_sweep.log): the persistent kernel wins once every workgroup gets about a tile's
 // worth of units (T >= W per XCD keeps the leftover share small); two workgroups per CU from ~500 tiles on, one below;
@@ -1173,7 +1163,7 @@ int sk_route(int M, int N, int K, int* bt) {
   *bt = 128;
   if (!g_sk_mode || K % 32 != 0 || K < 64) return 0;
   const long T = (long)cdiv(M, 128) * cdiv(N, 128), U = T * (K / 32);
-  const int cus = sk_cus();
+  const int cus = device_cus();
   int G = 0;
   if (g_sk_mode == 1 && M < g_sk_min_rows) return 0;  // (decode-step shapes: the register-operand / split-operand few-row kernels)
   if (g_sk_mode == 1) {
@@ -1185,67 +1175,8 @@ int sk_route(int M, int N, int K, int* bt) {
     G = 2 * cus;
     if (U / 4 < G) G = (int)(U / 4);  // short launches: fewer, longer ranges (>= 4 units per workgroup)
   }
-  if (G > kSkMaxGrid) G = kSkMaxGrid;
-  return G >= 8 ? (G / 8) * 8 : 8;  // W workgroups on each of the 8 XCDs
+  return xcd_grid(G > kSkMaxGrid ? kSkMaxGrid : G);  // W workgroups on each of the 8 XCDs
 }
-namespace {
-struct SkWorkspace {
-  float* slabs;
-  int* cnt;
-};
-// Stream workspaces are CALLER-OWNED device memory (sbk_stream_workspace_set, include/sbk.h): the library allocates
-// nothing.  One per (device, stream): launches of one stream are ordered, so they can share the slabs and the tickets.
-std::mutex g_sk_mu;
-std::map<std::pair<int, hipStream_t>, SkWorkspace> g_sk_ws;
-int g_sk_cus[64] = {};
-
-int cur_device() {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  return dev;
-}
-
-// two partial-tile slabs per workgroup: 512 workgroups x 128 x 128 (this file's kernels) or 256 x 256 x 256 (gemm_x3p.hip)
-constexpr size_t kSkSlabBytes = (size_t)2 * 256 * 256 * 256 * sizeof(float);
-static_assert(kSkSlabBytes >= (size_t)2 * kSkMaxGrid * 128 * 128 * sizeof(float), "slab area");
-constexpr size_t kSkTicketBytes = (size_t)kSkMaxTiles * sizeof(int);
-
-// the stream's workspace; false when the caller has registered none for it (the tile-grid kernels run instead)
-bool sk_workspace(hipStream_t st, SkWorkspace* out) {
-  std::lock_guard<std::mutex> lk(g_sk_mu);
-  auto it = g_sk_ws.find(std::make_pair(cur_device(), st));
-  if (it == g_sk_ws.end()) return false;
-  *out = it->second;
-  return true;
-}
-
-}  // namespace
-int* tile_tickets(hipStream_t st, long tiles) {
-  SkWorkspace w;
-  if (tiles > kSkMaxTiles || !sk_workspace(st, &w)) return nullptr;
-  return w.cnt;
-}
-bool stream_ws(hipStream_t st, float** slabs, int** cnt) {  // (gemm_x3p.hip)
-  SkWorkspace w;
-  if (!sk_workspace(st, &w)) return false;
-  *slabs = w.slabs;
-  *cnt = w.cnt;
-  return true;
-}
-namespace {
-
-int sk_cus() {
-  const int dev = cur_device() & 63;
-  if (!g_sk_cus[dev]) {
-    int cus = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    g_sk_cus[dev] = cus > 0 ? cus : 256;
-  }
-  return g_sk_cus[dev];
-}
-
-}  // namespace
-int device_cus() { return sk_cus(); }
 namespace {
 int launch_sk(const GemmArgs& g, int G, int bt, hipStream_t st, bool x3 = false) {
   SkArgs s;
@@ -1254,17 +1185,10 @@ int launch_sk(const GemmArgs& g, int G, int bt, hipStream_t st, bool x3 = false)
   s.tiles = cdiv(g.M, bt) * s.tiles_n;
   s.KT = g.K / 32;
   if (s.tiles > kSkMaxTiles || (long)s.tiles * s.KT > (1L << 30)) return -1;
-  SkWorkspace w;
-  if (!sk_workspace(st, &w)) return -1;
-  s.slabs = w.slabs;
-  s.cnt = w.cnt;
+  if (!stream_ws(st, &s.slabs, &s.cnt)) return -1;
   const size_t lds = x3 ? (size_t)2 * (128 * 32 + 128 * 48) * sizeof(float) : (size_t)(2 * 2 * bt * 32 + 4) * sizeof(float);
-  static bool once = false;
-  if (!once) {
-    (void)SBK_ALLOW_DYN_LDS((gemm_nt_sk_kernel<128, false>), (size_t)(2 * 2 * 128 * 32 + 4) * sizeof(float));
-    (void)SBK_ALLOW_DYN_LDS((gemm_nt_sk_kernel<128, true>), (size_t)2 * (128 * 32 + 128 * 48) * sizeof(float));
-    once = true;
-  }
+  void (*const kernel)(SkArgs) = !x3 ? gemm_nt_sk_kernel<128, false> : gemm_nt_sk_kernel<128, true>;
+  if (const int rc = require_dyn_lds(kernel, lds, "sbk_gemm_nt_f32 (stream-K)")) return rc;
   const double flops = 2.0 * g.M * g.N * g.K, bytes = 4.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N);
   if (x3) {
     // (fp32-equivalent flops: the six bf16 partial products of an element pair count as ONE multiply-add)
@@ -1292,14 +1216,12 @@ int gemm_nt_x3(const float* A, int lda, const uint16_t* W3, const float* bias, c
   GemmArgs g{A, reinterpret_cast<const float*>(W3), bias, R, C, lda, 0, ldr, ldc, M, N, K, act, alpha, seq_len,
              rows_per_seq > 0 ? rows_per_seq : 1};
   const long T = (long)cdiv(M, 128) * cdiv(N, 128), U = T * (K / 32);
-  const int cus = sk_cus();
+  const int cus = device_cus();
   // Measured on MI355X (tools/microbench.py --x3, profiles/r03_f32x3_sweep.log): two workgroups per CU from two tiles per
   // CU on, one below (M = 4 032: N = 1 024 31 vs 50 us, N = 1 536 59 vs 69 us with one)
   int G = T >= 2L * cus ? 2 * cus : cus;
   if (U / 4 < G) G = (int)(U / 4);  // short launches: fewer, longer ranges
-  if (G > kSkMaxGrid) G = kSkMaxGrid;
-  G = G >= 8 ? (G / 8) * 8 : 8;
-  return launch_sk(g, G, 128, st, true);
+  return launch_sk(g, xcd_grid(G > kSkMaxGrid ? kSkMaxGrid : G), 128, st, true);
 }
 
 int gemm_nt(const float* A, int lda, const float* W, int ldw, const float* bias, const float* R, int ldr, float* C,
@@ -1324,29 +1246,6 @@ int gemm_nt(const float* A, int lda, const float* W, int ldw, const float* bias,
   return launch_gemm<32, 64, 32, 32, 32>(g, vec, st);
 }
 }  // namespace sbk
-
-extern "C" size_t sbk_stream_workspace_bytes(void) { return sbk::kSkSlabBytes + sbk::kSkTicketBytes; }
-
-extern "C" int sbk_stream_workspace_set(sbk_stream_t stream, void* workspace, size_t workspace_bytes) {
-  SBK_REQUIRE(workspace && ((uintptr_t)workspace & 255) == 0, "stream workspace: null or not 256-byte aligned");
-  SBK_REQUIRE(workspace_bytes >= sbk_stream_workspace_bytes(), "stream workspace: %zu bytes given, %zu needed", workspace_bytes,
-              sbk_stream_workspace_bytes());
-  hipStream_t st = sbk::as_stream(stream);
-  sbk::SkWorkspace w{reinterpret_cast<float*>(workspace),
-                     reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + sbk::kSkSlabBytes)};
-  // tickets start at zero (ordered before the first launch on this stream); every launch leaves them at zero
-  const hipError_t e = hipMemsetAsync(w.cnt, 0, sbk::kSkTicketBytes, st);
-  if (e != hipSuccess) return sbk::fail((int)e, "stream workspace: memset: %s", hipGetErrorString(e));
-  std::lock_guard<std::mutex> lk(sbk::g_sk_mu);
-  sbk::g_sk_ws[std::make_pair(sbk::cur_device(), st)] = w;
-  return 0;
-}
-
-extern "C" int sbk_stream_workspace_release(sbk_stream_t stream) {
-  std::lock_guard<std::mutex> lk(sbk::g_sk_mu);
-  sbk::g_sk_ws.erase(std::make_pair(sbk::cur_device(), sbk::as_stream(stream)));
-  return 0;
-}
 
 extern "C" int sbk_gemm_nt_f32(const float* A, int lda, const float* W, int ldw, const float* bias,
                                const float* residual, int ldr, float* C, int ldc, int M, int N, int K, int act,

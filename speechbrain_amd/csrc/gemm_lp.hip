@@ -600,33 +600,38 @@ extern "C" int sbk_f32_to_bf16(const float* x, uint16_t* y, long n, sbk_stream_t
 }
 
 namespace {
+// two workgroups per CU, at most one per tile, shared out over the XCDs
+int two_per_cu_grid(int tiles) {
+  const int G = 2 * sbk::device_cus();
+  return sbk::xcd_grid(G > tiles ? tiles : G);
+}
+
 int launch_bf16dma(const Bf16DmaArgs& a0, hipStream_t st) {
   Bf16DmaArgs a = a0;
   a.tiles_n = sbk::cdiv(a.N, 128);
   a.tiles = sbk::cdiv(a.M, 128) * a.tiles_n;
   a.KT = a.K / 64;
-  int dev = 0, cus = 0;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (cus <= 0) cus = 256;
   // Measured on MI355X (tools/microbench.py --bf16a, profiles/r03_bf16_activation_gemm.log): two stages and two
   // workgroups per CU (634-827 TF/s at 12 000 rows) beat three / four stages with one (460-630): a second workgroup's
   // MFMAs cover the ~100-cycle issue of each LDS-DMA piece better than a deeper pipeline of one wave per SIMD does
   // (three / four stages with one workgroup per CU were the knobs 27 / 28 of rounds 3-4; removed with their instantiations)
-  int G = 2 * cus;
-  if (G > a.tiles) G = a.tiles;
-  G = G >= 8 ? (G / 8) * 8 : 8;
+  const int G = two_per_cu_grid(a.tiles);
   const size_t lds = (size_t)2 * 2 * 128 * 32 * sizeof(float);
-  static bool once = false;
-  if (!once) {
-    (void)SBK_ALLOW_DYN_LDS(gemm_nt_bf16dma_kernel<2>, lds);
-    once = true;
-  }
-  sbk::ProfScope prof("gemm_nt_bf16a", 2.0 * a.M * a.N * a.K,
-                      2.0 * ((double)a.M * a.K + (double)a.N * a.K) + (a.C ? 4.0 : 0.0) * a.M * a.N + (a.Cb ? 2.0 : 0.0) * a.M * a.N +
-                          (a.R ? 4.0 : 0.0) * a.M * a.N, st);
+  if (const int rc = sbk::require_dyn_lds(gemm_nt_bf16dma_kernel<2>, lds, "sbk_gemm_nt_bf16a")) return rc;
   SBK_LAUNCH(gemm_nt_bf16dma_kernel<2>, dim3((unsigned)G), dim3(256), lds, st, a);
   return sbk::launch_status("sbk_gemm_nt_bf16a");
+}
+
+int launch_fp8dma(const Fp8DmaArgs& a0, hipStream_t st) {  // two stages, two workgroups per CU (launch_bf16dma's measured choice)
+  Fp8DmaArgs a = a0;
+  a.tiles_n = sbk::cdiv(a.N, 128);
+  a.tiles = sbk::cdiv(a.M, 128) * a.tiles_n;
+  a.KT = a.K / 128;
+  const int G = two_per_cu_grid(a.tiles);
+  const size_t lds = (size_t)2 * 2 * 128 * 32 * sizeof(float);
+  if (const int rc = sbk::require_dyn_lds(gemm_nt_fp8dma_kernel, lds, "sbk_gemm_nt_fp8a")) return rc;
+  SBK_LAUNCH(gemm_nt_fp8dma_kernel, dim3((unsigned)G), dim3(256), lds, st, a);
+  return sbk::launch_status("sbk_gemm_nt_fp8a");
 }
 
 int launch_lp(int dt, const float* A, int lda, const void* Wq, int ldw, const float* bias, const float* residual, int ldr,
@@ -654,19 +659,26 @@ int launch_lp(int dt, const float* A, int lda, const void* Wq, int ldw, const fl
 #undef SBK_LP
   return sbk::launch_status(name);
 }
+
+// the argument checks of sbk_gemm_nt_bf16 / _f16 / _fp8 (kq: the elements of W in 16 bytes -- K and ldw are multiples of it)
+int require_lp(const char* who, bool operands, int kq, const float* A, int lda, const void* W, int ldw, const float* residual, int ldr,
+               int ldc, int M, int N, int K, int act, const int32_t* seq_len, int rows_per_seq) {
+  SBK_REQUIRE(operands, "%s: null operand", who);
+  SBK_REQUIRE(M >= 0 && N >= 0 && K > 0 && K % kq == 0, "%s: bad shape M=%d N=%d K=%d (K must be a multiple of %d)", who, M, N, K, kq);
+  SBK_REQUIRE(lda > 0 && ldw >= K && ldc >= N && lda % 4 == 0 && ldw % kq == 0, "%s: leading dimensions", who);
+  SBK_REQUIRE(sbk::aligned16(A) && sbk::aligned16(W), "%s: operands must be 16-byte aligned", who);
+  SBK_REQUIRE(!residual || ldr >= N, "%s: residual stride", who);
+  SBK_REQUIRE(act >= SBK_ACT_NONE && act <= SBK_ACT_LEAKY_RELU, "%s: unknown activation %d", who, act);
+  SBK_REQUIRE(!seq_len || rows_per_seq > 0, "%s: seq_len given without rows_per_seq", who);
+  return 0;
+}
 }  // namespace
 
 extern "C" int sbk_gemm_nt_bf16(const float* A, int lda, const uint16_t* Wb, int ldw, const float* bias,
                                 const float* residual, int ldr, float* C, int ldc, int M, int N, int K, int act,
                                 float alpha, const int32_t* seq_len, int rows_per_seq, sbk_stream_t stream) {
   if (M == 0 || N == 0) return 0;
-  SBK_REQUIRE(A && Wb && C, "gemm_bf16: null operand");
-  SBK_REQUIRE(M >= 0 && N >= 0 && K > 0 && K % 8 == 0, "gemm_bf16: bad shape M=%d N=%d K=%d (K must be a multiple of 8)", M, N, K);
-  SBK_REQUIRE(lda > 0 && ldw >= K && ldc >= N && lda % 4 == 0 && ldw % 8 == 0, "gemm_bf16: leading dimensions");
-  SBK_REQUIRE(sbk::aligned16(A) && sbk::aligned16(Wb), "gemm_bf16: operands must be 16-byte aligned");
-  SBK_REQUIRE(!residual || ldr >= N, "gemm_bf16: residual stride");
-  SBK_REQUIRE(act >= SBK_ACT_NONE && act <= SBK_ACT_LEAKY_RELU, "gemm_bf16: unknown activation %d", act);
-  SBK_REQUIRE(!seq_len || rows_per_seq > 0, "gemm_bf16: seq_len given without rows_per_seq");
+  if (const int rc = require_lp("gemm_bf16", A && Wb && C, 8, A, lda, Wb, ldw, residual, ldr, ldc, M, N, K, act, seq_len, rows_per_seq)) return rc;
   return launch_lp(0, A, lda, Wb, ldw, bias, residual, ldr, C, ldc, M, N, K, act, alpha, seq_len, rows_per_seq, nullptr, 1.0f,
                    sbk::as_stream(stream));
 }
@@ -681,18 +693,14 @@ extern "C" int sbk_gemm_nt_bf16a(const uint16_t* A, int lda, const uint16_t* Wb,
               "gemm_bf16a: operand rows must be 16-byte aligned (lda=%d ldw=%d)", lda, ldw);
   SBK_REQUIRE((!C || ldc >= N) && (!Cb || ldcb >= N) && (!residual || ldr >= N), "gemm_bf16a: leading dimension smaller than the row");
   SBK_REQUIRE(act >= SBK_ACT_NONE && act <= SBK_ACT_LEAKY_RELU, "gemm_bf16a: unknown activation %d", act);
-  {  // the large shapes: 256 x 256 tiles (csrc/gemm_lp256.hip), the same sums in the same order
-    const sbk::Lp256Args a{reinterpret_cast<const unsigned char*>(A), reinterpret_cast<const unsigned char*>(Wb), nullptr, nullptr, bias,
+  hipStream_t st = sbk::as_stream(stream);
+  sbk::ProfScope prof("gemm_nt_bf16a", 2.0 * M * (double)N * K,
+                      2.0 * ((double)M * K + (double)N * K) + ((C ? 4.0 : 0.0) + (Cb ? 2.0 : 0.0) + (residual ? 4.0 : 0.0)) * M * (double)N, st);
+  // the large shapes: 256 x 256 tiles (csrc/gemm_lp256.hip), the same sums in the same order
+  const sbk::Lp256Args big{reinterpret_cast<const unsigned char*>(A), reinterpret_cast<const unsigned char*>(Wb), nullptr, nullptr, bias,
                            residual, C, Cb, nullptr, 1.0f, 2L * lda, 2L * ldw, ldr, ldc, ldcb, 0, M, N, act, alpha, K / 64, 0, 0, 0, 0};
-    if (sbk::lp256_routed(a)) {
-      hipStream_t st = sbk::as_stream(stream);
-      sbk::ProfScope prof("gemm_nt_bf16a", 2.0 * M * (double)N * K,
-                          2.0 * ((double)M * K + (double)N * K) + ((C ? 4.0 : 0.0) + (Cb ? 2.0 : 0.0) + (residual ? 4.0 : 0.0)) * M * (double)N, st);
-      return sbk::gemm_nt_lp256(a, false, st);
-    }
-  }
-  Bf16DmaArgs a{A, Wb, bias, residual, C, Cb, lda, ldw, ldr, ldc, ldcb, M, N, K, act, alpha, 0, 0, 0};
-  return launch_bf16dma(a, sbk::as_stream(stream));
+  if (sbk::lp256_routed(big)) return sbk::gemm_nt_lp256(big, false, st);
+  return launch_bf16dma(Bf16DmaArgs{A, Wb, bias, residual, C, Cb, lda, ldw, ldr, ldc, ldcb, M, N, K, act, alpha, 0, 0, 0}, st);
 }
 
 extern "C" int sbk_gemm_nt_fp8a(const uint8_t* A8, int lda, const float* a_scale, const uint8_t* W8, int ldw, const float* w_scale,
@@ -707,52 +715,22 @@ extern "C" int sbk_gemm_nt_fp8a(const uint8_t* A8, int lda, const float* a_scale
   SBK_REQUIRE((!C || ldc >= N) && (!Cb || ldcb >= N) && (!C8 || (ldc8 >= N && c8_scale > 0.0f)) && (!residual || ldr >= N),
               "gemm_fp8a: leading dimension smaller than the row / non-positive fp8 output scale");
   SBK_REQUIRE(act >= SBK_ACT_NONE && act <= SBK_ACT_LEAKY_RELU, "gemm_fp8a: unknown activation %d", act);
-  {  // the large shapes: 256 x 256 tiles (csrc/gemm_lp256.hip), the same sums in the same order
-    const sbk::Lp256Args a{A8, W8, a_scale, w_scale, bias, residual, C, Cb, C8, C8 ? c8_scale : 1.0f, (long)lda, (long)ldw, ldr, ldc, ldcb, ldc8,
-                           M, N, act, alpha, K / 128, 0, 0, 0, 0};
-    if (sbk::lp256_routed(a)) {
-      hipStream_t st = sbk::as_stream(stream);
-      sbk::ProfScope prof("gemm_nt_fp8a", 2.0 * M * (double)N * K,
-                          1.0 * ((double)M * K + (double)N * K) + ((C ? 4.0 : 0.0) + (Cb ? 2.0 : 0.0) + (C8 ? 1.0 : 0.0) + (residual ? 4.0 : 0.0)) * M * (double)N, st);
-      return sbk::gemm_nt_lp256(a, true, st);
-    }
-  }
-  Fp8DmaArgs a{A8, W8, a_scale, w_scale, bias, residual, C, Cb, C8, C8 ? c8_scale : 1.0f, lda, ldw, ldr, ldc, ldcb, ldc8,
-               M, N, K, act, alpha, 0, 0, 0};
-  a.tiles_n = sbk::cdiv(N, 128);
-  a.tiles = sbk::cdiv(M, 128) * a.tiles_n;
-  a.KT = K / 128;
-  int dev = 0, cus = 0;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (cus <= 0) cus = 256;
-  int G = 2 * cus;  // two stages, two workgroups per CU (launch_bf16dma's measured choice)
-  if (G > a.tiles) G = a.tiles;
-  G = G >= 8 ? (G / 8) * 8 : 8;
-  const size_t lds = (size_t)2 * 2 * 128 * 32 * sizeof(float);
-  static bool once = false;
-  if (!once) {
-    (void)SBK_ALLOW_DYN_LDS(gemm_nt_fp8dma_kernel, lds);
-    once = true;
-  }
   hipStream_t st = sbk::as_stream(stream);
   sbk::ProfScope prof("gemm_nt_fp8a", 2.0 * M * (double)N * K,
                       1.0 * ((double)M * K + (double)N * K) + ((C ? 4.0 : 0.0) + (Cb ? 2.0 : 0.0) + (C8 ? 1.0 : 0.0) + (residual ? 4.0 : 0.0)) * M * (double)N, st);
-  SBK_LAUNCH(gemm_nt_fp8dma_kernel, dim3((unsigned)G), dim3(256), lds, st, a);
-  return sbk::launch_status("sbk_gemm_nt_fp8a");
+  // the large shapes: 256 x 256 tiles (csrc/gemm_lp256.hip), the same sums in the same order
+  const sbk::Lp256Args big{A8, W8, a_scale, w_scale, bias, residual, C, Cb, C8, C8 ? c8_scale : 1.0f, (long)lda, (long)ldw, ldr, ldc, ldcb, ldc8,
+                           M, N, act, alpha, K / 128, 0, 0, 0, 0};
+  if (sbk::lp256_routed(big)) return sbk::gemm_nt_lp256(big, true, st);
+  return launch_fp8dma(Fp8DmaArgs{A8, W8, a_scale, w_scale, bias, residual, C, Cb, C8, C8 ? c8_scale : 1.0f, lda, ldw, ldr, ldc, ldcb, ldc8,
+                                  M, N, K, act, alpha, 0, 0, 0}, st);
 }
 
 extern "C" int sbk_gemm_nt_f16(const float* A, int lda, const uint16_t* Wh, int ldw, const float* bias,
                                const float* residual, int ldr, float* C, int ldc, int M, int N, int K, int act,
                                float alpha, const int32_t* seq_len, int rows_per_seq, sbk_stream_t stream) {
   if (M == 0 || N == 0) return 0;
-  SBK_REQUIRE(A && Wh && C, "gemm_f16: null operand");
-  SBK_REQUIRE(M >= 0 && N >= 0 && K > 0 && K % 8 == 0, "gemm_f16: bad shape M=%d N=%d K=%d (K must be a multiple of 8)", M, N, K);
-  SBK_REQUIRE(lda > 0 && ldw >= K && ldc >= N && lda % 4 == 0 && ldw % 8 == 0, "gemm_f16: leading dimensions");
-  SBK_REQUIRE(sbk::aligned16(A) && sbk::aligned16(Wh), "gemm_f16: operands must be 16-byte aligned");
-  SBK_REQUIRE(!residual || ldr >= N, "gemm_f16: residual stride");
-  SBK_REQUIRE(act >= SBK_ACT_NONE && act <= SBK_ACT_LEAKY_RELU, "gemm_f16: unknown activation %d", act);
-  SBK_REQUIRE(!seq_len || rows_per_seq > 0, "gemm_f16: seq_len given without rows_per_seq");
+  if (const int rc = require_lp("gemm_f16", A && Wh && C, 8, A, lda, Wh, ldw, residual, ldr, ldc, M, N, K, act, seq_len, rows_per_seq)) return rc;
   return launch_lp(1, A, lda, Wh, ldw, bias, residual, ldr, C, ldc, M, N, K, act, alpha, seq_len, rows_per_seq, nullptr, 1.0f,
                    sbk::as_stream(stream));
 }
@@ -761,13 +739,8 @@ extern "C" int sbk_gemm_nt_fp8(const float* A, int lda, const float* a_absmax, c
                                const float* bias, const float* residual, int ldr, float* C, int ldc, int M, int N, int K,
                                int act, float alpha, const int32_t* seq_len, int rows_per_seq, sbk_stream_t stream) {
   if (M == 0 || N == 0) return 0;
-  SBK_REQUIRE(A && Wq && C && a_absmax, "gemm_fp8: null operand");
-  SBK_REQUIRE(M >= 0 && N >= 0 && K > 0 && K % 16 == 0, "gemm_fp8: bad shape M=%d N=%d K=%d (K must be a multiple of 16)", M, N, K);
-  SBK_REQUIRE(lda > 0 && ldw >= K && ldc >= N && lda % 4 == 0 && ldw % 16 == 0, "gemm_fp8: leading dimensions");
-  SBK_REQUIRE(sbk::aligned16(A) && sbk::aligned16(Wq), "gemm_fp8: operands must be 16-byte aligned");
-  SBK_REQUIRE(!residual || ldr >= N, "gemm_fp8: residual stride");
-  SBK_REQUIRE(act >= SBK_ACT_NONE && act <= SBK_ACT_LEAKY_RELU, "gemm_fp8: unknown activation %d", act);
-  SBK_REQUIRE(!seq_len || rows_per_seq > 0, "gemm_fp8: seq_len given without rows_per_seq");
+  if (const int rc = require_lp("gemm_fp8", A && Wq && C && a_absmax, 16, A, lda, Wq, ldw, residual, ldr, ldc, M, N, K, act, seq_len, rows_per_seq))
+    return rc;
   SBK_REQUIRE(w_scale > 0.0f, "gemm_fp8: w_scale must be positive");
   return launch_lp(2, A, lda, Wq, ldw, bias, residual, ldr, C, ldc, M, N, K, act, alpha, seq_len, rows_per_seq, a_absmax, w_scale,
                    sbk::as_stream(stream));

@@ -35,7 +35,6 @@
 using sbk::f32x16;
 
 namespace sbk {
-int device_cus();
 int g_lp256 = 1;  // key 61: 1 (default) = shapes with >= 128 (96: fp32 result + residual) tiles of 256 x 256 take this kernel, 0 = never, 2 = always (tests)
 }  // namespace sbk
 
@@ -359,22 +358,11 @@ int launch_lp256(const sbk::Lp256Args& a0, hipStream_t st) {
   a.tiles_m = sbk::cdiv(a.M, 256);
   a.tiles_n = sbk::cdiv(a.N, 256);
   a.tiles = a.tiles_m * a.tiles_n;
-  const int cus = sbk::device_cus();
-  int G;
-  if (a.tiles <= cus) {  // one tile per workgroup
-    a.whole = 1;
-    G = a.tiles;
-  } else {
-    a.whole = 0;
-    G = (cus / 8) * 8;
-  }
-  static bool once = false;
-  if (!once) {
-    (void)SBK_ALLOW_DYN_LDS((gemm_nt_lp256_kernel<FP8, ACT>), kLdsBytes);
-    once = true;
-  }
+  const int G = sbk::whole_tile_grid(a.tiles, sbk::device_cus(), &a.whole);
+  const char* who = FP8 ? "sbk_gemm_nt_fp8a" : "sbk_gemm_nt_bf16a";
+  if (const int rc = sbk::require_dyn_lds(gemm_nt_lp256_kernel<FP8, ACT>, kLdsBytes, who)) return rc;
   SBK_LAUNCH((gemm_nt_lp256_kernel<FP8, ACT>), dim3((unsigned)G), dim3(512), kLdsBytes, st, a);
-  return sbk::launch_status(FP8 ? "sbk_gemm_nt_fp8a" : "sbk_gemm_nt_bf16a");
+  return sbk::launch_status(who);
 }
 
 }  // namespace

@@ -40,9 +40,6 @@ using sbk::f32x16;
 
 namespace sbk {
 int g_x3p_fast_epi = 1;  // key 63
-// csrc/gemm.hip: the caller-registered stream workspace (slabs of kX3pSlabFloats floats each, tile tickets)
-bool stream_ws(hipStream_t st, float** slabs, int** cnt);
-int device_cus();
 }  // namespace sbk
 
 namespace {
@@ -569,22 +566,10 @@ int launch_x3p(const X3pArgs& a0, hipStream_t st) {
   a.tiles_n = cdiv(a.N, BN);
   a.tiles = cdiv(a.M, BM) * a.tiles_n;
   a.KT = a.K / 16;
-  const int cus = sbk::device_cus();
-  int G;
-  if (a.tiles <= cus) {  // one whole tile per workgroup
-    a.whole = 1;
-    G = a.tiles;
-  } else {
-    a.whole = 0;
-    G = (cus / 8) * 8;
-    if (!sbk::stream_ws(st, &a.slabs, &a.cnt)) return -1;
-    if (a.tiles > (1 << 16)) return -1;
-  }
-  static bool once = false;
-  if (!once) {
-    (void)SBK_ALLOW_DYN_LDS((gemm_nt_x3p_kernel<WM, WN, TM, TN>), lds);
-    once = true;
-  }
+  const int G = sbk::whole_tile_grid(a.tiles, sbk::device_cus(), &a.whole);
+  // shared tiles: the stream workspace's slabs (two of BM x BN floats per workgroup) and tile tickets
+  if (!a.whole && (!sbk::stream_ws(st, &a.slabs, &a.cnt) || a.tiles > sbk::kSkMaxTiles)) return -1;
+  if (const int rc = sbk::require_dyn_lds(gemm_nt_x3p_kernel<WM, WN, TM, TN>, lds, "sbk_gemm_nt_x3p")) return rc;
   SBK_LAUNCH((gemm_nt_x3p_kernel<WM, WN, TM, TN>), dim3((unsigned)G), dim3(512), lds, st, a);
   return sbk::launch_status("sbk_gemm_nt_x3p");
 }

@@ -126,8 +126,8 @@ __device__ __forceinline__ float exp2_raw(float x) { return __builtin_amdgcn_exp
 __device__ __forceinline__ bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0; }
 // GELU (erf form) for the epilogues of the REDUCED-PRECISION contractions (bf16 / e4m3 activations: csrc/gemm_lp.hip, gemm_lp256.hip;
 // the fp32 parity path keeps libm's erff).  1 + erf(x / sqrt 2) = 2 - erfc(z) for x >= 0 and erfc(z) for x < 0, z = |x| / sqrt 2, with
-// erfc by Abramowitz & Stegun 7.1.26 (absolute error <= 1.5e-7: below half an ulp of the bf16 / e4m3 value it is rounded to, and the
-// negative tail keeps its RELATIVE accuracy because erfc is formed directly, not as 1 - erf) on one v_rcp_f32 and one v_exp_f32: about 17
+// erfc by Abramowitz & Stegun 7.1.26 (absolute error <= 4.2e-7 against fp64 erfc as evaluated here -- 1.5e-7 of it is the polynomial
+// term, the rest the approximate v_rcp_f32 / v_exp_f32 --: below half an ulp of the bf16 / e4m3 value it is rounded to, and the negative tail keeps its RELATIVE accuracy because erfc is formed directly, not as 1 - erf) on one v_rcp_f32 and one v_exp_f32: about 17
 // instructions where libm's erff is ~35 with both of its branches taken in a wave -- the first feed-forward projection of a Whisper
 // large-v3 layer evaluates it 61 M times per launch (54 of its 146 us, profiles/r06_ad_*).
 // Compiled under `fp contract(off)` with its fused operations written out: two kernels that must agree bit for bit (the 128 x 128 and
@@ -368,20 +368,21 @@ __device__ __forceinline__ float wave_max(float v) {
 #define SBK_INLINE_LAMBDA __attribute__((always_inline))
 #define SBK_DYN_LDS(type, name) extern __shared__ __attribute__((aligned(16))) type name[]
 
-// Raise a kernel's dynamic-LDS window above the 64 KiB default (gfx950 has 160 KiB per CU).
-#define SBK_ALLOW_DYN_LDS(kernel, bytes) \
-  hipFuncSetAttribute(reinterpret_cast<const void*>(&kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes))
+// Raise a kernel's dynamic-LDS window above the 64 KiB default (gfx950 has 160 KiB per CU).  kernel_ptr: the kernel's address as
+// a const void*.  Launchers go through sbk::allow_dyn_lds (csrc/device.h), which asks once per device and kernel.
+#define SBK_ALLOW_DYN_LDS(kernel_ptr, bytes) \
+  hipFuncSetAttribute(kernel_ptr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes))
 
 // Cooperative launch (every workgroup resident at once: the kernel may use sbk::grid_barrier): ONE by-value argument struct;
-// evaluates to the hipError_t of the launch.  SBK_COOP_MAX_GRID: the largest grid the device can hold for this kernel.
+// evaluates to the hipError_t of the launch.  SBK_COOP_MAX_GRID: the largest grid the device can hold for this kernel
+// (host code that has seen csrc/device.h: the CU count is sbk::device_cus()).
 #define SBK_LAUNCH_COOP(kernel, grid, block, lds_bytes, stream, arg_struct) \
   ([&]() -> hipError_t { void* p__[] = {(void*)&(arg_struct)};               \
     return hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&kernel), grid, block, p__, lds_bytes, stream); }())
 #define SBK_COOP_MAX_GRID(kernel, block_threads, lds_bytes, out_int)                                                   \
-  ([&]() -> hipError_t { int dev__ = 0, cus__ = 0, per__ = 0; hipError_t e__ = hipGetDevice(&dev__);                    \
-    if (e__ == hipSuccess) e__ = hipDeviceGetAttribute(&cus__, hipDeviceAttributeMultiprocessorCount, dev__);         \
-    if (e__ == hipSuccess) e__ = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per__, kernel, block_threads, lds_bytes); \
-    (out_int) = cus__ * per__; return e__; }())
+  ([&]() -> hipError_t { int per__ = 0;                                                                                  \
+    const hipError_t e__ = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per__, kernel, block_threads, lds_bytes);      \
+    (out_int) = sbk::device_cus() * per__; return e__; }())
 
 // kernel<<<grid, block, lds_bytes, stream>>>(args...)
 #define SBK_LAUNCH(kernel, grid, block, lds_bytes, stream, ...) \

@@ -919,10 +919,7 @@ int launch_attn_pf(const AttnArgs& a, hipStream_t st) {
   constexpr int NCt = (DH + 31) / 32;
   const size_t lds = ((size_t)2 * 32 * (DH + 1) + (NW - NCt) * 32 * 33 + (size_t)32 * a.SP) * sizeof(float);
   if (lds > 160 * 1024) return sbk::fail(SBK_EINVAL, "relpos_attention: T=%d needs %zu B of LDS (max 160 KiB)", a.T, lds);
-  if (lds > 64 * 1024) {
-    hipError_t e = SBK_ALLOW_DYN_LDS((relpos_attn_kernel<DH, ROPE, PF, NW>), lds);
-    if (e != hipSuccess) return sbk::fail((int)e, "relpos_attention: cannot raise the LDS window to %zu B", lds);
-  }
+  if (const int rc = sbk::require_dyn_lds(relpos_attn_kernel<DH, ROPE, PF, NW>, lds, "relpos_attention")) return rc;
   sbk::ProfScope prof(ROPE ? "rope_attention" : "relpos_attention", (ROPE ? 4.0 : 6.0) * a.B * a.H * (double)a.T * a.T * DH,
                       4.0 * a.B * a.T * (4.0 * a.H * DH) + 4.0 * (2.0 * a.T - 1) * a.H * DH, st);
   SBK_LAUNCH((relpos_attn_kernel<DH, ROPE, PF, NW>), dim3((a.T + 31) / 32, a.H, a.B), dim3(NW * 64), lds, st, a);

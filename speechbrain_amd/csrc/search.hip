@@ -74,37 +74,6 @@ thread_local AsyncPoll g_poll;
 }  // namespace
 
 namespace sbk {
-// decoder.hip / ctc_prefix.hip
-int embed_pos(const int32_t* tok, const float* emb, const float* pe_row, float* x, int n, int d, float scale,
-              hipStream_t st);
-int self_attn_step(const float* qkv, float* kcache, float* vcache, const int32_t* kv_slot, float* out, int n, int d,
-                   int H, int step, int nslot, int Lmax, hipStream_t st, const int32_t* key_tok = nullptr,
-                   int key_stride = 0, int key_shift = 0, int key_first = 0, int pad_idx = 0, int group = 1);
-int cross_attn_step(const float* q, const float* kv, const int32_t* enc_len, float* out, float* part, int B, int T,
-                    int d, int H, int beam, hipStream_t st);
-size_t cross_attn_partial_floats(int B, int T, int H, int Dh, int beam);
-int log_softmax_rows(const float* x, float* out, int rows, int V, float temperature, float weight, hipStream_t st,
-                     const float* bias = nullptr, const float* bias2 = nullptr, int ld = 0);
-int ctc_prepare(float* x, float* xb_log, const int32_t* enc_len, float* state, float* psi_prev, int B, int T, int V,
-                int beam, int blank, hipStream_t st, int ldp = 0);
-size_t ctc_state_floats(int B, int beam, int T);
-int ctc_psi_step(const float* P, const float* state, const int32_t* last_tok, const int32_t* enc_len, float* psi, int B,
-                 int T, int V, int beam, int prefix_len, int blank, int eos, hipStream_t st, const int32_t* win = nullptr,
-                 int window = 0, int ldp = 0);
-int cross_attn_avg_probs(const float* q, const float* kv, const int32_t* enc_len, float* out, int n, int T, int d, int H,
-                         int beam, hipStream_t st);
-int ctc_combine(const float* am, const float* am_max, const float* psi, const float* psi_prev, float* comb, int n_bh,
-                int V, int blank, int eos, float weight, int eos_floor, int use_thr, float thr, float minus_inf,
-                const float* extra, hipStream_t st, const int32_t* utt_min = nullptr, int beam = 1, int step = 0);
-int ctc_advance(const float* x, const float* phi_old, const float* psi, const int32_t* parent, const int32_t* token,
-                const int32_t* parent_last_tok, float* phi_new, float* psi_prev_new, int n_bh, int T, int V, int beam,
-                int prefix_len, int blank, hipStream_t st, const int32_t* win = nullptr, int window = 0, int ldp = 0);
-int am_only(const float* am, float* comb, int n_bh, int V, int eos, int eos_floor, int use_thr, float thr,
-            float minus_inf, const float* am_max, const float* extra, hipStream_t st, const int32_t* utt_min = nullptr,
-            int beam = 1, int step = 0);
-int row_max(const float* x, float* out, int rows, int V, hipStream_t st);
-int ctc_partial_combine(float* comb, float* thr, const float* psi, const float* psi_prev, int n_bh, int V, int k, int blank,
-                        int eos, float weight, float minus_inf, hipStream_t st);
 int g_score_fused = 1;  // tuning knob (key 40): 0 = log_softmax / row_max / combine / top-k stage 1 as separate launches
 }  // namespace sbk
 

@@ -9,6 +9,7 @@
 
 #include "argmax.h"
 #include "common.h"
+#include "device.h"
 
 namespace sbk {
 
@@ -694,7 +695,7 @@ extern "C" int sbk_transducer_greedy_f32(const sbk_transducer_weights* W, const 
   a.B = B, a.T = T, a.F = F, a.S = cfg->max_symbols_per_step, a.blank = cfg->blank, a.act = cfg->act;
   a.start = cfg->start_from_blank ? 1 : 0;
   hipStream_t st = as_stream(stream);
-  if (lds > 64 * 1024 && (int)SBK_ALLOW_DYN_LDS(transducer_greedy_kernel, lds) != 0)
+  if (allow_dyn_lds(transducer_greedy_kernel, lds) != hipSuccess)
     return fail(SBK_EINVAL, "transducer_greedy: %zu bytes of LDS not available", lds);
   const double G = 4.0 * W->hidden;
   ProfScope prof("transducer_greedy", 0.0, 4.0 * B * T * W->joint + 4.0 * (double)W->joint * W->vocab * B * cdiv(T, F) +
@@ -833,7 +834,7 @@ extern "C" int sbk_transducer_beam_search_f32(const sbk_transducer_weights* W, c
   a.cap_a = (int)z.cap_a, a.n_slots = (int)z.n_slots, a.slot_floats = (int)z.slot_floats, a.node_cap = (int)z.node_cap;
   a.state_beam = cfg->state_beam, a.expand_beam = cfg->expand_beam;
   hipStream_t st = as_stream(stream);
-  if (z.lds > 64 * 1024 && (int)SBK_ALLOW_DYN_LDS(transducer_beam_kernel<false>, z.lds) != 0)
+  if (allow_dyn_lds(transducer_beam_kernel<false>, z.lds) != hipSuccess)
     return fail(SBK_EINVAL, "transducer_beam_search: %zu bytes of LDS not available", z.lds);
   ProfScope prof("transducer_beam", 0.0, 4.0 * B * T * W->joint + 4.0 * (double)W->joint * W->vocab * B * T, st);
   SBK_LAUNCH(transducer_beam_kernel<false>, dim3(B), dim3(kTdThreads), z.lds, st, a);
@@ -886,7 +887,7 @@ extern "C" int sbk_transducer_beam_search_lm_f32(const sbk_transducer_weights* W
   a.state_beam = cfg->state_beam, a.expand_beam = cfg->expand_beam;
   a.lm = *LM, a.lm_weight = lm_weight, a.gmax = (int)z.gmax;
   hipStream_t st = as_stream(stream);
-  if (z.lds > 64 * 1024 && (int)SBK_ALLOW_DYN_LDS(transducer_beam_kernel<true>, z.lds) != 0)
+  if (allow_dyn_lds(transducer_beam_kernel<true>, z.lds) != hipSuccess)
     return fail(SBK_EINVAL, "transducer_beam_search_lm: %zu bytes of LDS not available", z.lds);
   ProfScope prof("transducer_beam_lm", 0.0, 4.0 * B * T * W->joint + 4.0 * (double)W->joint * W->vocab * B * T, st);
   SBK_LAUNCH(transducer_beam_kernel<true>, dim3(B), dim3(kTdThreads), z.lds, st, a);
@@ -900,7 +901,7 @@ extern "C" int sbk_lstm_f32(const float* xp, const float* w_hh, const float* b_i
   const size_t lds = sizeof(float) * 10 * (size_t)H;
   SBK_REQUIRE(lds <= kTdLdsMax, "lstm: hidden size %d too large", H);  // (lstm_layer_kernel has no static LDS)
   hipStream_t st = as_stream(stream);
-  if (lds > 64 * 1024 && (int)SBK_ALLOW_DYN_LDS(lstm_layer_kernel, lds) != 0)
+  if (allow_dyn_lds(lstm_layer_kernel, lds) != hipSuccess)
     return fail(SBK_EINVAL, "lstm: %zu bytes of LDS not available", lds);
   ProfScope prof("lstm", 2.0 * B * T * 4.0 * H * H, 4.0 * B * T * 5.0 * H + 16.0 * H * H * B, st);
   SBK_LAUNCH(lstm_layer_kernel, dim3(B), dim3(kTdThreads), lds, st, xp, w_hh, b_ih, b_hh, h, c, out, T, H);

@@ -958,6 +958,65 @@ def test_no_stream_workspace_is_an_error_not_an_allocation(backend):
     assert _md(out, (a.double().cpu() @ w.double().cpu().t()).float()) <= 2e-6 * float((a.abs().double().cpu() @ w.abs().double().cpu().t()).max()) + 1e-5
 
 
+_CONCURRENT_FIRST_CALLS = """
+import threading
+import torch
+from speechbrain_amd import native as nat
+
+nat.load()
+dev, n = torch.device("cuda:0"), 8
+g = torch.Generator().manual_seed(3)
+rnd = lambda *s: torch.randn(*s, generator=g).to(dev)
+ab, wb = rnd(256, 128).bfloat16(), rnd(256, 128)  # sbk_gemm_nt_bf16a on 256 x 256 tiles (lp256 = 2; K tiles: 2), 128 KiB of LDS
+ax, wx = rnd(256, 32), rnd(128, 32)               # sbk_gemm_nt_x3p, one whole tile, 108 KiB
+af, wf = rnd(128, 64), rnd(128, 64)               # the stream-K fp32 kernel (sk_mode = 2), 64 KiB + 16 B
+nat.lp_weight(wb, "bf16"), nat.lp_weight(wx, "x3p")  # (weight images: plain conversion kernels, no LDS window to raise)
+torch.cuda.synchronize()
+paths = [lambda: nat.gemm_nt_bf16a(ab, wb), lambda: nat.gemm_nt_x3p(nat.split_x3p(ax), wx), lambda: nat.gemm_nt(af, wf)]
+gate, got, errors = threading.Barrier(n), [None] * n, []
+
+
+def worker(i):
+    try:
+        stream = torch.cuda.Stream(dev)
+        with torch.cuda.stream(stream):
+            nat._stream(ab)  # registers this stream's workspace
+            gate.wait()
+            out = [paths[(i + j) % 3]() for j in range(3)]  # (a failed call raises SbkError)
+            stream.synchronize()
+        got[i] = {(i + j) % 3: o.cpu() for j, o in enumerate(out)}
+    except BaseException as e:
+        gate.abort()
+        errors.append(repr(e))
+
+
+with nat.knobs(lp256=2, sk_mode=2):
+    threads = [threading.Thread(target=worker, args=(i,)) for i in range(n)]
+    [t.start() for t in threads]
+    [t.join() for t in threads]
+    assert not errors, errors
+    want = [p().cpu() for p in paths]
+for i in range(n):
+    for k in range(3):
+        assert torch.equal(got[i][k], want[k]), (i, k)
+print("ok")
+"""
+
+
+@pytest.mark.gpu
+def test_concurrent_first_calls_raise_the_lds_window():
+    """csrc/device.cpp: the dynamic-LDS window of a kernel is raised once per (device, kernel), under a lock.  In a fresh process
+    (true first calls) eight threads, each on a stream of its own with a registered workspace, are released together into their
+    first calls of the three contractions that need more than the default 64 KiB: every call succeeds, and every thread's results
+    equal, bit for bit, the same three calls made afterwards from one thread."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, "-c", _CONCURRENT_FIRST_CALLS], cwd=root, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stdout.strip() == "ok", out.stderr[-2000:]
+
+
 @pytest.mark.parametrize("rows,d,act", [(130, 512, 0), (64, 32, 1), (777, 144, 0), (300, 1024, 1), (129, 2048, 0), (5, 16, 0),
                                         (4100, 512, 1), (4097, 1024, 0)])
 def test_layernorm_x3p(backend, rows, d, act):
