@@ -52,10 +52,7 @@ class TransducerBeamSearcher(torch.nn.Module):
             self.searcher = self.transducer_greedy_decode
         else:
             self.searcher = self.transducer_beam_search_decode
-        self._prepared = None
-        self._prepared_key = None
-        self._lm_prepared = None
-        self._lm_prepared_key = None
+        self._prepared, self._lm_prepared = native.Derived(), native.Derived()
 
     def forward(self, tn_output):
         return self.searcher(tn_output)
@@ -157,15 +154,15 @@ class TransducerBeamSearcher(torch.nn.Module):
     def _prepare_lm(self, device):
         """The LM's weight layouts on ``device``, by the key rule of _prepare."""
         emb, lstm, blocks, out, act = self._lm_networks()
-        params = [p for p in self.lm.parameters()]
-        key = (device, act) + tuple((p.data_ptr(), p._version, p.device) for p in params) + tuple(ln.eps for _, ln in blocks)
-        if self._lm_prepared is None or key != self._lm_prepared_key:
-            d = lambda t: None if t is None else t.detach().to(device)  # noqa: E731
+        d = lambda t: None if t is None else t.detach().to(device)  # noqa: E731
+
+        def build():
             layers = [tuple(d(t) for t in layer) for layer in lstm.layer_weights()]
             dnn = [(d(lin.w.weight), d(lin.w.bias), d(ln.norm.weight), d(ln.norm.bias), ln.eps) for lin, ln in blocks]
-            self._lm_prepared = native.RNNLMPrepared(d(emb.Embedding.weight), layers, dnn, d(out.w.weight), d(out.w.bias), act)
-            self._lm_prepared_key = key
-        return self._lm_prepared
+            return native.RNNLMPrepared(d(emb.Embedding.weight), layers, dnn, d(out.w.weight), d(out.w.bias), act)
+
+        return self._lm_prepared.get(list(self.lm.parameters()), build, device=device,
+                                     extra=(device, act) + tuple(ln.eps for _, ln in blocks))
 
     def _prepare(self, device, beam=False):
         """The kernel's weight layouts on ``device``, rebuilt when a parameter changes (the PN and classifier modules are
@@ -174,14 +171,14 @@ class TransducerBeamSearcher(torch.nn.Module):
         emb, lstm, proj, lin = self._networks(beam)
         params = [emb.Embedding.weight] + [p for p in lstm.parameters()] + [p for p in proj.parameters()] + [
             p for p in lin.parameters()]
-        key = (device,) + tuple((p.data_ptr(), p._version, p.device) for p in params)
-        if self._prepared is None or key != self._prepared_key:
-            d = lambda t: None if t is None else t.detach().to(device)  # noqa: E731
+        d = lambda t: None if t is None else t.detach().to(device)  # noqa: E731
+
+        def build():
             layers = [tuple(d(t) for t in layer) for layer in lstm.layer_weights()]
-            self._prepared = native.TransducerPrepared(d(emb.Embedding.weight), layers, d(proj.w.weight), d(proj.w.bias),
-                                                       d(lin.w.weight), d(lin.w.bias))
-            self._prepared_key = key
-        return self._prepared
+            return native.TransducerPrepared(d(emb.Embedding.weight), layers, d(proj.w.weight), d(proj.w.bias), d(lin.w.weight),
+                                             d(lin.w.bias))
+
+        return self._prepared.get(params, build, device=device, extra=(device,))
 
     # ------------------------------------------------------------------ greedy search
     def transducer_greedy_decode(self, tn_output, hidden_state=None, return_hidden=False, max_symbols_per_step=5,

@@ -120,29 +120,24 @@ class _Attention(nn.Module):
         self.v_proj = nn.Linear(d, d)
         self.q_proj = nn.Linear(d, d)
         self.out_proj = nn.Linear(d, d)
+        self._stack_derived = native.Derived()
 
     def stacked(self, interleave_heads):
         """(in_proj weight [3d,d], bias [3d]) of the three projections, cached until a parameter changes.
         interleave_heads: rows ordered [head][q|k|v][head_dim] (what the encoder attention kernel reads in place);
         otherwise [q|k|v][d] (torch.nn.MultiheadAttention's in_proj layout, read by the decoder kernels)."""
+        def build():
+            zero = torch.zeros_like(self.q_proj.bias)
+            w = torch.stack([self.q_proj.weight, self.k_proj.weight, self.v_proj.weight])       # [3,d,d]
+            b = torch.stack([self.q_proj.bias, zero, self.v_proj.bias])                          # [3,d]
+            if interleave_heads:
+                H, Dh, d = self.num_heads, self.head_dim, self.embed_dim
+                w = w.view(3, H, Dh, d).permute(1, 0, 2, 3)
+                b = b.view(3, H, Dh).permute(1, 0, 2)
+            return w.reshape(3 * self.embed_dim, self.embed_dim).contiguous(), b.reshape(-1).contiguous()
+
         ps = (self.q_proj.weight, self.q_proj.bias, self.k_proj.weight, self.v_proj.weight, self.v_proj.bias)
-        key = (interleave_heads,) + tuple((p.data_ptr(), p._version) for p in ps)
-        if getattr(self, "_stack_key", None) != key:
-            with torch.no_grad():
-                zero = torch.zeros_like(self.q_proj.bias)
-                w = torch.stack([self.q_proj.weight, self.k_proj.weight, self.v_proj.weight])       # [3,d,d]
-                b = torch.stack([self.q_proj.bias, zero, self.v_proj.bias])                          # [3,d]
-                if interleave_heads:
-                    H, Dh, d = self.num_heads, self.head_dim, self.embed_dim
-                    w = w.view(3, H, Dh, d).permute(1, 0, 2, 3)
-                    b = b.view(3, H, Dh).permute(1, 0, 2)
-                self._stack = (w.reshape(3 * self.embed_dim, self.embed_dim).contiguous(), b.reshape(-1).contiguous())
-            # (built by kernels on THIS thread's stream; a batch in flight on another stream may ask for it a moment later:
-            # the consumer waits for the producer's event on the device, as for every derived weight image -- ADVICE r3)
-            self._stack_ready = native._Ready(self.q_proj.weight.device)
-            self._stack_key = key
-        self._stack_ready.wait(self.q_proj.weight.device)
-        return self._stack
+        return self._stack_derived.get(ps, build, extra=(interleave_heads,))
 
 
 class _EncoderLayer(nn.Module):
@@ -183,6 +178,7 @@ class WhisperEncoder(nn.Module):
         self.num_mel_bins, self.max_source_positions = cfg["num_mel_bins"], cfg["max_source_positions"]
         self.conv1 = nn.Conv1d(self.num_mel_bins, d, kernel_size=3, padding=1)
         self.conv2 = nn.Conv1d(d, d, kernel_size=3, stride=2, padding=1)
+        self.conv1.gemm_w, self.conv2.gemm_w = native.Derived(), native.Derived()  # (_conv_weight)
         self.embed_positions = nn.Embedding(self.max_source_positions, d)
         self.layers = nn.ModuleList([_EncoderLayer(d, cfg["encoder_attention_heads"], cfg["encoder_ffn_dim"])
                                      for _ in range(cfg["encoder_layers"])])
@@ -190,14 +186,8 @@ class WhisperEncoder(nn.Module):
 
     def _conv_weight(self, conv):
         """[out, in, 3] -> [out, 3*in] with the tap as the slow index: one row of the strided window."""
-        key = (conv.weight.data_ptr(), conv.weight._version)
-        if getattr(conv, "_gemm_key", None) != key:
-            with torch.no_grad():
-                conv._gemm_w = conv.weight.permute(0, 2, 1).reshape(conv.weight.shape[0], -1).contiguous()
-            conv._gemm_ready = native._Ready(conv.weight.device)  # (see _Attention.stacked)
-            conv._gemm_key = key
-        conv._gemm_ready.wait(conv.weight.device)
-        return conv._gemm_w
+        w = conv.weight
+        return conv.gemm_w.get((w,), lambda: w.permute(0, 2, 1).reshape(w.shape[0], -1).contiguous())
 
     def forward(self, input_features, output_hidden_states=False):
         """input_features [B, n_mels, 2 * max_source_positions] -> last hidden state [B, max_source_positions, d]
@@ -424,7 +414,7 @@ class Whisper(WhisperLogMel):
         dec = self.model.decoder
         if dec is None:
             raise RuntimeError("this Whisper was built with encoder_only=True")
-        key = tuple((p.data_ptr(), p._version) for p in dec.parameters())
+        key = native.source_key(dec.parameters())
         h = getattr(self, "_dec_handle", None)
         if h is None or h.key != key:
             layers = []

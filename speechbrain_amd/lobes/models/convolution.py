@@ -84,7 +84,7 @@ class ConvBlock(torch.nn.Module):
         self.convs["norm_0"] = LayerNorm(input_shape=self.out_shape)
         self.convs["act_0"] = activation()
         self.convs["dropout_0"] = torch.nn.Dropout(dropout)
-        self._wt_cache = None
+        self._wt_derived = native.Derived()
 
     def get_filter_properties(self):
         """convolution.py:283-320: one 3-wide stride-2 layer per block."""
@@ -94,11 +94,8 @@ class ConvBlock(torch.nn.Module):
 
     def _wt(self):
         w = self.convs["conv_0"].conv.weight
-        key = (w.data_ptr(), w._version, w.device)
-        if self._wt_cache is None or self._wt_cache[0] != key:
-            # [Cout,Cin,kF,kT] -> [(ci,kf,kt), Cout]: coalesced across output channels in the kernel
-            self._wt_cache = (key, w.detach().permute(1, 2, 3, 0).reshape(-1, w.shape[0]).contiguous())
-        return self._wt_cache[1]
+        # [Cout,Cin,kF,kT] -> [(ci,kf,kt), Cout]: coalesced across output channels in the kernel
+        return self._wt_derived.get((w,), lambda: w.detach().permute(1, 2, 3, 0).reshape(-1, w.shape[0]).contiguous())
 
     def forward(self, x):
         if x.dim() == 3:

@@ -68,16 +68,12 @@ class BranchformerEncoderLayer(nn.Module):
         self.norm_conv = LayerNorm(d_model)
         self.dropout = nn.Dropout(dropout)
         self.collect_attention = False  # attention maps are opt-in (they are [B,H,T,T] of HBM traffic)
-        self._merge_cache = None
+        self._merge_derived = native.Derived()
 
     def _merge_halves(self):
         """merge_proj.weight [d,2d] as its two column halves, contiguous: the contraction over cat[x1, x2] is x1 Wa^T + x2 Wb^T."""
-        w = self.merge_proj.weight
-        key = (w.data_ptr(), w._version, w.device)
-        if self._merge_cache is None or self._merge_cache[0] != key:
-            d = w.shape[0]
-            self._merge_cache = (key, w.detach()[:, :d].contiguous(), w.detach()[:, d:].contiguous())
-        return self._merge_cache[1], self._merge_cache[2]
+        w, d = self.merge_proj.weight, self.merge_proj.weight.shape[0]
+        return self._merge_derived.get((w,), lambda: (w.detach()[:, :d].contiguous(), w.detach()[:, d:].contiguous()))
 
     def _merge(self, x, x1, x2):
         wa, wb = self._merge_halves()

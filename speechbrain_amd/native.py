@@ -7,6 +7,7 @@ CPU fallback: a CPU tensor, or a missing library, raises.
 
 from __future__ import annotations
 
+import collections
 import contextlib
 import ctypes
 import os
@@ -303,11 +304,36 @@ _STREAM_WS_LOCK = threading.RLock()
 _STREAM_WS_REFS = {}
 
 
+def _ws_key(stream):
+    """(id(lib), device index | "host", handle): the _STREAM_WS key of a torch.cuda.Stream, or (None) of the emulator's NULL one."""
+    return (id(load()), stream.device.index, stream.cuda_stream) if stream is not None else (id(load()), "host", 0)
+
+
 def retain_stream_workspace(stream):
     """Declare an owner of the (device, handle) of ``stream`` (a ConcurrentTranscriber for each of its worker streams)."""
-    key = (id(load()), stream.device.index, stream.cuda_stream)
+    key = _ws_key(stream)
     with _STREAM_WS_LOCK:
         _STREAM_WS_REFS[key] = _STREAM_WS_REFS.get(key, 0) + 1
+
+
+class _Workspace:
+    """An aligned workspace of exactly ``nbytes`` for one library call: ``ptr`` is the address the entry gets, ``buf`` the uint8
+    tensor that owns it, ``off`` the aligned start inside ``buf``.  A fresh allocation of max(nbytes, floor) + align bytes, or
+    -- ``per_stream`` -- the grow-only search buffer of the current stream (_search_workspace), held for the ``with`` block."""
+    __slots__ = ("buf", "off", "ptr", "key")
+
+    def __init__(self, nbytes, device, align=256, floor=0, per_stream=False):
+        size = max(nbytes, floor) + align
+        self.buf, self.key = (_search_workspace(size, device) if per_stream
+                              else (torch.empty(size, dtype=torch.uint8, device=device), None))
+        self.off = (-self.buf.data_ptr()) % align
+        self.ptr = c_void_p(self.buf.data_ptr() + self.off)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        _search_workspace_done(self.key)
 
 
 def _register_workspace(key, device, handle):
@@ -316,12 +342,11 @@ def _register_workspace(key, device, handle):
         if key in _STREAM_WS:
             return
         nbytes = lib.sbk_stream_workspace_bytes()
-        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-        off = (-ws.data_ptr()) % 256
+        ws = _Workspace(nbytes, device)
         # the library keys its table on hipGetDevice(): make the tensor's device the current one for the call
         ctx = torch.cuda.device(device) if getattr(device, "type", None) == "cuda" else contextlib.nullcontext()
         with ctx:
-            _chk(lib.sbk_stream_workspace_set(c_void_p(handle) if handle is not None else None, c_void_p(ws.data_ptr() + off), nbytes),
+            _chk(lib.sbk_stream_workspace_set(c_void_p(handle) if handle is not None else None, ws.ptr, nbytes),
                  "sbk_stream_workspace_set")
         _STREAM_WS[key] = ws
 
@@ -329,7 +354,7 @@ def _register_workspace(key, device, handle):
 def forget_stream_owner(stream):
     """An owner of ``stream`` went away WITHOUT releasing (a transcriber dropped without ``close()``): its claim is withdrawn, the
     workspace stays registered -- the handle's next owner releases it, or it lives as long as the process (one per pooled handle)."""
-    key = (id(load()), stream.device.index, stream.cuda_stream)
+    key = _ws_key(stream)
     with _STREAM_WS_LOCK:
         left = _STREAM_WS_REFS.get(key, 0) - 1
         if left > 0:
@@ -343,7 +368,7 @@ def release_stream_workspace(stream) -> bool:
     ConcurrentTranscriber that is being closed): sbk_stream_workspace_release, then the ~134 MB return to torch's allocator once
     the stream has drained.  Streams that never issued an op have none (False)."""
     lib = load()
-    key = (id(lib), stream.device.index, stream.cuda_stream)
+    key = _ws_key(stream)
     with _STREAM_WS_LOCK:
         left = _STREAM_WS_REFS.get(key, 0) - 1
         if left > 0:  # another live owner of the same pooled handle: it keeps the workspace
@@ -365,17 +390,12 @@ def release_stream_workspace(stream) -> bool:
 
 
 def _stream(t: torch.Tensor):
-    lib = load()
-    if t.is_cuda:
-        h = torch.cuda.current_stream(t.device).cuda_stream
-        key = (id(lib), t.device.index, h)
-        if key not in _STREAM_WS:
-            _register_workspace(key, t.device, h)
-        return c_void_p(h)
-    key = (id(lib), "host", 0)  # (host tensors only reach a kernel under the test emulator: its one "stream" is NULL)
+    # (host tensors only reach a kernel under the test emulator: its one "stream" is NULL)
+    cur = torch.cuda.current_stream(t.device) if t.is_cuda else None
+    key = _ws_key(cur)
     if key not in _STREAM_WS:
-        _register_workspace(key, t.device, None)
-    return None
+        _register_workspace(key, t.device, cur.cuda_stream if cur is not None else None)
+    return c_void_p(cur.cuda_stream) if cur is not None else None
 
 
 def _f32(t):
@@ -421,13 +441,18 @@ X3R = os.environ.get("SBK_X3R", "1") != "0"
 X3P_MIN_TILES = int(os.environ.get("SBK_X3P_MIN_TILES", "96"))
 
 
+def _x3_shape(N: int, K: int) -> bool:
+    """Weights [N, K] that have an "x3" image (sbk_split_bf16x3: 32-deep K groups, rows moved four at a time)."""
+    return K % 32 == 0 and K >= 64 and N % 4 == 0
+
+
 def f32x3_ok(M: int, K: int, w: torch.Tensor) -> bool:
     """Shapes routed to sbk_gemm_nt_f32x3.  Measured on MI355X (tools/microbench.py --x3, profiles/r03_f32x3_sweep.log):
     from ~0.75 tiles of 128 x 128 per CU on the split-operand kernel wins (M = 8 000, N = 512: 38.9 vs 43.2 us); below, the
     fp32-MFMA tile kernels do (M = 4 032, N = 512: 25.4 vs 30.6 us)."""
-    if not (F32X3 and M >= F32X3_MIN_ROWS and K % 32 == 0 and K >= 64 and w.dim() == 2 and w.is_contiguous()):
+    if not (F32X3 and M >= F32X3_MIN_ROWS and w.dim() == 2 and w.is_contiguous() and _x3_shape(w.shape[0], K)):
         return False
-    return w.shape[0] % 4 == 0 and ((M + 127) // 128) * ((w.shape[0] + 127) // 128) >= F32X3_MIN_TILES
+    return ((M + 127) // 128) * ((w.shape[0] + 127) // 128) >= F32X3_MIN_TILES
 
 
 def _aligned16(*ts) -> bool:
@@ -436,6 +461,13 @@ def _aligned16(*ts) -> bool:
 
 
 # ------------------------------------------------------------------ ops
+def _rows(a, w, residual=None):
+    """The GEMM wrappers' view of their operands: (a as rows [M, K], residual as rows [M, N] or None, M, N, K)."""
+    K, N = a.shape[-1], w.shape[0]
+    a2 = a.reshape(-1, K)
+    return a2, (residual.reshape(-1, N) if residual is not None else None), a2.shape[0], N, K
+
+
 def gemm_nt(a: torch.Tensor, w: torch.Tensor, bias=None, residual=None, act=ACT_NONE, alpha=1.0, out=None,
             seq_len=None, rows_per_seq=0):
     """out[M,N] = residual + alpha * act(a[M,K] @ w[N,K]^T + bias).  `a` may have leading dims.
@@ -445,16 +477,13 @@ def gemm_nt(a: torch.Tensor, w: torch.Tensor, bias=None, residual=None, act=ACT_
     lib = load()
     if isinstance(a, Panel):  # the producer wrote the operand's panel image (layernorm_x3p, gemm_nt_x3p(panel_out=True))
         return gemm_nt_x3p(a, w, bias, residual, act, alpha, out=out, seq_len=seq_len, rows_per_seq=rows_per_seq)
-    K = a.shape[-1]
-    a2 = a.reshape(-1, K)
-    M, N = a2.shape[0], w.shape[0]
+    a2, r2, M, N, K = _rows(a, w, residual)
     if precision() != "fp32" and M >= 256 and K % (16 if precision() == "fp8" else 8) == 0 and w.is_contiguous():
         return gemm_nt_bf16(a, w, bias, residual, act, alpha, seq_len, rows_per_seq, out=out, kind=precision())  # opt-in fast path
     _dev_ok(a2, w, bias, residual)
     _f32(a2), _f32(w)
     if out is None:
         out = torch.empty(*a.shape[:-1], N, dtype=torch.float32, device=a.device)
-    r2 = residual.reshape(-1, N) if residual is not None else None
     _dev_ok(seq_len)
     if x3p_ok(M, K, w) and _aligned16(a2, out, bias, r2):  # both operands pre-split, 256-wide tiles (csrc/gemm_x3p.hip)
         return gemm_nt_x3p(split_x3p(a2), w, bias, r2, act, alpha, out=out, seq_len=seq_len, rows_per_seq=rows_per_seq)
@@ -615,13 +644,10 @@ def gemm_nt_x3r(a: torch.Tensor, w: torch.Tensor, bias=None, residual=None, act=
     """out[M,N] = residual + alpha * act(a @ w^T + bias) for FEW rows (a decoding step's projections) on the bf16 matrix
     pipe (sbk_gemm_nt_x3r): ``a`` fp32 (split in registers), ``w`` is used through its cached panel image."""
     lib = load()
-    K = a.shape[-1]
-    a2 = a.reshape(-1, K)
-    M, N = a2.shape[0], w.shape[0]
+    a2, r2, M, N, K = _rows(a, w, residual)
     _dev_ok(a2, w, bias, residual)
     _f32(a2)
     out = torch.empty(*a.shape[:-1], N, dtype=torch.float32, device=a.device)
-    r2 = residual.reshape(-1, N) if residual is not None else None
     _chk(lib.sbk_gemm_nt_x3r(_p(a2), K, _p(lp_weight(w, "x3p")), _p(bias), _p(r2), N, _p(out), N, M, N, K, act, float(alpha),
                              _stream(w)), "sbk_gemm_nt_x3r")
     return out
@@ -632,13 +658,10 @@ def gemm_ln_nt_x3r(a: torch.Tensor, wf: torch.Tensor, bf, eps, residual=None, ac
     prologue (sbk_gemm_ln_nt_x3r): gamma / beta pre-folded into (wf, bf) as for ``gemm_ln_nt``; ``wf`` is used through its
     cached panel image.  K = 256, 512, 1024 or 1280."""
     lib = load()
-    K = a.shape[-1]
-    a2 = a.reshape(-1, K)
-    M, N = a2.shape[0], wf.shape[0]
+    a2, r2, M, N, K = _rows(a, wf, residual)
     _dev_ok(a2, wf, bf, residual)
     _f32(a2)
     out = torch.empty(*a.shape[:-1], N, dtype=torch.float32, device=a.device)
-    r2 = residual.reshape(-1, N) if residual is not None else None
     _chk(lib.sbk_gemm_ln_nt_x3r(_p(a2), K, _p(lp_weight(wf, "x3p")), _p(bf), _p(r2), N, _p(out), N, M, N, K,
                                 float(eps), act, float(alpha), _stream(wf)), "sbk_gemm_ln_nt_x3r")
     return out
@@ -671,31 +694,56 @@ class _Ready:
             cur.wait_event(ev)
 
 
-_BF16_WEIGHTS = {}  # (id(base tensor), kind, view geometry) -> (weakref to the base, _version, image, scale, _Ready, data_ptr)
+def source_key(sources, extra=()):
+    """The validity key of what is derived from the tensors ``sources``: ``extra`` + (data_ptr, _version, device) of each.  An
+    in-place update (load_state_dict, copy_) bumps _version; ``param.data = other`` (nn.Module._apply) changes data_ptr."""
+    return tuple(extra) + tuple((t.data_ptr(), t._version, t.device) for t in sources if t is not None)
+
+
+_DERIVED_LOCK = threading.RLock()  # (re-entrant, as _BF16_LOCK below: a build allocates, and may build another Derived)
+_Hit = collections.namedtuple("_Hit", "key value ready device")  # (what a Derived holds; ready: the producer's _Ready)
+
+
+class Derived:
+    """One value derived from parameter tensors (a permuted / stacked / folded copy, a TransducerPrepared), owned by the module
+    that uses it and shared by its shallow copies (the per-worker searchers of a ConcurrentTranscriber): built once per
+    ``source_key``, by one thread, and handed to the other streams through its producer's event (_Ready)."""
+    __slots__ = ("_hit",)
+
+    def __init__(self):
+        self._hit = None  # (a _Hit, published as one object: a hit takes no lock)
+
+    def __deepcopy__(self, memo):
+        return Derived()
+
+    def get(self, sources, build, device=None, extra=()):
+        """The value ``build()`` returned for these ``sources`` (parameter tensors, None entries skipped) and ``extra``; built
+        under torch.no_grad() on a miss.  ``device``: where the value lives (default: the first source's)."""
+        key = source_key(sources, extra)
+        hit = self._hit
+        if hit is None or hit.key != key:
+            with _DERIVED_LOCK:
+                hit = self._hit
+                if hit is None or hit.key != key:
+                    self._hit = None  # (a build that raises leaves nothing behind)
+                    device = device if device is not None else next(t for t in sources if t is not None).device
+                    with torch.no_grad():
+                        value = build()
+                    hit = self._hit = _Hit(key, value, _Ready(device), device)
+        hit.ready.wait(hit.device)  # (made on another worker's stream a moment ago?)
+        return hit.value
+
+
+# (an entry of _BF16_WEIGHTS; ref: weak reference to the base tensor; scale: "fp8" float, "fp8r" tensor [N], else None)
+_Image = collections.namedtuple("_Image", "ref version image scale ready data_ptr")
+_BF16_WEIGHTS = {}  # (id(base tensor), kind, view geometry) -> _Image
 # re-entrant: the weak-reference callback below takes the lock too, and a cyclic-GC pass started by an allocation INSIDE a
 # locked region may run it on the thread that already holds the lock (ADVICE r3)
 _BF16_LOCK = threading.RLock()
 
 
-def lp_weight(w: torch.Tensor, kind: str = "bf16"):
-    """The reduced-precision image of a weight matrix ("bf16" / "fp16": int16 bits; "fp8": (uint8 e4m3 bits, w_scale);
-    "x3": the exact three-piece bf16 split [N, K/32, 3, 32] of sbk_split_bf16x3 -- not reduced: the pieces sum to w),
-    cached for the lifetime of THAT tensor object: the entry holds a weak reference to its source and is used only while
-    ``ref() is w`` and the version counter is unchanged (a freed model's addresses are commonly handed to the next
-    model of the same shapes by the caching allocator, and load_state_dict leaves ``_version`` alike -- a (data_ptr,
-    version, shape) key would then serve the OLD model's weights).  Entries die with their tensor (weakref callback);
-    insert / evict under a lock (worker threads)."""
-    # a VIEW of a parameter (conv weight [2d,d,1] reshaped to [2d,d], a slice of a stacked projection) is a new tensor object
-    # on every call: the entry belongs to the view's base and the view's geometry, so the image is made once
-    base = w._base if w._base is not None else w
-    key = (id(base), kind, w.storage_offset(), tuple(w.shape), tuple(w.stride()))
-    with _BF16_LOCK:
-        hit = _BF16_WEIGHTS.get(key)
-        # (data_ptr: `param.data = other` -- nn.Module._apply, a manual weight swap -- keeps the object and its version)
-        if (hit is not None and hit[0]() is base and hit[1] == w._version and hit[2].device == w.device
-                and hit[5] == w.data_ptr()):
-            hit[4].wait(w.device)  # (made on another worker's stream a moment ago?)
-            return hit[2] if kind not in ("fp8", "fp8r") else (hit[2], hit[3])
+def _make_image(w: torch.Tensor, kind: str):
+    """(image, scale) of the fp32 matrix ``w`` for ``kind`` (see lp_weight), written on the current stream."""
     lib = load()
     w2 = w.detach().contiguous()
     _dev_ok(w2)
@@ -721,15 +769,38 @@ def lp_weight(w: torch.Tensor, kind: str = "bf16"):
         out = torch.empty(w2.shape, dtype=torch.int16, device=w.device)
         fn = lib.sbk_f32_to_bf16 if kind == "bf16" else lib.sbk_f32_to_f16
         _chk(fn(_p(w2), _p(out), w2.numel(), _stream(w2)), "sbk_f32_to_" + kind)
+    return out, scale
+
+
+def lp_weight(w: torch.Tensor, kind: str = "bf16"):
+    """The reduced-precision image of a weight matrix ("bf16" / "fp16": int16 bits; "fp8": (uint8 e4m3 bits, w_scale);
+    "x3": the exact three-piece bf16 split [N, K/32, 3, 32] of sbk_split_bf16x3 -- not reduced: the pieces sum to w),
+    cached for the lifetime of THAT tensor object: the entry holds a weak reference to its source and is used only while
+    ``ref() is w`` and the version counter is unchanged (a freed model's addresses are commonly handed to the next
+    model of the same shapes by the caching allocator, and load_state_dict leaves ``_version`` alike -- a (data_ptr,
+    version, shape) key would then serve the OLD model's weights).  Entries die with their tensor (weakref callback);
+    insert / evict under a lock (worker threads)."""
+    # a VIEW of a parameter (conv weight [2d,d,1] reshaped to [2d,d], a slice of a stacked projection) is a new tensor object
+    # on every call: the entry belongs to the view's base and the view's geometry, so the image is made once
+    base = w._base if w._base is not None else w
+    key = (id(base), kind, w.storage_offset(), tuple(w.shape), tuple(w.stride()))
+    with _BF16_LOCK:
+        hit = _BF16_WEIGHTS.get(key)
+        # (data_ptr: `param.data = other` -- nn.Module._apply, a manual weight swap -- keeps the object and its version)
+        if (hit is not None and hit.ref() is base and hit.version == w._version and hit.image.device == w.device
+                and hit.data_ptr == w.data_ptr()):
+            hit.ready.wait(w.device)  # (made on another worker's stream a moment ago?)
+            return hit.image if kind not in ("fp8", "fp8r") else (hit.image, hit.scale)
+    out, scale = _make_image(w, kind)
 
     def _drop(_ref, key=key):
         with _BF16_LOCK:
             cur = _BF16_WEIGHTS.get(key)
-            if cur is not None and cur[0] is _ref:
+            if cur is not None and cur.ref is _ref:
                 del _BF16_WEIGHTS[key]
 
     with _BF16_LOCK:
-        _BF16_WEIGHTS[key] = (weakref.ref(base, _drop), w._version, out, scale, _Ready(w.device), w.data_ptr())
+        _BF16_WEIGHTS[key] = _Image(weakref.ref(base, _drop), w._version, out, scale, _Ready(w.device), w.data_ptr())
     return out if kind not in ("fp8", "fp8r") else (out, scale)
 
 
@@ -748,13 +819,11 @@ def gemm_nt_bf16(a: torch.Tensor, w: torch.Tensor, bias=None, residual=None, act
         with precision_scope("fp32"):
             return gemm_nt(a, w, bias, residual, act, alpha, out=out, seq_len=seq_len, rows_per_seq=rows_per_seq)
     lib = load()
-    a2 = a.reshape(-1, K)
-    M, N = a2.shape[0], w.shape[0]
+    a2, r2, M, N, K = _rows(a, w, residual)
     _dev_ok(a2, bias, residual, seq_len)
     _f32(a2)
     if out is None:
         out = torch.empty(*a.shape[:-1], N, dtype=torch.float32, device=a.device)
-    r2 = residual.reshape(-1, N) if residual is not None else None
     if kind == "fp8":
         wq, w_scale = lp_weight(w, "fp8")
         amax = torch.empty(1, dtype=torch.float32, device=a.device)
@@ -791,15 +860,12 @@ def gemm_nt_bf16a(a: torch.Tensor, w: torch.Tensor, bias=None, residual=None, ac
     fp32 accumulation, fp32 residual; the result is fp32 or -- ``out_dtype=torch.bfloat16`` -- the next contraction's
     bf16 operand."""
     lib = load()
-    K = a.shape[-1]
-    a2 = a.reshape(-1, K)
-    M, N = a2.shape[0], w.shape[0]
+    a2, r2, M, N, K = _rows(a, w, residual)
     _dev_ok(a2, bias, residual)
     if a2.dtype != torch.bfloat16 or not a2.is_contiguous():
         raise SbkError("gemm_nt_bf16a: the activation operand must be a contiguous torch.bfloat16 tensor")
     wb = lp_weight(w, "bf16")
     out = torch.empty(*a.shape[:-1], N, dtype=out_dtype, device=a.device)
-    r2 = residual.reshape(-1, N) if residual is not None else None
     c32, cb = (out, None) if out_dtype == torch.float32 else (None, out)
     _chk(lib.sbk_gemm_nt_bf16a(_p(a2), K, _p(wb), K, _p(bias), _p(r2), N, _p(c32), N, _p(cb), N, M, N, K, act,
                                float(alpha), _stream(a2)), "sbk_gemm_nt_bf16a")
@@ -877,12 +943,9 @@ def gemm_nt_fp8a(a: Fp8Rows, w: torch.Tensor, bias=None, residual=None, act=ACT_
     fp32, torch.bfloat16 (the attention kernel's operand) or -- ``out_dtype="fp8"`` -- e4m3 at scale 1 (an Fp8Rows
     without scales: the hidden layer of a feed-forward pair)."""
     lib = load()
-    K = a.q.shape[-1]
-    a2 = a.q.reshape(-1, K)
-    M, N = a2.shape[0], w.shape[0]
+    a2, r2, M, N, K = _rows(a.q, w, residual)
     _dev_ok(a2, a.scale, bias, residual)
     wq, w_scale = lp_weight(w, "fp8r")
-    r2 = residual.reshape(-1, N) if residual is not None else None
     lead = tuple(a.q.shape[:-1])
     c = cb = c8 = None
     if out_dtype == "fp8":
@@ -901,13 +964,10 @@ def gemm_nt_fp8a(a: Fp8Rows, w: torch.Tensor, bias=None, residual=None, act=ACT_
 def gemm_nt_splitk(a, w, bias=None, residual=None, act=ACT_NONE, alpha=1.0, slices=8):
     """gemm_nt for few-row operands with a caller-provided split-K workspace."""
     lib = load()
-    K = a.shape[-1]
-    a2 = a.reshape(-1, K)
-    M, N = a2.shape[0], w.shape[0]
+    a2, r2, M, N, K = _rows(a, w, residual)
     _dev_ok(a2, w, bias, residual)
     out = torch.empty(*a.shape[:-1], N, dtype=torch.float32, device=a.device)
     ws = torch.empty(max(1, slices * M * N), dtype=torch.float32, device=a.device)
-    r2 = residual.reshape(-1, N) if residual is not None else None
     _chk(lib.sbk_gemm_nt_splitk_f32(_p(a2), K, _p(w), w.stride(0), _p(bias), _p(r2), N, _p(out), N, M, N, K, act,
                                     float(alpha), _p(ws), ws.numel(), _stream(a2)), "sbk_gemm_nt_splitk_f32")
     return out
@@ -916,12 +976,9 @@ def gemm_nt_splitk(a, w, bias=None, residual=None, act=ACT_NONE, alpha=1.0, slic
 def gemm_ln_nt(a, wf, bf, eps, residual=None, act=ACT_NONE, alpha=1.0):
     """LN(a) @ W^T + b with gamma/beta pre-folded into (wf, bf) (see include/sbk.h)."""
     lib = load()
-    K = a.shape[-1]
-    a2 = a.reshape(-1, K)
-    M, N = a2.shape[0], wf.shape[0]
+    a2, r2, M, N, K = _rows(a, wf, residual)
     _dev_ok(a2, wf, bf, residual)
     out = torch.empty(*a.shape[:-1], N, dtype=torch.float32, device=a.device)
-    r2 = residual.reshape(-1, N) if residual is not None else None
     _chk(lib.sbk_gemm_ln_nt_f32(_p(a2), K, _p(wf), K, _p(bf), _p(r2), N, _p(out), N, M, N, K, float(eps), act,
                                 float(alpha), _stream(a2)), "sbk_gemm_ln_nt_f32")
     return out
@@ -1179,6 +1236,23 @@ def csgu(h, gamma, beta, eps, w, bias, ksize, gate_act=ACT_NONE, out=None):
 
 
 # ------------------------------------------------------------------ decoder / searchers
+def _keeper(keep, strict):
+    """``ptr(t)`` for filling a weights struct: the address of ``t``, detached and contiguous and appended to ``keep`` so that
+    it stays valid.  ``strict`` (the handles): anything but an fp32 device tensor raises; otherwise (the transducer / RNNLM
+    layouts) the tensor is converted with ``.float()`` and None gives NULL."""
+    def ptr(t):
+        if t is None and not strict:
+            return None
+        t = t.detach().contiguous() if strict else t.detach().float().contiguous()
+        if strict:
+            _dev_ok(t)
+            _f32(t)
+        keep.append(t)
+        return t.data_ptr()
+
+    return ptr
+
+
 class DecoderHandle:
     """Device pointers of a TransformerASR decoder (+ seq_lin) laid out as sbk_decoder_weights.
     Holds references to the parameter tensors so the pointers stay valid."""
@@ -1218,40 +1292,16 @@ class DecoderHandle:
         self.keep = []
         fold = fold and final_ln[0].shape[0] in (128, 256, 512)  # shapes the fused kernel takes
         layers = (DecoderLayer * len(layer_specs))()
-
-        def ptr(t):
-            t = t.detach()
-            if not t.is_contiguous():
-                t = t.contiguous()
-            _dev_ok(t)
-            _f32(t)
-            self.keep.append(t)
-            return t.data_ptr()
-
+        ptr = _keeper(self.keep, strict=True)
         dm = emb.shape[1]
 
-        def split3(w):  # sbk_split_bf16x3's image (the big contractions of the search run on the bf16 matrix pipe)
-            if not F32X3 or w.shape[1] % 32 != 0 or w.shape[1] < 64 or w.shape[0] % 4 != 0:
+        def image(kind, w):  # the handle's own image of w where the kernels that read it take the shape, else NULL: "x3" for the
+            # big contractions of the search (bf16 matrix pipe), "x3p" for the decode step's projections (sbk_gemm_nt_x3r)
+            N, K = w.shape
+            if not (F32X3 and (_x3_shape(N, K) if kind == "x3" else X3R and K % 256 == 0 and N % 4 == 0)):
                 return None
-            w2 = w.detach().contiguous()
-            _dev_ok(w2)
-            _f32(w2)
-            out = torch.empty(w2.shape[0], w2.shape[1] // 32, 3, 32, dtype=torch.int16, device=w2.device)
-            _chk(load().sbk_split_bf16x3(_p(w2), w2.shape[1], _p(out), w2.shape[0], w2.shape[1], _stream(w2)), "sbk_split_bf16x3")
-            self.keep.append(out)
-            return out.data_ptr()
-
-        def panel(w):  # sbk_split_x3p's image: the decode step's projections as sbk_gemm_nt_x3r (csrc/gemm.hip)
-            if not (F32X3 and X3R) or w.shape[1] % 256 != 0 or w.shape[0] % 4 != 0:
-                return None
-            w2 = w.detach().contiguous()
-            _dev_ok(w2)
-            _f32(w2)
-            N, K = w2.shape
-            out = torch.empty(((N + 63) // 64) * 64 * K * 3, dtype=torch.int16, device=w2.device)
-            _chk(load().sbk_split_x3p(_p(w2), K, _p(out), N, K, _stream(w2)), "sbk_split_x3p")
-            self.keep.append(out)
-            return out.data_ptr()
+            self.keep.append(_make_image(w, kind)[0])
+            return self.keep[-1].data_ptr()
 
         for l, S in enumerate(layer_specs):
             o = layers[l]
@@ -1264,17 +1314,17 @@ class DecoderHandle:
             o.ln3_g, o.ln3_b = map(ptr, S["ln3"])
             o.ff1_w, o.ff1_b = map(ptr, S["ff1"])
             o.ff2_w, o.ff2_b = map(ptr, S["ff2"])
-            o.ca_kv_w3 = split3(S["ca_in"][0][dm:])
-            o.sa_in_wp, o.sa_out_wp = panel(S["sa_in"][0]), panel(S["sa_out"][0])
-            o.ca_q_wp, o.ca_out_wp = panel(S["ca_in"][0][:dm]), panel(S["ca_out"][0])
-            o.ff1_wp, o.ff2_wp = panel(S["ff1"][0]), panel(S["ff2"][0])
+            o.ca_kv_w3 = image("x3", S["ca_in"][0][dm:])
+            o.sa_in_wp, o.sa_out_wp = image("x3p", S["sa_in"][0]), image("x3p", S["sa_out"][0])
+            o.ca_q_wp, o.ca_out_wp = image("x3p", S["ca_in"][0][:dm]), image("x3p", S["ca_out"][0])
+            o.ff1_wp, o.ff2_wp = image("x3p", S["ff1"][0]), image("x3p", S["ff2"][0])
             if fold:  # LayerNorm folded into the projection it feeds (fused kernels, csrc/gemm.hip)
                 for name, (wf, bf) in (("sa_in", _fold_ln(*S["sa_in"], *S["ln1"])),
                                        ("ca_q", _fold_ln(S["ca_in"][0][:dm], S["ca_in"][1][:dm], *S["ln2"])),
                                        ("ff1", _fold_ln(*S["ff1"], *S["ln3"]))):
                     setattr(o, name + "_wf", ptr(wf))
                     setattr(o, name + "_bf", ptr(bf))
-                    setattr(o, name + "_wfp", panel(wf))  # (ABI 9: the same fold for the rows sbk_gemm_ln_nt_x3r takes)
+                    setattr(o, name + "_wfp", image("x3p", wf))  # (ABI 9: the same fold for the rows sbk_gemm_ln_nt_x3r takes)
         self.layers = layers
         W = DecoderWeights()
         W.layers = ctypes.cast(layers, POINTER(DecoderLayer))
@@ -1282,30 +1332,26 @@ class DecoderHandle:
         W.final_ln_g, W.final_ln_b = map(ptr, final_ln)
         if seq is not None:
             W.seq_w, W.seq_b = map(ptr, seq)
-            W.seq_w3 = split3(seq[0])
-            W.seq_wp = panel(seq[0])
+            W.seq_w3, W.seq_wp = image("x3", seq[0]), image("x3p", seq[0])
             if fold:
                 wf, bf = _fold_ln(seq[0], seq[1], *final_ln)
-                W.seq_wf, W.seq_bf, W.seq_wfp = ptr(wf), ptr(bf), panel(wf)
+                W.seq_wf, W.seq_bf, W.seq_wfp = ptr(wf), ptr(bf), image("x3p", wf)
         W.d_model, W.nhead = dm, nhead
         W.d_ffn, W.n_layers = layer_specs[0]["ff1"][0].shape[0], len(layer_specs)
         W.vocab = seq[0].shape[0] if seq is not None else emb.shape[0]
         W.max_len, W.ffn_act, W.ln_eps, W.emb_scale = pe.shape[-2], ffn_act, ln_eps, float(emb_scale)
-        self.W = W
-        self.device = emb.device
+        self.W, self.device = W, emb.device
         self.ready = _Ready(emb.device)  # (the folded / split tables above were written on this thread's stream)
 
     @staticmethod
     def source_key(model, seq_lin=None):
-        """(data_ptr, _version) of every tensor the handle was derived from -- the folded LayerNorm copies go
-        stale when a source parameter is updated IN PLACE (load_state_dict, Pretrainer, copy_), which keeps
-        data_ptr and bumps _version.  Cheap: no handle is built."""
+        """``source_key`` of every tensor the handle was derived from (the folded LayerNorm copies go stale with them)."""
         src = list(model.decoder.parameters())
         src.append(model.custom_tgt_module.layers[0].emb.Embedding.weight)
         src.append(model.positional_encoding_decoder.pe)
         if seq_lin is not None:
             src.extend(seq_lin.parameters())
-        return tuple((t.data_ptr(), t._version) for t in src)
+        return source_key(src)
 
     def stale(self, model, seq_lin=None):
         return self.source_key(model, seq_lin) != self.key
@@ -1316,16 +1362,7 @@ class LMHandle:
 
     def __init__(self, lm):
         self.keep = []
-
-        def ptr(t):
-            t = t.detach()
-            if not t.is_contiguous():
-                t = t.contiguous()
-            _dev_ok(t)
-            _f32(t)
-            self.keep.append(t)
-            return t.data_ptr()
-
+        ptr = _keeper(self.keep, strict=True)
         enc = lm.encoder
         layers = (LMLayer * len(enc.layers))()
         for l, L in enumerate(enc.layers):
@@ -1351,15 +1388,14 @@ class LMHandle:
         W.d_ffn, W.n_layers, W.vocab = enc.layers[0].pos_ffn.ffn[0].weight.shape[0], len(enc.layers), o2.w.weight.shape[0]
         W.max_len, W.ffn_act = pe.shape[-2], enc.layers[0].pos_ffn.act_code
         W.normalize_before, W.pad_idx, W.ln_eps = int(enc.layers[0].normalize_before), 0, enc.norm.eps
-        self.W = W
-        self.device = emb.device
+        self.W, self.device = W, emb.device
         self.ready = _Ready(emb.device)
         self.key = self.source_key(lm)
 
     @staticmethod
     def source_key(lm):
-        """(data_ptr, _version) of every source tensor (see DecoderHandle.source_key)."""
-        return tuple((t.data_ptr(), t._version) for t in list(lm.parameters()) + [lm.positional_encoding.pe])
+        """``source_key`` of every source tensor (see DecoderHandle.source_key)."""
+        return source_key(list(lm.parameters()) + [lm.positional_encoding.pe])
 
     def stale(self, lm):
         return self.source_key(lm) != self.key
@@ -1372,11 +1408,10 @@ def lm_prefix(handle: "LMHandle", tokens):
     n, L = tokens.shape
     handle.ready.wait(tokens.device)
     nbytes = lib.sbk_lm_prefix_workspace_bytes(ctypes.byref(handle.W), n, L)
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=tokens.device)
-    off = (-ws.data_ptr()) % 256
+    ws = _Workspace(nbytes, tokens.device)
     out = torch.empty(n, L, handle.W.vocab, dtype=torch.float32, device=tokens.device)
-    _chk(lib.sbk_lm_prefix_f32(ctypes.byref(handle.W), _p(tokens), c_void_p(ws.data_ptr() + off), nbytes, _p(out), n, L,
-                               _stream(tokens)), "sbk_lm_prefix_f32")
+    _chk(lib.sbk_lm_prefix_f32(ctypes.byref(handle.W), _p(tokens), ws.ptr, nbytes, _p(out), n, L, _stream(tokens)),
+         "sbk_lm_prefix_f32")
     return out
 
 
@@ -1415,28 +1450,22 @@ def beam_search(handle: DecoderHandle, cfg: SearchConfig, enc, enc_len, ctc_w=No
     K = max(int(cfg.topk), 1)  # rows per utterance (return_topk)
     handle.ready.wait(dev)
     nbytes = lib.sbk_beam_search_workspace_bytes(ctypes.byref(handle.W), ctypes.byref(cfg), B, T)
-    ws, ws_key = _search_workspace(nbytes + 256, dev)
-    off = (-ws.data_ptr()) % 256
-    out_tok = torch.zeros(B * K, L, dtype=torch.int32, device=dev)
-    out_len = torch.zeros(B * K, dtype=torch.int32, device=dev)
-    out_score = torch.zeros(B * K, dtype=torch.float32, device=dev)
-    out_lp = torch.zeros(B * K, L, dtype=torch.float32, device=dev)
-    out_max = torch.zeros(1, dtype=torch.int32, device=dev)
-    out_longest = torch.zeros(B, dtype=torch.int32, device=dev) if want_longest else None
-    flag = _host_flag(dev)
-    steps = c_int32(0)
-    cfg.ctc_w3 = None
-    if ctc_w is not None and F32X3 and ctc_w.dim() == 2 and ctc_w.is_contiguous() and ctc_w.shape[1] % 32 == 0 \
-            and ctc_w.shape[1] >= 64 and ctc_w.shape[0] % 4 == 0:
-        cfg.ctc_w3 = lp_weight(ctc_w, "x3").data_ptr()  # (cached with the parameter: the CTC head over B*T frames)
-    try:
+    with _Workspace(nbytes, dev, per_stream=True) as ws:
+        out_tok = torch.zeros(B * K, L, dtype=torch.int32, device=dev)
+        out_len = torch.zeros(B * K, dtype=torch.int32, device=dev)
+        out_score = torch.zeros(B * K, dtype=torch.float32, device=dev)
+        out_lp = torch.zeros(B * K, L, dtype=torch.float32, device=dev)
+        out_max = torch.zeros(1, dtype=torch.int32, device=dev)
+        out_longest = torch.zeros(B, dtype=torch.int32, device=dev) if want_longest else None
+        flag = _host_flag(dev)
+        steps = c_int32(0)
+        cfg.ctc_w3 = None
+        if ctc_w is not None and F32X3 and ctc_w.dim() == 2 and ctc_w.is_contiguous() and _x3_shape(*ctc_w.shape):
+            cfg.ctc_w3 = lp_weight(ctc_w, "x3").data_ptr()  # (cached with the parameter: the CTC head over B*T frames)
         _chk(lib.sbk_beam_search_f32(ctypes.byref(handle.W), ctypes.byref(cfg), _p(enc), _p(enc_len), _p(ctc_w), _p(ctc_b),
-                                     c_void_p(ws.data_ptr() + off), nbytes, _p(out_tok), _p(out_len), _p(out_score),
-                                     _p(out_lp), _p(out_max), _p(out_longest), c_void_p(flag.data_ptr()),
-                                     ctypes.byref(steps), B, T, _stream(enc)),
+                                     ws.ptr, nbytes, _p(out_tok), _p(out_len), _p(out_score), _p(out_lp), _p(out_max),
+                                     _p(out_longest), c_void_p(flag.data_ptr()), ctypes.byref(steps), B, T, _stream(enc)),
              "sbk_beam_search_f32")
-    finally:
-        _search_workspace_done(ws_key)
     if want_longest:
         return out_tok, out_len, out_score, out_lp, out_max, steps.value, out_longest
     return out_tok, out_len, out_score, out_lp, out_max, steps.value
@@ -1510,13 +1539,12 @@ def greedy_search(handle: DecoderHandle, enc, enc_len, min_steps, max_steps, bos
     L = max(int(max_steps), 1)
     handle.ready.wait(dev)
     nbytes = lib.sbk_greedy_search_workspace_bytes(ctypes.byref(handle.W), B, T, max_steps)
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-    off = (-ws.data_ptr()) % 256
+    ws = _Workspace(nbytes, dev)
     out_tok = torch.zeros(B, L, dtype=torch.int32, device=dev)
     out_sc = torch.zeros(B, L, dtype=torch.float32, device=dev)
     flag = _host_flag(dev)
     steps = c_int32(0)
-    _chk(lib.sbk_greedy_search_f32(ctypes.byref(handle.W), _p(enc), _p(enc_len), c_void_p(ws.data_ptr() + off), nbytes,
+    _chk(lib.sbk_greedy_search_f32(ctypes.byref(handle.W), _p(enc), _p(enc_len), ws.ptr, nbytes,
                                    _p(out_tok), _p(out_sc), c_void_p(flag.data_ptr()), ctypes.byref(steps), B, T,
                                    int(min_steps), int(max_steps), int(bos), int(eos), int(check_every), _stream(enc)),
          "sbk_greedy_search_f32")
@@ -1536,8 +1564,7 @@ def prompted_greedy_search(handle: DecoderHandle, enc, enc_len, prompt, max_new,
     L = max(int(max_new), 1)
     handle.ready.wait(enc.device)
     nbytes = lib.sbk_prompted_greedy_search_workspace_bytes(ctypes.byref(handle.W), B, T, P, int(max_new))
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-    off = (-ws.data_ptr()) % 256
+    ws = _Workspace(nbytes, dev)
     out_tok = torch.zeros(B, L, dtype=torch.int32, device=dev)
     out_sc = torch.zeros(B, L, dtype=torch.float32, device=dev)
     out_probe = torch.zeros(B, dtype=torch.float32, device=dev) if probe is not None else None
@@ -1545,7 +1572,7 @@ def prompted_greedy_search(handle: DecoderHandle, enc, enc_len, prompt, max_new,
     steps = c_int32(0)
     _chk(lib.sbk_prompted_greedy_search_f32(
         ctypes.byref(handle.W), _p(enc), _p(enc_len), _p(prompt), P, _p(logit_bias), _p(first_bias),
-        c_void_p(ws.data_ptr() + off), nbytes, _p(out_tok), _p(out_sc), int(probe[0]) if probe else 0,
+        ws.ptr, nbytes, _p(out_tok), _p(out_sc), int(probe[0]) if probe else 0,
         int(probe[1]) if probe else 0, _p(out_probe), c_void_p(flag.data_ptr()), ctypes.byref(steps), B, T, int(max_new),
         int(eos), int(check_every), _stream(enc)), "sbk_prompted_greedy_search_f32")
     return out_tok, out_sc, steps.value, out_probe
@@ -1559,12 +1586,10 @@ def decoder_prefix(handle: DecoderHandle, tokens, enc, enc_len):
     T = enc.shape[1]
     handle.ready.wait(enc.device)
     nbytes = lib.sbk_decoder_prefix_workspace_bytes(ctypes.byref(handle.W), n, T, L)
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=enc.device)
-    off = (-ws.data_ptr()) % 256
+    ws = _Workspace(nbytes, enc.device)
     pred = torch.empty(n, L, handle.W.d_model, dtype=torch.float32, device=enc.device)
-    _chk(lib.sbk_decoder_prefix_f32(ctypes.byref(handle.W), _p(tokens), _p(enc), _p(enc_len),
-                                    c_void_p(ws.data_ptr() + off), nbytes, _p(pred), n, T, L, _stream(enc)),
-         "sbk_decoder_prefix_f32")
+    _chk(lib.sbk_decoder_prefix_f32(ctypes.byref(handle.W), _p(tokens), _p(enc), _p(enc_len), ws.ptr, nbytes, _p(pred), n, T, L,
+                                    _stream(enc)), "sbk_decoder_prefix_f32")
     return pred
 
 
@@ -1590,9 +1615,8 @@ class CTCStepScorer:
         lib = load()
         self.beam = beam
         self.nbytes = lib.sbk_ctc_scorer_workspace_bytes(self.B, self.T, self.V, beam)
-        self.ws = torch.empty(self.nbytes + 256, dtype=torch.uint8, device=self.x.device)
-        self._off = (-self.ws.data_ptr()) % 256
-        _chk(lib.sbk_ctc_scorer_reset_f32(_p(self.x), _p(self.enc_len), c_void_p(self.ws.data_ptr() + self._off), self.nbytes, self.B,
+        self.ws = _Workspace(self.nbytes, self.x.device)
+        _chk(lib.sbk_ctc_scorer_reset_f32(_p(self.x), _p(self.enc_len), self.ws.ptr, self.nbytes, self.B,
                                           self.T, self.V, beam, self.blank, _stream(self.x)), "sbk_ctc_scorer_reset_f32")
 
     def score(self, inp_tokens, step, attn_window=None):
@@ -1602,14 +1626,14 @@ class CTCStepScorer:
         self._ready(n // self.B)
         tok = inp_tokens.to(torch.int32).contiguous()
         out = torch.empty(n, self.V, dtype=torch.float32, device=self.x.device)
-        _chk(load().sbk_ctc_scorer_score_f32(_p(self.x), _p(self.enc_len), c_void_p(self.ws.data_ptr() + self._off), self.nbytes, _p(tok),
+        _chk(load().sbk_ctc_scorer_score_f32(_p(self.x), _p(self.enc_len), self.ws.ptr, self.nbytes, _p(tok),
                                              int(step), _p(attn_window), self.window if attn_window is not None else 0, _p(out), self.B,
                                              self.T, self.V, self.beam, self.blank, self.eos, _stream(self.x)), "sbk_ctc_scorer_score_f32")
         return out
 
     def permute(self, parent, token, parent_last_tok, step, attn_window=None):
         par, tk, last = (t.to(torch.int32).contiguous() for t in (parent, token, parent_last_tok))
-        _chk(load().sbk_ctc_scorer_permute_f32(_p(self.x), c_void_p(self.ws.data_ptr() + self._off), self.nbytes, _p(par), _p(tk), _p(last),
+        _chk(load().sbk_ctc_scorer_permute_f32(_p(self.x), self.ws.ptr, self.nbytes, _p(par), _p(tk), _p(last),
                                                int(step), _p(attn_window), self.window if attn_window is not None else 0, self.B, self.T,
                                                self.V, self.beam, self.blank, _stream(self.x)), "sbk_ctc_scorer_permute_f32")
 
@@ -1626,6 +1650,10 @@ def log_softmax(x, temperature=1.0, weight=1.0):
 
 
 # ------------------------------------------------------------------ CTC decoding (csrc/ctc_decode.hip)
+def _rel_len(rel_len, device):  # as the CTC decoders take it: fp32 [B] on ``device``, or None (every frame)
+    return None if rel_len is None else rel_len.to(device=device, dtype=torch.float32).contiguous()
+
+
 def ctc_greedy_decode(x, rel_len, blank):
     """x [B,T,V] fp32 -> (tokens [B,T] int32, count [B] int32): row b's first count[b] entries are its collapsed,
     blank-free arg-max path over int(round(rel_len[b] * T)) frames (rel_len None = every frame)."""
@@ -1633,7 +1661,7 @@ def ctc_greedy_decode(x, rel_len, blank):
     _f32(x)
     B, T, V = x.shape
     x = x.contiguous()
-    rel = None if rel_len is None else rel_len.to(device=x.device, dtype=torch.float32).contiguous()
+    rel = _rel_len(rel_len, x.device)
     _dev_ok(x, rel)
     tokens = torch.empty(B, T, dtype=torch.int32, device=x.device)
     count = torch.empty(B, dtype=torch.int32, device=x.device)
@@ -1651,12 +1679,11 @@ def ctc_beam_search(x, rel_len, table, n_vocab, cfg, lm=None):
     _f32(x)
     B, T, V = x.shape
     x = x.contiguous()
-    rel = None if rel_len is None else rel_len.to(device=x.device, dtype=torch.float32).contiguous()
+    rel = _rel_len(rel_len, x.device)
     table = table.to(device=x.device, dtype=torch.int32).contiguous()
     _dev_ok(x, rel, table)
     nbytes = lib.sbk_ctc_beam_search_workspace_bytes(B, T, V, cfg.beam_size, cfg.topk)
-    ws = torch.empty(max(nbytes, 1) + 16, dtype=torch.uint8, device=x.device)
-    off = (-ws.data_ptr()) % 16
+    ws = _Workspace(nbytes, x.device, align=16, floor=1)
     paths = torch.empty(B, max(cfg.topk, 1), T, dtype=torch.int32, device=x.device)
     scores = torch.empty(B, max(cfg.topk, 1), dtype=torch.float32, device=x.device)
     count = torch.empty(B, dtype=torch.int32, device=x.device)
@@ -1664,93 +1691,69 @@ def ctc_beam_search(x, rel_len, table, n_vocab, cfg, lm=None):
         tabs = lm.tables(x.device)
         lm_scores = torch.empty_like(scores)
         _chk(lib.sbk_ctc_beam_search_lm_f32(_p(x), _p(rel), _p(table), int(n_vocab), ctypes.byref(cfg), ctypes.byref(tabs),
-                                            c_void_p(ws.data_ptr() + off), nbytes, _p(paths), _p(scores), _p(lm_scores),
-                                            _p(count), B, T, V, _stream(x)), "sbk_ctc_beam_search_lm_f32")
+                                            ws.ptr, nbytes, _p(paths), _p(scores), _p(lm_scores), _p(count), B, T, V,
+                                            _stream(x)), "sbk_ctc_beam_search_lm_f32")
         return paths, scores, count, lm_scores
-    _chk(lib.sbk_ctc_beam_search_f32(_p(x), _p(rel), _p(table), int(n_vocab), ctypes.byref(cfg),
-                                     c_void_p(ws.data_ptr() + off), nbytes, _p(paths), _p(scores), _p(count), B, T, V,
-                                     _stream(x)), "sbk_ctc_beam_search_f32")
+    _chk(lib.sbk_ctc_beam_search_f32(_p(x), _p(rel), _p(table), int(n_vocab), ctypes.byref(cfg), ws.ptr, nbytes, _p(paths),
+                                     _p(scores), _p(count), B, T, V, _stream(x)), "sbk_ctc_beam_search_f32")
     return paths, scores, count
 
 
 # ------------------------------------------------------------------ transducer greedy decoding (csrc/transducer.hip)
+def _fill_lstm_stack(W, what, emb, lstm_layers, ptr):
+    """The part sbk_transducer_weights and sbk_rnnlm_weights share: the Embedding folded into layer 0's input weights (one
+    sbk_gemm_nt_f32, on the current stream), the other LSTM matrices as they are.  Returns emb_ih [n_emb, 4H] = E . W_ih^T."""
+    if not 1 <= len(lstm_layers) <= TRANSDUCER_MAX_LAYERS:
+        raise SbkError(f"{what}: {len(lstm_layers)} LSTM layers (1..{TRANSDUCER_MAX_LAYERS} supported)")
+    w_ih0 = lstm_layers[0][0].detach().float().contiguous()
+    with precision_scope("fp32"):
+        emb_ih = gemm_nt(emb.detach().float().contiguous(), w_ih0)
+    W.emb_ih = ptr(emb_ih)
+    for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(lstm_layers):
+        if l > 0:
+            W.w_ih[l] = ptr(w_ih)
+        W.w_hh[l], W.b_ih[l], W.b_hh[l] = ptr(w_hh), ptr(b_ih), ptr(b_hh)
+    W.n_layers, W.hidden, W.n_emb = len(lstm_layers), lstm_layers[0][1].shape[1], emb.shape[0]
+    return emb_ih
+
+
 class TransducerPrepared:
     """The prediction network, joint and classifier of a transducer in the layouts of sbk_transducer_weights (include/sbk.h):
-    the Embedding folded into layer 0's input weights (one sbk_gemm_nt_f32), the other matrices as they are.  Built once per
-    set of weights; the tensors are kept alive here for as long as the struct points at them."""
+    the Embedding folded into layer 0's input weights, the other matrices as they are.  Built once per set of weights; the
+    tensors are kept alive here for as long as the struct points at them."""
 
     def __init__(self, emb, lstm_layers, proj_w, proj_b, out_w, out_b):
         """emb [n_emb, E]; lstm_layers: [(w_ih [4H, in], w_hh [4H, H], b_ih or None, b_hh or None)] * L;
         proj_w [J, H], proj_b [J] or None; out_w [V, J], out_b [V] or None (all fp32 on one device)."""
-        if not 1 <= len(lstm_layers) <= TRANSDUCER_MAX_LAYERS:
-            raise SbkError(f"transducer: {len(lstm_layers)} LSTM layers (1..{TRANSDUCER_MAX_LAYERS} supported)")
-        keep = []
-
-        def t(x):
-            if x is None:
-                return None
-            x = x.detach().float().contiguous()
-            keep.append(x)
-            return x
-
-        w_ih0 = lstm_layers[0][0].detach().float().contiguous()
-        with precision_scope("fp32"):
-            self.emb_ih = t(gemm_nt(emb.detach().float().contiguous(), w_ih0))  # [n_emb, 4H] = E . W_ih^T
-        W = TransducerWeights()
-        W.emb_ih = self.emb_ih.data_ptr()
-        for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(lstm_layers):
-            if l > 0:
-                W.w_ih[l] = t(w_ih).data_ptr()
-            W.w_hh[l] = t(w_hh).data_ptr()
-            W.b_ih[l] = None if b_ih is None else t(b_ih).data_ptr()
-            W.b_hh[l] = None if b_hh is None else t(b_hh).data_ptr()
-        W.proj = t(proj_w).data_ptr()
-        W.proj_b = None if proj_b is None else t(proj_b).data_ptr()
-        W.out = t(out_w).data_ptr()
-        W.out_b = None if out_b is None else t(out_b).data_ptr()
-        W.n_layers, W.hidden, W.joint = len(lstm_layers), lstm_layers[0][1].shape[1], proj_w.shape[0]
-        W.vocab, W.n_emb = out_w.shape[0], emb.shape[0]
-        self.W, self._keep, self.device = W, keep, self.emb_ih.device
+        self.W, self._keep = W, keep = TransducerWeights(), []
+        ptr = _keeper(keep, strict=False)
+        self.emb_ih = _fill_lstm_stack(W, "transducer", emb, lstm_layers, ptr)
+        W.proj, W.proj_b, W.out, W.out_b = ptr(proj_w), ptr(proj_b), ptr(out_w), ptr(out_b)
+        W.joint, W.vocab = proj_w.shape[0], out_w.shape[0]
+        self.device = self.emb_ih.device
 
 
 class RNNLMPrepared:
     """An RNNLM (lobes/models/RNNLM.py) in the layouts of sbk_rnnlm_weights (include/sbk.h): the Embedding folded into layer
-    0's input weights (one sbk_gemm_nt_f32), the other matrices as they are.  Built once per set of weights; the tensors are
-    kept alive here for as long as the struct points at them."""
+    0's input weights, the other matrices as they are.  Built once per set of weights; the tensors are kept alive here for as
+    long as the struct points at them."""
 
     def __init__(self, emb, lstm_layers, dnn_blocks, out_w, out_b, act):
         """emb [n_emb, E]; lstm_layers: [(w_ih [4H, in], w_hh [4H, H], b_ih or None, b_hh or None)] * L; dnn_blocks:
         [(w [D, in], b [D] or None, ln_weight [D], ln_bias [D], ln_eps)] * n_dnn; out_w [V, D], out_b [V] or None; act: one of
         ACT_LEAKY_RELU, ACT_RELU, ACT_GELU, ACT_TANH (all fp32 on one device)."""
-        if not 1 <= len(lstm_layers) <= TRANSDUCER_MAX_LAYERS:
-            raise SbkError(f"RNNLM: {len(lstm_layers)} LSTM layers (1..{TRANSDUCER_MAX_LAYERS} supported)")
         if not 1 <= len(dnn_blocks) <= RNNLM_MAX_DNN:
             raise SbkError(f"RNNLM: {len(dnn_blocks)} DNN blocks (1..{RNNLM_MAX_DNN} supported)")
-        keep = []
-
-        def t(x):
-            x = x.detach().float().contiguous()
-            keep.append(x)
-            return x
-
-        ptr = lambda x: None if x is None else t(x).data_ptr()  # noqa: E731
-        w_ih0 = lstm_layers[0][0].detach().float().contiguous()
-        with precision_scope("fp32"):
-            self.emb_ih = t(gemm_nt(emb.detach().float().contiguous(), w_ih0))  # [n_emb, 4H] = E . W_ih^T
-        M = RNNLMWeights()
-        M.emb_ih = self.emb_ih.data_ptr()
-        for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(lstm_layers):
-            if l > 0:
-                M.w_ih[l] = ptr(w_ih)
-            M.w_hh[l], M.b_ih[l], M.b_hh[l] = ptr(w_hh), ptr(b_ih), ptr(b_hh)
+        self.M, self._keep = M, keep = RNNLMWeights(), []
+        ptr = _keeper(keep, strict=False)
+        self.emb_ih = _fill_lstm_stack(M, "RNNLM", emb, lstm_layers, ptr)
         for i, (w, b, g, beta, eps) in enumerate(dnn_blocks):
             M.dnn_w[i], M.dnn_b[i], M.ln_g[i], M.ln_b[i], M.ln_eps[i] = ptr(w), ptr(b), ptr(g), ptr(beta), float(eps)
         M.out, M.out_b = ptr(out_w), ptr(out_b)
-        M.n_layers, M.hidden, M.n_dnn, M.dnn = len(lstm_layers), lstm_layers[0][1].shape[1], len(dnn_blocks), out_w.shape[1]
-        M.vocab, M.n_emb, M.act = out_w.shape[0], emb.shape[0], int(act)
-        self.M, self._keep, self.device = M, keep, self.emb_ih.device
-        self.weight_bytes = 4 * sum(int(x.numel()) for x in keep) - 4 * int(self.emb_ih.numel()) + 4 * 4 * M.hidden
+        M.n_dnn, M.dnn, M.vocab, M.act = len(dnn_blocks), out_w.shape[1], out_w.shape[0], int(act)
+        self.device = self.emb_ih.device
         # (what one LM step reads: every matrix once, and one row of emb_ih)
+        self.weight_bytes = 4 * sum(int(x.numel()) for x in keep) - 4 * int(self.emb_ih.numel()) + 4 * 4 * M.hidden
 
 
 def lstm(x, layers, hx=None):
@@ -1843,23 +1846,19 @@ def transducer_beam_search(prep: TransducerPrepared, tn, blank, beam_size, nbest
         if lm.device != prep.device:
             raise SbkError(f"transducer_beam_search: the LM is prepared on {lm.device}, the network on {prep.device}")
         nbytes = lib.sbk_transducer_beam_lm_workspace_bytes(ctypes.byref(prep.W), ctypes.byref(lm.M), ctypes.byref(cfg), B, T)
-    ws, ws_key = _search_workspace(max(nbytes, 16) + 16, dev)
-    off = (-ws.data_ptr()) % 16
-    try:
+    with _Workspace(nbytes, dev, align=16, floor=16, per_stream=True) as ws:
         # (a refused configuration gives 0 bytes above; the entry then reports the reason)
         if lm is None:
-            _chk(lib.sbk_transducer_beam_search_f32(ctypes.byref(prep.W), ctypes.byref(cfg), _p(tn),
-                                                    c_void_p(ws.data_ptr() + off), nbytes, _p(tokens), _p(length), _p(score),
-                                                    _p(count), _p(status), B, T, _stream(tn)), "sbk_transducer_beam_search_f32")
+            _chk(lib.sbk_transducer_beam_search_f32(ctypes.byref(prep.W), ctypes.byref(cfg), _p(tn), ws.ptr, nbytes, _p(tokens),
+                                                    _p(length), _p(score), _p(count), _p(status), B, T, _stream(tn)),
+                 "sbk_transducer_beam_search_f32")
         else:
             _chk(lib.sbk_transducer_beam_search_lm_f32(ctypes.byref(prep.W), ctypes.byref(lm.M), float(lm_weight),
-                                                       ctypes.byref(cfg), _p(tn), c_void_p(ws.data_ptr() + off), nbytes,
-                                                       _p(tokens), _p(length), _p(score), _p(count), _p(status), B, T,
-                                                       _stream(tn)), "sbk_transducer_beam_search_lm_f32")
-        expansions = ws[off:off + 4 * B].view(torch.int32).clone()
-        lm_steps = ws[off + 4 * B:off + 8 * B].view(torch.int32).clone() if lm is not None else None
-    finally:
-        _search_workspace_done(ws_key)
+                                                       ctypes.byref(cfg), _p(tn), ws.ptr, nbytes, _p(tokens), _p(length),
+                                                       _p(score), _p(count), _p(status), B, T, _stream(tn)),
+                 "sbk_transducer_beam_search_lm_f32")
+        expansions = ws.buf[ws.off:ws.off + 4 * B].view(torch.int32).clone()
+        lm_steps = ws.buf[ws.off + 4 * B:ws.off + 8 * B].view(torch.int32).clone() if lm is not None else None
     ret = (tokens, length, score, count, status, expansions)
     return ret + (lm_steps,) if return_lm_steps else ret
 
