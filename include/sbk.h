@@ -352,6 +352,28 @@ int sbk_conv_block_f32(const float* x, const float* wt, const float* bias, const
                        float* y, int B, int Tin, int Fin, int Cin, int Cout, float eps, float slope,
                        sbk_stream_t stream);
 
+/* The same block with a ksize x ksize kernel: (ksize, stride) = (3, 2) IS sbk_conv_block_f32 (same launch, same bits); (5, 2) is
+ * the transformer.yaml front end's: reflect-pad(2) (nnet/CNN.py get_padding_elem: ksize / 2 on each side when stride > 1) ->
+ * Conv2d(5x5, stride 2, bias) -> LayerNorm over (F',C') -> LeakyReLU, Tout = (Tin-1)/2+1, Fout = (Fin-1)/2+1 again; Tin, Fin >= 3.
+ * The weight layout follows sbk_conv_block_k_layout(Cin, Cout, ksize):
+ *   0: wt [Cin*ksize*ksize, Cout], row (ci*ksize+kf)*ksize+kt (the layout of sbk_conv_block_f32; F'*C' <= 2560)
+ *   1: the matrix-core panel [kt][kf][Cin/8][2][Cout][4] = conv.weight[co][8g + 4h + e][kf][kt], 16-byte aligned (ksize 5, Cin = Cout = 64:
+ *      v_mfma_f32_32x32x2_f32, several output frames per workgroup)
+ * Any other (ksize, stride): SBK_EINVAL. */
+int sbk_conv_block_k_layout(int Cin, int Cout, int ksize);
+int sbk_conv_block_k_f32(const float* x, const float* wt, const float* bias, const float* gamma, const float* beta, float* y,
+                         int B, int Tin, int Fin, int Cin, int Cout, int ksize, int stride, float eps, float slope,
+                         sbk_stream_t stream);
+
+/* A residual ConvBlock of one 1x1 stride-1 layer (lobes/models/convolution.py:297-317), one launch:
+ *   y = LeakyReLU(LN_1(conv_0(x))) + LN_2(reduce_conv(x)),   x [B,T,F,Cin] -> y [B,T,F,Cout], both LayerNorms over (F,Cout)
+ *   w1t / w2t [Cin,Cout] = the two 1x1 conv weights transposed, b1 / b2 [Cout], gamma / beta [F*Cout] each.
+ * Cout a divisor of 256, F*Cout <= 2560 (SBK_EINVAL otherwise). */
+int sbk_conv_block_res1x1_f32(const float* x, const float* w1t, const float* b1, const float* gamma1, const float* beta1,
+                              float eps1, const float* w2t, const float* b2, const float* gamma2, const float* beta2,
+                              float eps2, float* y, int B, int T, int F, int Cin, int Cout, float slope,
+                              sbk_stream_t stream);
+
 /* ---- a12: RelPosMHAXL core (nnet/attention.py:555-742 minus the two Linear layers):
  *   qkv  [B,T,H,3*Dh] = F.linear(x, in_proj_weight) viewed per head as (q|k|v) (:623-626)
  *   pos  [2T-1,H*Dh]  = linear_pos(RelPosEncXL(T))                            (:655)

@@ -60,6 +60,9 @@ struct SelfAttnArgs {
 // 55.5 / 73.2 us per launch against 43.3 at 1 280 rows and prefixes of 1 .. 60 tokens, profiles/r05_p_*: the kernel is bound
 // by the number of row requests it issues, not by their latency -- every surplus (clamped) request and every wave lost to
 // the 112 / 188 registers costs more than the shorter chain returns.  Removed.)
+// NP = 16-byte pieces of the head row per lane: 1 serves head_dim <= 64; 2 (head_dim 65 .. 128, a multiple of 4) adds the piece
+// 64 channels further on, so the wide heads of the transformer.yaml recipe (d 512, 4 heads) keep the vector path.
+template <int NP>
 __global__ void __launch_bounds__(256) self_attn_step_kernel(SelfAttnArgs a) {
   SBK_DYN_LDS(float, lds);  // [4 waves][2][Lmax_pad]: probabilities, slots
   if (a.step_ptr) a.step = a.step_ptr[0];
@@ -80,7 +83,7 @@ __global__ void __launch_bounds__(256) self_attn_step_kernel(SelfAttnArgs a) {
   const float* knew = q + d;
   const float* vnew = q + 2 * d;
   const int pg = lane >> 4, cq = lane & 15;  // position group, 16-byte piece of the head row
-  const bool vec = (Dh % 4 == 0) && Dh <= 64;
+  const bool vec = (Dh % 4 == 0) && Dh <= 64 * NP;
   // append this token's K/V head slice to the cache (slot = hypothesis index)
   if (live) {
     for (int c = lane; c < Dh; c += 64) {
@@ -100,6 +103,12 @@ __global__ void __launch_bounds__(256) self_attn_step_kernel(SelfAttnArgs a) {
     q4 = *reinterpret_cast<const float4*>(q + cq * 4);
     q4.x *= a.scale; q4.y *= a.scale; q4.z *= a.scale; q4.w *= a.scale;
   }
+  const bool piece2 = NP == 2 && vec && 64 + cq * 4 < Dh;  // the lane's second piece: channels 64 + 4 cq .. + 3
+  float4 q4b = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (piece2) {
+    q4b = *reinterpret_cast<const float4*>(q + 64 + cq * 4);
+    q4b.x *= a.scale; q4b.y *= a.scale; q4b.z *= a.scale; q4b.w *= a.scale;
+  }
   // scores
   for (int p0 = 0; p0 < L; p0 += 16) {
     float sc[4];
@@ -112,6 +121,15 @@ __global__ void __launch_bounds__(256) self_attn_step_kernel(SelfAttnArgs a) {
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) sc[u] = (q4.x * kv[u].x + q4.y * kv[u].y) + (q4.z * kv[u].z + q4.w * kv[u].w);
+      if constexpr (NP == 2) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int p = p0 + 4 * u + pg;
+          kv[u] = (p < L && piece2) ? *reinterpret_cast<const float4*>(krow(p) + 64 + cq * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) sc[u] += (q4b.x * kv[u].x + q4b.y * kv[u].y) + (q4b.z * kv[u].z + q4b.w * kv[u].w);
+      }
     } else {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -182,6 +200,35 @@ __global__ void __launch_bounds__(256) self_attn_step_kernel(SelfAttnArgs a) {
       o[e] += sbk::shfl_xor(o[e], 32);
     }
     if (live && pg == 0 && piece) *reinterpret_cast<float4*>(a.out + (size_t)i * d + head_off + cq * 4) = make_float4(o[0], o[1], o[2], o[3]);
+    if constexpr (NP == 2) {  // the same walk for the second piece
+      float4 accb = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int p0 = 0; p0 < L; p0 += 16) {
+        float4 vv[4];
+        float w[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int p = p0 + 4 * u + pg;
+          const bool ok = p < L && piece2;
+          vv[u] = ok ? *reinterpret_cast<const float4*>(vrow(p) + 64 + cq * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+          w[u] = ok ? prob[p] : 0.0f;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          accb.x = fmaf(w[u], vv[u].x, accb.x);
+          accb.y = fmaf(w[u], vv[u].y, accb.y);
+          accb.z = fmaf(w[u], vv[u].z, accb.z);
+          accb.w = fmaf(w[u], vv[u].w, accb.w);
+        }
+      }
+      float ob[4] = {accb.x, accb.y, accb.z, accb.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        ob[e] += sbk::shfl_xor(ob[e], 16);
+        ob[e] += sbk::shfl_xor(ob[e], 32);
+      }
+      if (live && pg == 0 && piece2)
+        *reinterpret_cast<float4*>(a.out + (size_t)i * d + head_off + 64 + cq * 4) = make_float4(ob[0], ob[1], ob[2], ob[3]);
+    }
   } else {
     for (int c0 = 0; c0 < Dh; c0 += 16) {
       const int c = c0 + cq;
@@ -473,15 +520,31 @@ __global__ void __launch_bounds__(256) cross_attn_step_kernel(CrossAttnArgs a) {
   {
     const int f = tid & (FC - 1), par = tid / FC;  // 256 / FC threads per frame, beams split between them
     if (f < nf) {
-      float kr[DH];
       const float* kp = kvb + (size_t)(t0 + f) * kvv.row;
+      if constexpr (DH <= 64) {
+        float kr[DH];
 #pragma unroll
-      for (int c = 0; c < DH; ++c) kr[c] = kp[c];
-      for (int j = par; j < nq; j += 256 / FC) {
-        float s = 0.0f;
+        for (int c = 0; c < DH; ++c) kr[c] = kp[c];
+        for (int j = par; j < nq; j += 256 / FC) {
+          float s = 0.0f;
 #pragma unroll
-        for (int c = 0; c < DH; ++c) s = fmaf(qs[j][c], kr[c], s);
-        S[j][f] = s;
+          for (int c = 0; c < DH; ++c) s = fmaf(qs[j][c], kr[c], s);
+          S[j][f] = s;
+        }
+      } else {  // head_dim 128: the K row in two 64-channel halves (64 registers, not 128), the partial score waits in LDS
+        static_assert(DH % 64 == 0, "wide heads walk the K row in 64-channel halves");
+#pragma unroll 1
+        for (int c0 = 0; c0 < DH; c0 += 64) {
+          float kr[64];
+#pragma unroll
+          for (int c = 0; c < 64; ++c) kr[c] = kp[c0 + c];
+          for (int j = par; j < nq; j += 256 / FC) {
+            float s = c0 ? S[j][f] : 0.0f;
+#pragma unroll
+            for (int c = 0; c < 64; ++c) s = fmaf(qs[j][c0 + c], kr[c], s);
+            S[j][f] = s;
+          }
+        }
       }
     }
   }
@@ -506,11 +569,13 @@ __global__ void __launch_bounds__(256) cross_attn_step_kernel(CrossAttnArgs a) {
   }
   __syncthreads();
   {  // context: wave <-> quarter of the frames, lane <-> channel; 8 V rows in flight per lane
-    float acc[kQT];
 #pragma unroll
-    for (int j = 0; j < kQT; ++j) acc[j] = 0.0f;
-    const int c = lane;
-    if (c < DH) {
+    for (int cc = 0; cc < (DH + 63) / 64; ++cc) {  // (one trip up to head_dim 64, two at 128)
+      const int c = lane + 64 * cc;
+      if (c >= DH) break;
+      float acc[kQT];
+#pragma unroll
+      for (int j = 0; j < kQT; ++j) acc[j] = 0.0f;
       const float* vcol = kvb + (size_t)t0 * kvv.row + kvv.voff + c;
       for (int f0 = wave; f0 < nf; f0 += 32) {
         float v[8];
@@ -906,7 +971,11 @@ int self_attn_step(const float* qkv, float* kcache, float* vcache, const int32_t
   const size_t lds = (size_t)8 * (((Lmax + 63) / 64) * 64) * sizeof(float);
   if (lds > 64 * 1024) return fail(SBK_EINVAL, "self_attn_step: Lmax=%d too long for the LDS window", Lmax);
   ProfScope prof("self_attn_step", 4.0 * n * d * (step + 1), 8.0 * n * d * (step + 1), st);
-  SBK_LAUNCH(self_attn_step_kernel, dim3(cdiv(n * H, 4)), dim3(256), lds, st, a);
+  if (a.Dh > 64 && a.Dh <= 128 && a.Dh % 4 == 0) {
+    SBK_LAUNCH(self_attn_step_kernel<2>, dim3(cdiv(n * H, 4)), dim3(256), lds, st, a);
+  } else {
+    SBK_LAUNCH(self_attn_step_kernel<1>, dim3(cdiv(n * H, 4)), dim3(256), lds, st, a);
+  }
   return launch_status("self_attn_step");
 }
 
@@ -928,12 +997,13 @@ int cross_attn_step(const float* q, const float* kv, const int32_t* enc_len, flo
   if (NS > 1 && !part) return fail(SBK_EINVAL, "cross_attn_step: T=%d needs a partial buffer", T);
   CrossAttnArgs a{q, kv, enc_len, out, part, B, T, d, H, Dh, beam, NS, 1.0f / sqrtf((float)Dh), fc};
   switch (Dh) {
+    case 128: return launch_cross<128>(a, st);  // (the frame-per-thread kernel; the register ring is head_dim 64's)
     case 64: return launch_cross<64>(a, st);
     case 36: return launch_cross<36>(a, st);
     case 32: return launch_cross<32>(a, st);
     case 16: return launch_cross<16>(a, st);
     case 8: return launch_cross<8>(a, st);
-    default: return fail(SBK_EINVAL, "cross_attn_step: head_dim %d not instantiated (8,16,32,36,64)", Dh);
+    default: return fail(SBK_EINVAL, "cross_attn_step: head_dim %d not instantiated (8,16,32,36,64,128)", Dh);
   }
 }
 

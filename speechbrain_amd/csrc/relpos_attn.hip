@@ -409,6 +409,149 @@ __global__ void __launch_bounds__(256, 2) rope_flash_t_kernel(AttnArgs a) {
   }
 }
 
+// ---- head dim 128 (the transformer.yaml recipe: d_model 512, 4 heads), same transposed-score scheme.  rope_flash_t_kernel<128> would
+// hold qu[64] + kreg[64] + vv[4][16] + o[4][16] + the score tile per lane (~270 live floats: scratch under 256 registers).  Here the
+// operand residency is cut instead:
+//   * the score product walks the head dimension in two 64-channel halves: in half p the two k-slices of the MFMA are channels
+//     64p + [0, 32) and 64p + [32, 64), so a lane's K operand is one contiguous 32-float run that dies with its 32 MFMAs (the Q
+//     operand, 2 x 32 floats, is the only full-width operand that stays);
+//   * the rotation tables come in 16-byte pieces (rotate_chunks), never as whole runs;
+//   * the V^T operand is loaded one 32-channel group at a time, the next group's 16 loads in flight behind the current group's
+//     16 MFMAs (two 16-register buffers instead of four).
+// Live per lane: qu 64 + o 64 + score tile 16 + max(K run 32 + table pieces, V^T buffers 32) -- see DESIGN.md section 5 for the
+// compiler's figures.  Key masking, the chunk masks and the "no allowed key -> zero context" rule are those of rope_flash_t_kernel.
+template <int N>
+__device__ __forceinline__ void rotate_chunks(float (&x)[N], const float* __restrict__ cs, const float* __restrict__ sn) {
+#pragma unroll
+  for (int i = 0; i < N / 4; ++i) {
+    const float4 c = reinterpret_cast<const float4*>(cs)[i], g = reinterpret_cast<const float4*>(sn)[i];
+    const float x0 = x[4 * i], x1 = x[4 * i + 1], x2 = x[4 * i + 2], x3 = x[4 * i + 3];
+    x[4 * i] = x0 * c.x + x1 * g.x;
+    x[4 * i + 1] = x1 * c.y + x0 * g.y;
+    x[4 * i + 2] = x2 * c.z + x3 * g.z;
+    x[4 * i + 3] = x3 * c.w + x2 * g.w;
+    if (i % 2 == 1) {  // at most 16 table registers in flight: the rotated values are pinned (the arithmetic may not sink below) and
+                       // the scheduler may not lift the next pieces' loads above
+#pragma unroll
+      for (int e = 0; e < 8; ++e) sbk::pin(x[4 * i - 4 + e]);
+      sbk::sched_fence();
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256, 2) rope_flash_t128_kernel(AttnArgs a) {
+  constexpr int DH = 128, SEG = 32, NC = 4;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int jl = lane & 31, half = lane >> 5;
+  const int i0 = (blockIdx.x * 4 + wave) * 32, h = blockIdx.y, b = blockIdx.z;
+  const int T = a.T, d = a.H * DH;
+  if (i0 >= T) return;
+  const size_t row3 = (size_t)3 * d;
+  const unsigned row3u = 3u * d;  // (the launcher checks T * 3d < 2^30: offsets inside an utterance fit 32 bits)
+  const float* qkv_b = a.qkv + (size_t)b * T * row3 + (size_t)h * 3 * DH;
+  const int qrow = min(i0 + jl, T - 1);  // this lane's query (B operand column / output row)
+  const bool rot = a.pos != nullptr;     // no tables: plain scaled-dot-product attention (uniform for the launch)
+
+  float qu[2][SEG];  // channels 64p + 32*half + s of the query, rotated and scaled
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const int c0 = 64 * p + SEG * half;
+    load_run<SEG>(qu[p], qkv_b + (size_t)qrow * row3 + c0);
+    if (rot) rotate_chunks<SEG>(qu[p], a.pos + (size_t)qrow * DH + c0, a.bias_u + (size_t)qrow * DH + c0);
+#pragma unroll
+    for (int s = 0; s < SEG; ++s) qu[p][s] *= a.scale;
+  }
+
+  int klen = T;
+  if (a.key_len) klen = min(max(a.key_len[b], 1), T);
+  const int nkt = (klen + 31) / 32;
+  int lo, hi;  // allowed keys of this lane's query
+  key_range(a, qrow, klen, lo, hi);
+  int kt_begin = 0, kt_end = nkt;
+  if (a.chunk > 0) {
+    kt_end = min(nkt, ((min(i0 + 31, T - 1) / a.chunk + 1) * a.chunk + 31) / 32);
+    if (a.left >= 0) kt_begin = max(0, (i0 / a.chunk - a.left) * a.chunk) / 32;
+  }
+  float m_run = -INFINITY, l_run = 0.0f;
+  f32x16 o[NC];
+#pragma unroll
+  for (int ct = 0; ct < NC; ++ct)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[ct][r] = 0.0f;
+
+  for (int kt = kt_begin; kt < kt_end; ++kt) {
+    const int j0 = kt * 32;
+    const int krow = min(j0 + jl, T - 1);
+    f32x16 acc;  // S^T: row = key (r&3) + 8(r>>2) + 4*half of the tile, column = query jl
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int c0 = 64 * p + SEG * half;
+      float kreg[SEG];
+      load_run<SEG>(kreg, qkv_b + ((unsigned)krow * row3u + DH + c0));
+      if (rot) rotate_chunks<SEG>(kreg, a.pos + (size_t)krow * DH + c0, a.bias_u + (size_t)krow * DH + c0);
+#pragma unroll
+      for (int s = 0; s < SEG; ++s) acc = sbk::mfma_32x32x2(kreg[s], qu[p][s], acc);
+      sbk::sched_fence();
+    }
+    // V^T operand of one 32-channel group, in the key order of the accumulator registers
+    auto load_v = [&](int ct, float (&vv)[16]) {
+      unsigned t0 = j0 + 4 * half;
+      sbk::pin(t0);  // (the 16 row offsets are recomputed per group instead of living across the four groups)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const unsigned t = min(t0 + (r & 3) + 8 * (r >> 2), (unsigned)(T - 1));
+        vv[r] = qkv_b[t * row3u + (2 * DH + ct * 32 + jl)];
+      }
+    };
+    float vv[2][16];
+    load_v(0, vv[0]);  // (requested before the softmax)
+    float mx = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int key = j0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+      if (!(key >= lo && key < hi)) acc[r] = -INFINITY;
+      mx = fmaxf(mx, acc[r]);
+    }
+    mx = fmaxf(mx, sbk::shfl_xor(mx, 32));
+    const float m_new = fmaxf(m_run, mx);
+    const float alpha = m_new == -INFINITY ? 1.0f : expf(m_run - m_new);
+    float sum = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      acc[r] = acc[r] == -INFINITY ? 0.0f : expf(acc[r] - m_new);
+      sum += acc[r];
+    }
+    sum += sbk::shfl_xor(sum, 32);
+    l_run = l_run * alpha + sum;
+    m_run = m_new;
+    if (sbk::wave_any(alpha != 1.0f)) {  // (a new maximum is rare after the first tiles)
+#pragma unroll
+      for (int ct = 0; ct < NC; ++ct)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[ct][r] *= alpha;
+    }
+#pragma unroll
+    for (int ct = 0; ct < NC; ++ct) {
+      if (ct + 1 < NC) load_v(ct + 1, vv[(ct + 1) & 1]);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) o[ct] = sbk::mfma_32x32x2(vv[ct & 1][r], acc[r], o[ct]);
+    }
+  }
+  // O^T: column = this lane's query, row = channel (r&3) + 8(r>>2) + 4*half + 32*ct
+  if (i0 + jl < T) {
+    const float inv = l_run > 0.0f ? 1.0f / l_run : 0.0f;  // no allowed key at all: zero context
+    float* orow = a.out + ((size_t)b * T + i0 + jl) * d + h * DH;
+#pragma unroll
+    for (int ct = 0; ct < NC; ++ct)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)  // registers 4q .. 4q+3 are four consecutive channels: one 16-byte store
+        *reinterpret_cast<float4*>(orow + ct * 32 + 8 * q + 4 * half) =
+            make_float4(o[ct][4 * q] * inv, o[ct][4 * q + 1] * inv, o[ct][4 * q + 2] * inv, o[ct][4 * q + 3] * inv);
+  }
+}
+
 // RelPosMHAXL with the same transposed scores.  The position term BD[i][j] = (q_i + v) . p[T-1-i+j] is the one thing that
 // cannot stay in registers: G^T[r'][i] = p[rbase + r'] . (q_i + v) comes out of the MFMA with a lane owning one query
 // column, and the row that query needs for key j is r' = 31 - i + j -- a per-lane shift.  So G^T goes through a 64-row
@@ -898,6 +1041,19 @@ int launch_flash(const AttnArgs& a, hipStream_t st) {
   }
 }
 
+// head dim 128: the context only (the attention-weights output keeps the score strip in LDS next to 2 x 32 x 129 floats of Q -- not
+// instantiated at 128)
+int launch_flash128(const AttnArgs& a, hipStream_t st) {
+  if (a.attn)
+    return sbk::fail(SBK_EINVAL, "rope_attention: the attention-weights output is not instantiated for head_dim 128 (context only)");
+  if ((double)a.T * 3.0 * a.H * 128 >= 1073741824.0)
+    return sbk::fail(SBK_EINVAL, "rope_attention: head_dim 128 addresses an utterance's rows with 32-bit offsets: T * 3 * d must be < 2^30");
+  if (!sbk::aligned16(a.out)) return sbk::fail(SBK_EINVAL, "rope_attention: head_dim 128 writes 16-byte pieces: out must be 16-byte aligned");
+  sbk::ProfScope prof("rope_attention", 4.0 * a.B * a.H * (double)a.T * a.T * 128, 4.0 * a.B * a.T * (4.0 * a.H * 128), st);
+  SBK_LAUNCH(rope_flash_t128_kernel, dim3((a.T + 127) / 128, a.H, a.B), dim3(256), 0, st, a);
+  return sbk::launch_status("sbk_rope_attention_f32");
+}
+
 template <int DH, bool ROPE, bool PF, int NW>
 int launch_attn_pf(const AttnArgs& a, hipStream_t st);
 
@@ -952,12 +1108,13 @@ int rope_attention(const float* qkv, const float* cosines, const float* sines, c
   const int SP = ((T + 31) / 32) * 32 + 1;
   AttnArgs a{qkv, cosines, sines, nullptr, key_len, out, attn, B, T, H, SP, scale, chunk, left};
   switch (Dh) {
+    case 128: return launch_flash128(a, st);
     case 64: return launch_attn<64, true>(a, st);
     case 36: return launch_attn<36, true>(a, st);
     case 32: return launch_attn<32, true>(a, st);
     case 16: return launch_attn<16, true>(a, st);
     case 8: return launch_attn<8, true>(a, st);
-    default: return fail(SBK_EINVAL, "rope_attention: head_dim %d not instantiated (8,16,32,36,64)", Dh);
+    default: return fail(SBK_EINVAL, "rope_attention: head_dim %d not instantiated (8,16,32,36,64,128)", Dh);
   }
 }
 }  // namespace sbk

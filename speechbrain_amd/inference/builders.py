@@ -46,6 +46,32 @@ def build_modules(size="L", vocab=5000, seed=0, **override):
                 compute_features=fbank, cfg=cfg)
 
 
+# recipes/LibriSpeech/ASR/transformer/hparams/transformer.yaml: d_model 512, 4 heads (head dim 128), 12 + 6 layers
+TRANSFORMER = dict(d_model=512, nhead=4, d_ffn=2048, n_enc=12, n_dec=6, n_fft=400, win_length=25, cnn_channels=64)
+
+
+def build_transformer_modules(vocab=5000, seed=0, **override):
+    """The modules of the transformer.yaml recipe, random-initialised: the three-block front end (kernel sizes 5, 5, 1; strides 2,
+    2, 1; residuals F, F, T; 80 mels -> 20 x channels features), a pre-norm Transformer encoder (regularMHA, absolute positions)
+    and the pre-norm decoder.  ``build_asr(modules=...)`` wires them like the Conformer's."""
+    cfg = {**TRANSFORMER, **override}
+    torch.manual_seed(seed)
+    C = cfg["cnn_channels"]
+    cnn = ConvolutionFrontEnd(input_shape=(8, 10, 80), num_blocks=3, num_layers_per_block=1, out_channels=(C, C, C),
+                              kernel_sizes=(5, 5, 1), strides=(2, 2, 1), residuals=(False, False, True))
+    transformer = TransformerASR(input_size=20 * C, tgt_vocab=vocab, d_model=cfg["d_model"], nhead=cfg["nhead"],
+                                 num_encoder_layers=cfg["n_enc"], num_decoder_layers=cfg["n_dec"], d_ffn=cfg["d_ffn"],
+                                 dropout=0.1, activation=torch.nn.GELU, encoder_module="transformer",
+                                 attention_type="regularMHA", normalize_before=True, causal=False)
+    ctc_lin = Linear(input_size=cfg["d_model"], n_neurons=vocab)
+    seq_lin = Linear(input_size=cfg["d_model"], n_neurons=vocab)
+    normalize = InputNormalization(norm_type="global", update_until_epoch=4)
+    normalize.glob_mean, normalize.glob_std, normalize.count = torch.zeros(80), torch.ones(80), 1
+    fbank = Fbank(sample_rate=16000, n_fft=cfg["n_fft"], n_mels=80, win_length=cfg["win_length"])
+    return dict(CNN=cnn, Transformer=transformer, ctc_lin=ctc_lin, seq_lin=seq_lin, normalize=normalize,
+                compute_features=fbank, cfg=cfg)
+
+
 def build_asr(size="L", vocab=5000, seed=0, beam_size=10, ctc_weight=0.4, max_decode_ratio=1.0, min_decode_ratio=0.0,
               using_eos_threshold=False, greedy=False, device=None, tokenizer=None, modules=None, **override):
     """EncoderDecoderASR with the recipe's ``valid_search`` (beam 10 + CTC 0.4, conformer_large.yaml:225-239)."""

@@ -65,45 +65,88 @@ class ConvolutionalSpatialGatingUnit(torch.nn.Module):
 
 
 class ConvBlock(torch.nn.Module):
-    """conv(3x3, stride s, reflect 'same') -> LayerNorm(F',C') -> LeakyReLU -> Dropout, one HIP launch."""
+    """One fused HIP launch per block, for the block shapes of the ASR recipes (one layer per block):
+      (kernel_size, stride, residual) = (3, 2, False) / (5, 2, False): conv (reflect 'same') -> LayerNorm(F',C') -> LeakyReLU
+      (1, 1, True): LeakyReLU(LayerNorm(conv1x1(x))) + LayerNorm(reduce_conv1x1(x))       (transformer.yaml's third block)
+    State-dict keys as in the reference: convs.conv_0 / convs.norm_0 and, for the residual block, reduce_conv.conv / reduce_conv.norm."""
+
+    SHAPES = ((3, 2, False), (5, 2, False), (1, 1, True))
 
     def __init__(self, num_layers, out_channels, input_shape, kernel_size=3, stride=1, dilation=1, residual=False,
                  conv_module=Conv2d, activation=torch.nn.LeakyReLU, norm=LayerNorm, dropout=0.1, conv_bias=True,
                  padding="same", conv_init=None):
         super().__init__()
-        if num_layers != 1 or residual or dilation != 1 or kernel_size != 3 or stride != 2 or padding != "same":
-            raise NotImplementedError("MI355X ConvBlock implements the ASR recipe shape: one 3x3 stride-2 layer")
+        if num_layers != 1:
+            raise NotImplementedError(f"ConvBlock num_layers={num_layers}: one layer per block is implemented")
+        if dilation != 1:
+            raise NotImplementedError(f"ConvBlock dilation={dilation}: only dilation 1 is implemented")
+        if padding != "same":
+            raise NotImplementedError(f"ConvBlock padding={padding!r}: only 'same' (reflect) is implemented")
+        if (kernel_size, stride, bool(residual)) not in self.SHAPES:
+            raise NotImplementedError(f"ConvBlock (kernel_size, stride, residual) = ({kernel_size}, {stride}, {bool(residual)}): "
+                                      f"the fused kernels cover {self.SHAPES}")
         if conv_module is not Conv2d or norm is not LayerNorm or activation is not torch.nn.LeakyReLU:
             raise NotImplementedError("ConvBlock is fused for Conv2d + LayerNorm + LeakyReLU")
+        if not conv_bias:
+            raise NotImplementedError("ConvBlock conv_bias=False is not implemented")
         B, T, F = input_shape[0], input_shape[1], input_shape[2]
         cin = 1 if len(input_shape) == 3 else input_shape[3]
-        self.out_shape = (B, (T - 1) // 2 + 1, (F - 1) // 2 + 1, out_channels)
+        self.kernel_size, self.stride, self.residual = kernel_size, stride, bool(residual)
+        if stride == 2:  # get_padding_elem (nnet/CNN.py): kernel_size // 2 on each side -> (n - 1) // 2 + 1 for 3 and 5
+            self.out_shape = (B, None if T is None else (T - 1) // 2 + 1, (F - 1) // 2 + 1, out_channels)
+        else:
+            self.out_shape = (B, T, F, out_channels)
+        if self.residual and 256 % out_channels != 0:
+            raise NotImplementedError(f"residual ConvBlock out_channels={out_channels}: the fused kernel takes a divisor of 256")
         self.convs = _NamedChildren()
         self.convs["conv_0"] = Conv2d(out_channels, kernel_size, in_channels=cin, stride=stride, bias=conv_bias,
                                       conv_init=conv_init)
         self.convs["norm_0"] = LayerNorm(input_shape=self.out_shape)
         self.convs["act_0"] = activation()
         self.convs["dropout_0"] = torch.nn.Dropout(dropout)
+        self.reduce_conv = self.drop = None
+        if self.residual:
+            self.reduce_conv = _NamedChildren()
+            self.reduce_conv["conv"] = Conv2d(out_channels, 1, in_channels=cin, stride=stride)
+            self.reduce_conv["norm"] = LayerNorm(input_shape=self.out_shape)
+            self.drop = torch.nn.Dropout(dropout)
         self._wt_derived = native.Derived()
 
     def get_filter_properties(self):
-        """convolution.py:283-320: one 3-wide stride-2 layer per block."""
+        """convolution.py:283-320: the block's one layer."""
         from speechbrain_amd.utils.filter_analysis import FilterProperties
 
-        return FilterProperties(window_size=3, stride=2, dilation=1)
+        return FilterProperties(window_size=self.kernel_size, stride=self.stride, dilation=1)
 
     def _wt(self):
         w = self.convs["conv_0"].conv.weight
-        # [Cout,Cin,kF,kT] -> [(ci,kf,kt), Cout]: coalesced across output channels in the kernel
-        return self._wt_derived.get((w,), lambda: w.detach().permute(1, 2, 3, 0).reshape(-1, w.shape[0]).contiguous())
+        if self.residual:  # the two 1x1 weights [Cout,Cin,1,1] -> [Cin,Cout]
+            w2 = self.reduce_conv["conv"].conv.weight
+            return self._wt_derived.get((w, w2), lambda: (w.detach().reshape(w.shape[0], -1).t().contiguous(),
+                                                          w2.detach().reshape(w2.shape[0], -1).t().contiguous()))
+        if self.kernel_size == 3:
+            # [Cout,Cin,kF,kT] -> [(ci,kf,kt), Cout]: coalesced across output channels in the kernel
+            return self._wt_derived.get((w,), lambda: w.detach().permute(1, 2, 3, 0).reshape(-1, w.shape[0]).contiguous())
+        return self._wt_derived.get((w,), lambda: native.conv_block_weight(w, self.kernel_size))
 
     def forward(self, x):
         if x.dim() == 3:
             x = x.unsqueeze(-1)
         conv, norm = self.convs["conv_0"], self.convs["norm_0"]
-        return native.conv_block(x.contiguous(), self._wt(), conv.conv.bias, norm.norm.weight.reshape(-1),
-                                 norm.norm.bias.reshape(-1), conv.out_channels, eps=norm.eps,
-                                 slope=self.convs["act_0"].negative_slope)
+        slope = self.convs["act_0"].negative_slope
+        if self.residual:
+            w1t, w2t = self._wt()
+            rconv, rnorm = self.reduce_conv["conv"], self.reduce_conv["norm"]
+            return native.conv_block_res1x1(x.contiguous(), w1t, conv.conv.bias, norm.norm.weight.reshape(-1),
+                                            norm.norm.bias.reshape(-1), norm.eps, w2t, rconv.conv.bias,
+                                            rnorm.norm.weight.reshape(-1), rnorm.norm.bias.reshape(-1), rnorm.eps,
+                                            conv.out_channels, slope=slope)
+        if self.kernel_size == 3:
+            return native.conv_block(x.contiguous(), self._wt(), conv.conv.bias, norm.norm.weight.reshape(-1),
+                                     norm.norm.bias.reshape(-1), conv.out_channels, eps=norm.eps, slope=slope)
+        return native.conv_block_k(x.contiguous(), self._wt(), conv.conv.bias, norm.norm.weight.reshape(-1),
+                                   norm.norm.bias.reshape(-1), conv.out_channels, self.kernel_size, self.stride, eps=norm.eps,
+                                   slope=slope)
 
 
 class ConvolutionFrontEnd(torch.nn.ModuleDict):

@@ -7,6 +7,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
+from speechbrain_amd import native
 from speechbrain_amd.nnet.activations import Swish
 from speechbrain_amd.nnet.attention import MultiheadAttention, PositionalwiseFeedForward, RelPosEncXL
 from speechbrain_amd.nnet.embedding import Embedding
@@ -42,16 +43,22 @@ class NormalizedEmbedding(nn.Module):
 
 
 class TransformerEncoderLayer(nn.Module):
-    """Transformer.py:306-481 (regularMHA + regularFFN): holder of self_att / pos_ffn / norm1-2.  The
-    arithmetic on the path is the KV-cached TransformerLM step in csrc/search.hip (lm_step)."""
+    """Transformer.py:306-481 (regularMHA + regularFFN): self_att / pos_ffn / norm1-2 under the reference's names.
+
+    Two users.  TransformerLM reads the parameters only: its arithmetic is the KV-cached step in csrc/search.hip (lm_step).  The
+    Transformer ASR encoder (transformer.yaml) runs ``forward``: pre-norm  x + out_proj(MHA(norm1(x))), x + ffn(norm2(x));
+    post-norm  norm1(x + out_proj(MHA(x))), norm2(x + ffn(x)) -- LayerNorm written as the next contraction's operand, every
+    Linear one MFMA GEMM with bias / activation / residual in its epilogue, the attention one fused kernel
+    (native.rope_attention without rotation tables: plain scaled-dot-product attention with key-length masking)."""
 
     def __init__(self, d_ffn, nhead, d_model, kdim=None, vdim=None, dropout=0.0, activation=nn.ReLU,
                  normalize_before=False, attention_type="regularMHA", ffn_type="regularFFN",
                  ffn_cnn_kernel_size_list=[3, 3], causal=False):
         super().__init__()
-        if attention_type != "regularMHA" or ffn_type != "regularFFN":
-            raise NotImplementedError("TransformerEncoderLayer: only regularMHA + regularFFN (the TransformerLM "
-                                      "configuration) is implemented")
+        if attention_type != "regularMHA":
+            raise NotImplementedError(f"TransformerEncoderLayer attention_type={attention_type!r}: regularMHA is implemented")
+        if ffn_type != "regularFFN":
+            raise NotImplementedError(f"TransformerEncoderLayer ffn_type={ffn_type!r}: regularFFN is implemented")
         self.nhead = nhead
         self.self_att = MultiheadAttention(nhead=nhead, d_model=d_model, dropout=dropout, kdim=kdim, vdim=vdim)
         self.pos_ffn = PositionalwiseFeedForward(d_ffn=d_ffn, input_size=d_model, dropout=dropout, activation=activation)
@@ -60,6 +67,78 @@ class TransformerEncoderLayer(nn.Module):
         self.dropout1 = nn.Dropout(dropout)
         self.dropout2 = nn.Dropout(dropout)
         self.normalize_before = normalize_before
+        self.causal = causal
+        self.collect_attention = False  # attention maps are opt-in (they are [B,H,T,T] of HBM traffic)
+        self._in_proj_derived = native.Derived()
+
+    def _in_proj(self):
+        """torch's in_proj_weight / in_proj_bias are [q | k | v] by rows; the attention kernels read per-head (q|k|v): the rows
+        permuted once to (head, q|k|v, channel)."""
+        att = self.self_att.att
+        w, b, H = att.in_proj_weight, att.in_proj_bias, self.nhead
+        d = w.shape[1]
+        return self._in_proj_derived.get((w, b), lambda: (
+            w.detach().view(3, H, d // H, d).permute(1, 0, 2, 3).reshape(3 * d, d).contiguous(),
+            b.detach().view(3, H, d // H).permute(1, 0, 2).reshape(3 * d).contiguous()))
+
+    def _attend(self, qkv, key_len, out=None):
+        """qkv [B,T,3d] per-head interleaved -> (context [B,T,d], head-averaged weights [B,T,T] | None)."""
+        H, d = self.nhead, qkv.shape[-1] // 3
+        Dh = d // H
+        scale = 1.0 / math.sqrt(Dh)
+        if not self.collect_attention:
+            return native.rope_attention(qkv, None, None, key_len, H, scale, out=out)
+        if Dh == 128:
+            raise NotImplementedError("collect_attention with head_dim 128: the attention-weights output of the kernel is not "
+                                      "instantiated at 128 (the context is)")
+        # the weights come from the strip kernel, which takes rotation tables: the identity rotation
+        T = qkv.shape[1]
+        ones, zeros = torch.ones(T, Dh, device=qkv.device), torch.zeros(T, Dh, device=qkv.device)
+        ctx, attn = native.rope_attention(qkv, ones, zeros, key_len, H, scale, want_attn=True, out=out)
+        return ctx, attn.mean(1)  # (torch.nn.MultiheadAttention averages its weights over the heads)
+
+    def _check(self, src_mask):
+        if self.causal:
+            raise NotImplementedError("causal=True (a look-ahead mask in the encoder) is not implemented")
+        if src_mask is not None:
+            raise NotImplementedError("src_mask (causal / chunked attention masks) is not supported by the Transformer encoder")
+
+    def forward(self, src, src_mask: Optional[torch.Tensor] = None, src_key_padding_mask: Optional[torch.Tensor] = None,
+                pos_embs: Optional[torch.Tensor] = None, key_len=None):
+        self._check(src_mask)
+        if key_len is None and src_key_padding_mask is not None:
+            key_len = (~src_key_padding_mask).sum(-1, dtype=torch.int32)
+        B, T, d = src.shape
+        out, attn = self._layer(src.contiguous().view(B * T, d), [(0, B, T, key_len, 0)], want_attn=True)
+        return out.view(B, T, d), attn
+
+    def forward_group(self, x, segs):
+        """``forward`` over several independently padded batches laid end to end (x [M,d], segs = [(row0, B, T, key_len,
+        pos0)]): every row-wise launch covers all the batches at once, the attention runs per batch."""
+        self._check(None)
+        return self._layer(x, segs, want_attn=False)[0]
+
+    def _layer(self, x, segs, want_attn):
+        from speechbrain_amd.lobes.models.transformer.Conformer import _norm
+
+        att = self.self_att.att
+        w, b = self._in_proj()
+        d = x.shape[-1]
+        h = _norm(x, self.norm1.norm, w) if self.normalize_before else x
+        qkv = native.gemm_nt(h, w, b)
+        ctx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        attn = None
+        for row0, B, T, key_len, _ in segs:
+            _, a = self._attend(qkv[row0: row0 + B * T].view(B, T, 3 * d), key_len, out=ctx[row0: row0 + B * T].view(B, T, d))
+            attn = a if want_attn else None
+        x = native.gemm_nt(ctx, att.out_proj.weight, att.out_proj.bias, residual=x)
+        if not self.normalize_before:
+            x = self.norm1(x)
+        h = _norm(x, self.norm2.norm, self.pos_ffn.ffn[0].weight) if self.normalize_before else x
+        x = self.pos_ffn(h, residual=x)
+        if not self.normalize_before:
+            x = self.norm2(x)
+        return x, attn
 
 
 class TransformerEncoder(nn.Module):
@@ -79,6 +158,35 @@ class TransformerEncoder(nn.Module):
         self.norm = LayerNorm(d_model, eps=1e-6)
         self.layerdrop_prob = layerdrop_prob
         self.output_hidden_states = output_hidden_states
+
+    def forward(self, src, src_mask: Optional[torch.Tensor] = None, src_key_padding_mask: Optional[torch.Tensor] = None,
+                pos_embs: Optional[torch.Tensor] = None, dynchunktrain_config=None):
+        if dynchunktrain_config is not None:  # (the reference asserts, :622)
+            raise NotImplementedError("dynchunktrain_config: Dynamic Chunk Training unsupported for this encoder")
+        key_len = None
+        if src_key_padding_mask is not None:
+            key_len = (~src_key_padding_mask).sum(-1, dtype=torch.int32)
+        output = src
+        attention_lst = []
+        hidden = [output] if self.output_hidden_states else None
+        for layer in self.layers:
+            output, attention = layer(output, src_mask=src_mask, pos_embs=pos_embs, key_len=key_len)
+            attention_lst.append(attention)
+            if hidden is not None:
+                hidden.append(output)
+        output = self.norm(output)
+        if hidden is not None:
+            return output, attention_lst, hidden
+        return output, attention_lst
+
+    def forward_group(self, x, pos2d, segs, dynchunktrain_config=None):
+        """The layers + final norm over several independently padded batches laid end to end (see
+        TransformerEncoderLayer.forward_group); returns [M,d]."""
+        if dynchunktrain_config is not None:
+            raise NotImplementedError("dynchunktrain_config: Dynamic Chunk Training unsupported for this encoder")
+        for layer in self.layers:
+            x = layer.forward_group(x, segs)
+        return self.norm(x)
 
 
 class TransformerDecoderLayer(nn.Module):
@@ -117,8 +225,8 @@ class TransformerDecoder(nn.Module):
 
 
 class TransformerInterface(nn.Module):
-    """Transformer.py:35-250: encoder_module="conformer" + RelPosMHAXL | RoPEMHA or encoder_module="branchformer" +
-    RelPosMHAXL (TransformerASR), or encoder_module="transformer" + regularMHA (TransformerLM)."""
+    """Transformer.py:35-250: encoder_module="conformer" + RelPosMHAXL | RoPEMHA, encoder_module="branchformer" +
+    RelPosMHAXL or encoder_module="transformer" + regularMHA (TransformerASR: the transformer.yaml recipe; TransformerLM)."""
 
     def __init__(self, d_model=512, nhead=8, num_encoder_layers=6, num_decoder_layers=6, d_ffn=2048, dropout=0.1,
                  activation=nn.ReLU, custom_src_module=None, custom_tgt_module=None,
@@ -159,6 +267,9 @@ class TransformerInterface(nn.Module):
             self.positional_encoding_decoder = PositionalEncoding(d_model, max_length)
         if attention_type == "RoPEMHA":  # Transformer.py:171-174
             self.positional_encoding_decoder = PositionalEncoding(d_model, max_length)
+        if lm_like and num_decoder_layers > 0 and not normalize_before:
+            raise NotImplementedError("normalize_before=False with decoder layers: the KV-cached decode step implements the "
+                                      "pre-norm decoder (a post-norm encoder alone, num_decoder_layers=0, is implemented)")
         if num_encoder_layers > 0 and lm_like:
             if custom_src_module is not None:
                 self.custom_src_module = custom_src_module(d_model)

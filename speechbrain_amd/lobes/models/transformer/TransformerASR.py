@@ -80,6 +80,9 @@ class TransformerASR(TransformerInterface):
                  output_hidden_states=False, layerdrop_prob=0.0):
         if causal is None:
             causal = True
+        if encoder_module == "transformer" and attention_type == "regularMHA" and causal:
+            raise NotImplementedError("encoder_module='transformer' with causal=True (a look-ahead mask in the encoder) is not "
+                                      "implemented: pass causal=False, as transformer.yaml does")
         super().__init__(d_model=d_model, nhead=nhead, num_encoder_layers=num_encoder_layers,
                          num_decoder_layers=num_decoder_layers, d_ffn=d_ffn, dropout=dropout, activation=activation,
                          positional_encoding=positional_encoding, normalize_before=normalize_before,
@@ -101,9 +104,14 @@ class TransformerASR(TransformerInterface):
             if p.dim() > 1:
                 torch.nn.init.xavier_normal_(p)
 
+    def _no_chunks_for_regular_mha(self, dynchunktrain_config):
+        if dynchunktrain_config is not None and self.attention_type == "regularMHA":  # (before anything is launched)
+            raise NotImplementedError("dynchunktrain_config: Dynamic Chunk Training unsupported for the Transformer encoder")
+
     def encode(self, src, wav_len=None, pad_idx=0, dynchunktrain_config=None):
         """[B,T',F',C] or [B,T',F] -> [B,T',d] (TransformerASR.py:475-544).  ``dynchunktrain_config``: chunked
         attention + Dynamic Chunk Convolution (what a streaming-capable model is trained and evaluated with)."""
+        self._no_chunks_for_regular_mha(dynchunktrain_config)
         if src.dim() == 4:
             bz, t, ch1, ch2 = src.shape
             src = src.reshape(bz, t, ch1 * ch2)
@@ -111,7 +119,12 @@ class TransformerASR(TransformerInterface):
             src, None, wav_len, pad_idx=pad_idx, causal=self.causal, dynchunktrain_config=dynchunktrain_config)
         src = self.custom_src_module(src)
         # RoPEMHA rotates q/k inside the attention kernel; RelPosMHAXL takes the sinusoid table (:519-528)
-        pos_embs_source = None if self.attention_type == "RoPEMHA" else self.positional_encoding(src)
+        if self.attention_type == "regularMHA":  # src = src + positional_encoding(src) (:529-531)
+            if self.positional_encoding_type == "fixed_abs_sine":
+                src = src + self.positional_encoding.pe[:, : src.size(1)]
+            pos_embs_source = None
+        else:
+            pos_embs_source = None if self.attention_type == "RoPEMHA" else self.positional_encoding(src)
         outputs = self.encoder(src=src, src_mask=src_mask, src_key_padding_mask=src_key_padding_mask,
                                pos_embs=pos_embs_source, dynchunktrain_config=dynchunktrain_config)
         if self.output_hidden_states:
@@ -125,6 +138,7 @@ class TransformerASR(TransformerInterface):
         [[B_i], ...] -> [[B_i,T_i,d], ...].  The batches' rows are laid end to end so that every projection,
         feed-forward and LayerNorm of the encoder is ONE launch over all of them; each batch keeps its own padded
         length, key lengths and position table (results equal ``encode`` batch by batch)."""
+        self._no_chunks_for_regular_mha(dynchunktrain_config)
         if not hasattr(self.encoder, "forward_group") or self.output_hidden_states:
             return [self.encode(s, l, dynchunktrain_config=dynchunktrain_config) for s, l in zip(srcs, wav_lens)]
         flat, segs, tables, row0, pos0 = [], [], [], 0, 0
@@ -135,10 +149,14 @@ class TransformerASR(TransformerInterface):
                 key_len = torch.round(wav_len * T).to(torch.int32).clamp_(max=T)
             segs.append((row0, B, T, key_len, pos0))
             flat.append(src.reshape(B * T, -1))
-            if self.attention_type != "RoPEMHA":
+            if self.attention_type == "RelPosMHAXL":
                 tables.append(self.positional_encoding.make_pe(T).reshape(2 * T - 1, -1))
             row0, pos0 = row0 + B * T, pos0 + 2 * T - 1
         x = self.custom_src_module(torch.cat(flat, dim=0))
+        if self.attention_type == "regularMHA" and self.positional_encoding_type == "fixed_abs_sine":
+            # every batch's own positions, starting at 0
+            pe = self.positional_encoding.pe[0]
+            x = x + torch.cat([pe[:T].repeat(B, 1) for _, B, T, _, _ in segs], dim=0)
         pos2d = torch.cat(tables, dim=0) if tables else None
         y = self.encoder.forward_group(x, pos2d, segs, dynchunktrain_config=dynchunktrain_config)
         return [y[r0: r0 + B * T].view(B, T, -1) for r0, B, T, _, _ in segs]

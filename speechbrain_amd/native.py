@@ -177,6 +177,9 @@ def _declare(lib):
         "sbk_gemm_ln_nt_f32": ([p, i, p, i, p, p, i, p, i, i, i, i, f, i, f, p], c_int),
         "sbk_gemm_nt_splitk_f32": ([p, i, p, i, p, p, i, p, i, i, i, i, i, f, p, ctypes.c_size_t, p], c_int),
         "sbk_conv_block_f32": ([p, p, p, p, p, p, i, i, i, i, i, f, f, p], c_int),
+        "sbk_conv_block_k_layout": ([i, i, i], c_int),
+        "sbk_conv_block_k_f32": ([p, p, p, p, p, p, i, i, i, i, i, i, i, f, f, p], c_int),
+        "sbk_conv_block_res1x1_f32": ([p, p, p, p, p, f, p, p, p, p, f, p, i, i, i, i, i, f, p], c_int),
         "sbk_relpos_attention_f32": ([p, p, p, p, p, p, p, i, i, i, i, f, i, i, p], c_int),
         "sbk_rope_attention_f32": ([p, p, p, p, p, p, i, i, i, i, i, f, i, i, p], c_int),
         "sbk_rope_attention_bf16": ([p, p, p, p, p, i, i, i, i, i, f, i, i, p], c_int),
@@ -1133,6 +1136,44 @@ def conv_block(x, wt, bias, gamma, beta, cout, eps=1e-5, slope=0.01):
     return y
 
 
+def conv_block_weight(w, ksize):
+    """conv.weight [Cout,Cin,kF,kT] in the layout sbk_conv_block_k_f32 reads for this shape (sbk_conv_block_k_layout): the
+    tap-major rows [(ci,kf,kt), Cout] of conv_block, or the matrix-core panel [kt][kf][Cin/8][2][Cout][4]."""
+    cout, cin = w.shape[0], w.shape[1]
+    w = w.detach()
+    if load().sbk_conv_block_k_layout(cin, cout, int(ksize)) == 1:
+        return w.permute(3, 2, 1, 0).reshape(ksize, ksize, cin // 8, 2, 4, cout).permute(0, 1, 2, 3, 5, 4).contiguous()
+    return w.permute(1, 2, 3, 0).reshape(-1, cout).contiguous()
+
+
+def conv_block_k(x, wt, bias, gamma, beta, cout, ksize, stride, eps=1e-5, slope=0.01):
+    """A ConvolutionFrontEnd block with a ksize x ksize stride-2 kernel ((3, 2) or (5, 2)): x [B,T,F,Cin] -> [B,T',F',Cout];
+    ``wt`` = conv_block_weight(conv.weight, ksize) (see include/sbk.h)."""
+    lib = load()
+    _dev_ok(x, wt, bias, gamma, beta)
+    _f32(x)
+    B, Tin, Fin, Cin = x.shape
+    Tout, Fout = (Tin - 1) // 2 + 1, (Fin - 1) // 2 + 1
+    y = torch.empty(B, Tout, Fout, cout, dtype=torch.float32, device=x.device)
+    _chk(lib.sbk_conv_block_k_f32(_p(x), _p(wt), _p(bias), _p(gamma), _p(beta), _p(y), B, Tin, Fin, Cin, cout, int(ksize),
+                                  int(stride), float(eps), float(slope), _stream(x)), "sbk_conv_block_k_f32")
+    return y
+
+
+def conv_block_res1x1(x, w1t, b1, gamma1, beta1, eps1, w2t, b2, gamma2, beta2, eps2, cout, slope=0.01):
+    """The residual 1x1 ConvBlock in one launch: LeakyReLU(LN(conv_0(x))) + LN(reduce_conv(x)); x [B,T,F,Cin] -> [B,T,F,Cout],
+    w1t / w2t [Cin,Cout]."""
+    lib = load()
+    _dev_ok(x, w1t, b1, gamma1, beta1, w2t, b2, gamma2, beta2)
+    _f32(x)
+    B, T, F, Cin = x.shape
+    y = torch.empty(B, T, F, cout, dtype=torch.float32, device=x.device)
+    _chk(lib.sbk_conv_block_res1x1_f32(_p(x), _p(w1t), _p(b1), _p(gamma1), _p(beta1), float(eps1), _p(w2t), _p(b2), _p(gamma2),
+                                       _p(beta2), float(eps2), _p(y), B, T, F, Cin, cout, float(slope), _stream(x)),
+         "sbk_conv_block_res1x1_f32")
+    return y
+
+
 def relpos_attention(qkv, pos, bias_u, bias_v, key_len, H, scale, want_attn=False, chunk_size=0, left_chunks=-1,
                      out=None):
     """qkv [B,T,3*d] (per-head interleaved), pos [2T-1,d] -> context [B,T,d] (+ weights [B,H,T,T]).
@@ -1271,12 +1312,19 @@ class DecoderHandle:
                 ca_out=(L.multihead_attn.att.out_proj.weight, L.multihead_attn.att.out_proj.bias),
                 ln3=(L.norm3.norm.weight, L.norm3.norm.bias), ff1=(L.pos_ffn.ffn[0].weight, L.pos_ffn.ffn[0].bias),
                 ff2=(L.pos_ffn.ffn[3].weight, L.pos_ffn.ffn[3].bias)))
-        pe = model.positional_encoding_decoder.pe
+        pe = self._decoder_pe(model)
         self._build(layers, emb=model.custom_tgt_module.layers[0].emb.Embedding.weight,
                     pe=pe.reshape(pe.shape[-2], pe.shape[-1]), final_ln=(dec.norm.norm.weight, dec.norm.norm.bias),
                     seq=(seq_lin.w.weight, seq_lin.w.bias) if seq_lin is not None else None, nhead=dec.layers[0].nhead,
                     ffn_act=dec.layers[-1].pos_ffn.act_code, ln_eps=dec.norm.eps, emb_scale=0.0, fold=fold)
         self.key = self.source_key(model, seq_lin)
+
+    @staticmethod
+    def _decoder_pe(model):
+        """The absolute table the target positions come from: positional_encoding_decoder where the encoder's attention type
+        replaced positional_encoding (RelPosMHAXL, RoPEMHA), else positional_encoding itself (regularMHA; TransformerASR.py:449-457)."""
+        holder = getattr(model, "positional_encoding_decoder", None)
+        return (holder if holder is not None else model.positional_encoding).pe
 
     @classmethod
     def from_tensors(cls, layers, emb, pe, final_ln, seq, nhead, ffn_act, ln_eps, emb_scale, fold=True, key=None):
@@ -1348,7 +1396,7 @@ class DecoderHandle:
         """``source_key`` of every tensor the handle was derived from (the folded LayerNorm copies go stale with them)."""
         src = list(model.decoder.parameters())
         src.append(model.custom_tgt_module.layers[0].emb.Embedding.weight)
-        src.append(model.positional_encoding_decoder.pe)
+        src.append(DecoderHandle._decoder_pe(model))
         if seq_lin is not None:
             src.extend(seq_lin.parameters())
         return source_key(src)
