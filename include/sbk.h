@@ -428,6 +428,36 @@ int sbk_glu_dwconv_f32(const float* h, const float* w, const float* bias, float*
 int sbk_csgu_f32(const float* h, const float* gamma, const float* beta, float eps, const float* w, const float* bias,
                  float* y, float* stats, int B, int T, int C, int ksize, int gate_act, sbk_stream_t stream);
 
+/* ---- wav2vec 2.0 (csrc/wav2vec2.hip; additive entries, ABI 11 unchanged) ---------------------------------------------------
+ * Layer 0 of the feature encoder, over the raw waveform wav [B,N] (C_in = 1, kernel k <= 16, stride s <= k, T0 = (N-k)/s + 1):
+ *   x'       = (wav - mu_b) * r_b with wstat[b] = {mu_b, r_b} (F.layer_norm over the whole padded row), or wav (wstat NULL)
+ *   c[t,ch]  = bias[ch] + sum_j w[ch,j] * x'[t*s + j]                     (w [C0,k]; bias may be NULL)
+ *   mode 1   = GroupNorm(C0, C0): (c - mean[b,ch]) * rstd[b,ch] * gamma[ch] + beta[ch], statistics over all T0 frames of the
+ *              padded row, read from cstat [B,C0,2] (T0 <= 32: taken from the values themselves, cstat unused);   mode 2 = LayerNorm over the C0 channels of a frame (gamma, beta, eps)
+ *   y[b,t,ch] = GELU(norm(c))   -> y [B,T0,C0] time-major, written once.  C0 <= 1024.
+ * sbk_w2v_conv0_stats_f32 produces the statistics WITHOUT forming c: wstat [B,2] = mean and 1/sqrt(var + wav_eps) of every
+ * row (written whenever wstat is given) and, when w is given, cstat [B,C0,2] of the convolution of x' (x' = wav unless
+ * `normalize`), from the mean vector and the centred covariance of the stride-s windows (fp64 accumulation).  workspace:
+ * sbk_w2v_conv0_stats_workspace_bytes(B, N, k, s) bytes of 8-byte aligned device memory (scratch, no initial contents). */
+size_t sbk_w2v_conv0_stats_workspace_bytes(int B, int N, int k, int s);
+int sbk_w2v_conv0_stats_f32(const float* wav, const float* w, const float* bias, int normalize, float wav_eps, float eps,
+                            float* wstat, float* cstat, void* workspace, size_t workspace_bytes, int B, int N, int C0, int k,
+                            int s, sbk_stream_t stream);
+int sbk_w2v_conv0_f32(const float* wav, const float* wstat, const float* w, const float* bias, int mode, const float* cstat,
+                      const float* gamma, const float* beta, float eps, float* y, int B, int N, int C0, int k, int s,
+                      sbk_stream_t stream);
+/* The positional convolution with its residual:  xm = x [B,T,d] with the frames >= key_len[b] zeroed (key_len NULL: none; x
+ * itself is not modified);  y = xm + GELU(conv(xm) + bias), conv = Conv1d(d, d, k, padding k/2, groups G) without the last
+ * frame when k is even.  w [d, k * d/G] is the effective (weight-normalised) filter TAP-MAJOR: w[o][j * cg + i] = W[o][i][j].
+ * With gamma / beta (both or neither) LayerNorm_d(y; gamma, beta, eps) is what is written.  d/G in {16,32,48,64}, k <= 128,
+ * any T; x and w 16-byte aligned; y may be a view but not x. */
+int sbk_w2v_posconv_f32(const float* x, const int32_t* key_len, const float* w, const float* bias, const float* gamma,
+                        const float* beta, float eps, float* y, int B, int T, int d, int G, int k, sbk_stream_t stream);
+
+/* The wrapper's output_norm: y[r] = (x[r] - mean_r) / sqrt(var_r + eps) over the n values of each of `rows` rows (an utterance's
+ * whole [T', d] block; biased variance, no affine).  y may be x. */
+int sbk_w2v_utt_norm_f32(const float* x, float* y, int rows, long n, float eps, sbk_stream_t stream);
+
 /* ---- CTC decoding (csrc/ctc_decode.hip; additive entries, ABI 11 unchanged) ---------------------------------------------
  * ctc_greedy_decode (decoders/ctc.py:335-380): x [B,T,V] (log-)probabilities, rel_len [B] relative lengths (device; NULL =
  * 1.0).  Utterance b uses its first int(round(fp32(rel_len[b] * T))) frames (round half to even, as torch.round); per frame

@@ -15,6 +15,7 @@ __device__ __forceinline__ float act_f(float v, int act) {
   if (act == SBK_ACT_SWISH) return v / (1.0f + expf(-v));
   if (act == SBK_ACT_LEAKY_RELU) return v > 0.0f ? v : 0.01f * v;
   if (act == SBK_ACT_RELU) return v > 0.0f ? v : 0.0f;
+  if (act == SBK_ACT_GELU) return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));  // (the wav2vec 2.0 feature encoder)
   return v;
 }
 

@@ -185,6 +185,11 @@ def _declare(lib):
         "sbk_rope_attention_bf16": ([p, p, p, p, p, i, i, i, i, i, f, i, i, p], c_int),
         "sbk_glu_dwconv_f32": ([p, p, p, p, i, i, i, i, i, p], c_int),
         "sbk_csgu_f32": ([p, p, p, f, p, p, p, p, i, i, i, i, i, p], c_int),
+        "sbk_w2v_conv0_stats_workspace_bytes": ([i, i, i, i], ctypes.c_size_t),
+        "sbk_w2v_conv0_stats_f32": ([p, p, p, i, f, f, p, p, p, ctypes.c_size_t, i, i, i, i, i, p], c_int),
+        "sbk_w2v_conv0_f32": ([p, p, p, p, i, p, p, p, f, p, i, i, i, i, i, p], c_int),
+        "sbk_w2v_posconv_f32": ([p, p, p, p, p, p, f, p, i, i, i, i, i, p], c_int),
+        "sbk_w2v_utt_norm_f32": ([p, p, i, ctypes.c_long, f, p], c_int),
         "sbk_layernorm_f32": ([p, p, p, p, i, i, f, i, p], c_int),
         "sbk_log_softmax_f32": ([p, p, i, i, f, f, p], c_int),
         "sbk_ctc_greedy_decode_f32": ([p, p, p, p, i, i, i, i, p], c_int),
@@ -1273,6 +1278,78 @@ def csgu(h, gamma, beta, eps, w, bias, ksize, gate_act=ACT_NONE, out=None):
     stats = torch.empty(B * T * 2, dtype=torch.float32, device=h.device)
     _chk(lib.sbk_csgu_f32(_p(h), _p(gamma), _p(beta), float(eps), _p(w), _p(bias), _p(y), _p(stats), B, T, C2 // 2, ksize,
                           int(gate_act), _stream(h)), "sbk_csgu_f32")
+    return y
+
+
+# ------------------------------------------------------------------ wav2vec 2.0 (csrc/wav2vec2.hip)
+W2V_GROUP_NORM, W2V_LAYER_NORM = 1, 2  # the ``mode`` of w2v_conv0
+W2V_POSCONV_GROUP_WIDTHS = (16, 32, 48, 64)  # the instantiations of the positional convolution
+W2V_CONV0_MAX_KERNEL, W2V_POSCONV_MAX_KERNEL = 16, 128
+
+
+def w2v_conv0(wav, w, bias, gamma, beta, stride, mode, eps=1e-5, normalize=False, wav_eps=1e-5, out=None):
+    """Layer 0 of the wav2vec 2.0 feature encoder: wav [B,N] -> GELU(norm(conv(wav))) [B,T0,C0], time-major.  w [C0,k] (the
+    Conv1d weight without its unit input-channel axis), bias [C0] or None; ``mode`` W2V_GROUP_NORM (GroupNorm(C0, C0): the
+    statistics of every (utterance, channel) over the T0 frames of the padded row, from a statistics launch that does not form
+    the activation) or W2V_LAYER_NORM (over the channels of a frame); gamma / beta [C0].  ``normalize``: the feature
+    extractor's F.layer_norm over every padded row, applied on load."""
+    lib = load()
+    _dev_ok(wav, w, bias, gamma, beta, out)
+    _f32(wav), _f32(w)
+    B, N = wav.shape
+    C0, k = w.shape
+    s = int(stride)
+    if not (1 <= s <= k <= W2V_CONV0_MAX_KERNEL):
+        raise SbkError(f"w2v_conv0: kernel {k} / stride {s} (1 <= stride <= kernel <= {W2V_CONV0_MAX_KERNEL})")
+    if N < k:
+        raise SbkError(f"w2v_conv0: N={N} samples are fewer than the kernel's {k}")
+    if mode not in (W2V_GROUP_NORM, W2V_LAYER_NORM):
+        raise SbkError(f"w2v_conv0: mode {mode}")
+    T0 = (N - k) // s + 1
+    y = out if out is not None else torch.empty(B, T0, C0, dtype=torch.float32, device=wav.device)
+    wstat = cstat = None
+    if normalize or mode == W2V_GROUP_NORM:
+        wstat = torch.empty(B, 2, dtype=torch.float32, device=wav.device) if normalize else None
+        cstat = torch.empty(B, C0, 2, dtype=torch.float32, device=wav.device) if mode == W2V_GROUP_NORM else None
+        nbytes = lib.sbk_w2v_conv0_stats_workspace_bytes(B, N, k, s)
+        ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=wav.device)
+        _chk(lib.sbk_w2v_conv0_stats_f32(_p(wav), _p(w) if cstat is not None else None, _p(bias), int(bool(normalize)),
+                                         float(wav_eps), float(eps), _p(wstat), _p(cstat), _p(ws), nbytes, B, N, C0, k, s,
+                                         _stream(wav)), "sbk_w2v_conv0_stats_f32")
+    _chk(lib.sbk_w2v_conv0_f32(_p(wav), _p(wstat), _p(w), _p(bias), int(mode), _p(cstat), _p(gamma), _p(beta), float(eps),
+                               _p(y), B, N, C0, k, s, _stream(wav)), "sbk_w2v_conv0_f32")
+    return y
+
+
+def w2v_posconv(x, key_len, w, bias, groups, ksize, ln=None, out=None):
+    """x [B,T,d] -> mask(x) + GELU(grouped_conv(mask(x)) + bias), the positional convolution of wav2vec 2.0 with its residual;
+    ``mask`` zeroes the frames >= key_len[b] (int32 [B] or None) on read -- ``x`` is left as it is.  w [d, ksize * d/groups]:
+    the effective filter tap-major (w[o, j * cg + i] = W[o, i, j]).  ``ln`` = (gamma, beta, eps): LayerNorm over d on the way
+    out.  ``out`` may be a view (of anything but ``x``)."""
+    lib = load()
+    gamma, beta, eps = ln if ln is not None else (None, None, 0.0)
+    _dev_ok(x, key_len, w, bias, gamma, beta, out)
+    _f32(x), _f32(w)
+    B, T, d = x.shape
+    groups, ksize = int(groups), int(ksize)
+    if d % groups or d // groups not in W2V_POSCONV_GROUP_WIDTHS:
+        raise SbkError(f"w2v_posconv: group width {d}/{groups} not instantiated {W2V_POSCONV_GROUP_WIDTHS}")
+    if not (1 <= ksize <= W2V_POSCONV_MAX_KERNEL) or tuple(w.shape) != (d, ksize * (d // groups)):
+        raise SbkError(f"w2v_posconv: {ksize} taps (1..{W2V_POSCONV_MAX_KERNEL}) with a weight {tuple(w.shape)}")
+    y = out if out is not None else torch.empty(B, T, d, dtype=torch.float32, device=x.device)
+    _chk(lib.sbk_w2v_posconv_f32(_p(x), _p(key_len), _p(w), _p(bias), _p(gamma), _p(beta), float(eps), _p(y), B, T, d, groups,
+                                 ksize, _stream(x)), "sbk_w2v_posconv_f32")
+    return y
+
+
+def w2v_utt_norm(x, eps=1e-5):
+    """F.layer_norm(x, x.shape[-2:]) without affine: every [T', d] block of x [..., T', d] over all of its values."""
+    lib = load()
+    _dev_ok(x)
+    _f32(x)
+    n = x.shape[-2] * x.shape[-1]
+    y = torch.empty_like(x)
+    _chk(lib.sbk_w2v_utt_norm_f32(_p(x), _p(y), x.numel() // n if n else 0, n, float(eps), _stream(x)), "sbk_w2v_utt_norm_f32")
     return y
 
 

@@ -1,4 +1,4 @@
-"""speechbrain.nnet.activations mirror: only what the Conformer path instantiates."""
+"""speechbrain.nnet.activations mirror: only what the ASR paths instantiate."""
 import torch
 
 
@@ -15,6 +15,26 @@ class Swish(torch.nn.Module):
 
     def forward(self, x):
         raise RuntimeError("Swish is fused into the HIP epilogues; it is never called stand-alone on this path")
+
+
+class Softmax(torch.nn.Module):
+    """nnet/activations.py:16-86 -- the ``log_softmax`` of the wav2vec 2.0 CTC recipes is ``Softmax(apply_log=True)``: over the
+    last dimension, on sbk_log_softmax_f32.  (The reference's reshape of 3-d / 4-d inputs changes nothing for the last dim.)"""
+
+    def __init__(self, apply_log=False, dim=-1, reshape=True, dtype=torch.float32):
+        super().__init__()
+        if not apply_log:
+            raise NotImplementedError("Softmax(apply_log=False): only the log form has a kernel (the CTC heads use it)")
+        if dtype != torch.float32:
+            raise NotImplementedError(f"Softmax(dtype={dtype}): fp32 only")
+        self.apply_log, self.dim, self.reshape, self.dtype = apply_log, dim, reshape, dtype
+
+    def forward(self, x):
+        from speechbrain_amd import native
+
+        if self.dim not in (-1, x.dim() - 1):
+            raise NotImplementedError(f"Softmax over dim {self.dim} of a {x.dim()}-d tensor: last dimension only")
+        return native.log_softmax(x.contiguous())
 
 
 class NativeLogSoftmax(torch.nn.Module):
