@@ -458,6 +458,22 @@ int sbk_w2v_posconv_f32(const float* x, const int32_t* key_len, const float* w, 
  * whole [T', d] block; biased variance, no affine).  y may be x. */
 int sbk_w2v_utt_norm_f32(const float* x, float* y, int rows, long n, float eps, sbk_stream_t stream);
 
+/* ---- WavLM (csrc/wavlm.hip; additive entries, ABI 11 unchanged) ------------------------------------------------------------
+ * Self-attention with the gated relative-position bias of transformers' WavLMAttention fused into the flash kernel:
+ *   p      = gate_w x[b,i,h*Dh:(h+1)*Dh] + gate_b          gate_w [8,Dh], gate_b [8]: gru_rel_pos_linear, shared by the heads
+ *   ga, gb = sigmoid(p0+p1+p2+p3), sigmoid(p4+p5+p6+p7)
+ *   gate   = ga * (gb * gate_const[h] - 1) + 2             gate_const [H]: gru_rel_pos_const
+ *   s[i,j] = scale * q_i.k_j + gate * tab[h, j - i + T - 1]   for the keys j < key_len[b] (int32 [B], or NULL: every key)
+ *   out_i  = softmax_j(s[i,:]) V
+ * qkv [B,T,H,3*Dh] per-head interleaved as sbk_rope_attention_f32 reads it; x [B,T,H*Dh] the hidden states the attention module
+ * received; tab [H,2T-1]: tab[h, r + T - 1] = the bias of the relative position r = key - query; out [B,T,H*Dh].  Every query
+ * row is computed, the ones past key_len[b] too.  Dh in {16,32,64}; T <= sbk_wavlm_attention_max_frames() (the head's table row
+ * is staged in 64 KiB of LDS: 8177); qkv, x and gate_w 16-byte aligned.  fp32; no chunk mask, no attention-weights output. */
+int sbk_wavlm_attention_max_frames(void);
+int sbk_wavlm_attention_f32(const float* qkv, const float* x, const float* gate_w, const float* gate_b, const float* gate_const,
+                            const float* tab, const int32_t* key_len, float* out, int B, int T, int H, int Dh, float scale,
+                            sbk_stream_t stream);
+
 /* ---- CTC decoding (csrc/ctc_decode.hip; additive entries, ABI 11 unchanged) ---------------------------------------------
  * ctc_greedy_decode (decoders/ctc.py:335-380): x [B,T,V] (log-)probabilities, rel_len [B] relative lengths (device; NULL =
  * 1.0).  Utterance b uses its first int(round(fp32(rel_len[b] * T))) frames (round half to even, as torch.round); per frame

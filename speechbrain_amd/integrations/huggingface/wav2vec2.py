@@ -52,9 +52,9 @@ class _FeatureEncoder(nn.Module):
 
 
 class _FeatureProjection(nn.Module):
-    def __init__(self, cfg):
+    def __init__(self, cfg, layer_norm=True):
         super().__init__()
-        self.layer_norm = nn.LayerNorm(cfg["conv_dim"][-1], eps=cfg["layer_norm_eps"])
+        self.layer_norm = nn.LayerNorm(cfg["conv_dim"][-1], eps=cfg["layer_norm_eps"]) if layer_norm else None
         self.projection = nn.Linear(cfg["conv_dim"][-1], cfg["hidden_size"])
 
 
@@ -122,21 +122,22 @@ class _FeedForward(nn.Module):
 
 
 class _EncoderLayer(nn.Module):
-    def __init__(self, cfg):
+    def __init__(self, cfg, attention):
         super().__init__()
         d, eps = cfg["hidden_size"], cfg["layer_norm_eps"]
-        self.attention = _Attention(d, cfg["num_attention_heads"])
+        self.attention = attention
         self.layer_norm = nn.LayerNorm(d, eps=eps)
         self.feed_forward = _FeedForward(d, cfg["intermediate_size"])
         self.final_layer_norm = nn.LayerNorm(d, eps=eps)
 
 
 class _Encoder(nn.Module):
-    def __init__(self, cfg):
+    def __init__(self, cfg, new_attention):
+        """``new_attention(cfg, i)``: the attention module of layer i."""
         super().__init__()
         self.pos_conv_embed = _PosConvEmbedding(cfg)
         self.layer_norm = nn.LayerNorm(cfg["hidden_size"], eps=cfg["layer_norm_eps"])
-        self.layers = nn.ModuleList([_EncoderLayer(cfg) for _ in range(cfg["num_hidden_layers"])])
+        self.layers = nn.ModuleList([_EncoderLayer(cfg, new_attention(cfg, i)) for i in range(cfg["num_hidden_layers"])])
 
 
 _DEFAULTS = dict(hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072, hidden_act="gelu",
@@ -146,13 +147,15 @@ _DEFAULTS = dict(hidden_size=768, num_hidden_layers=12, num_attention_heads=12, 
                  mask_time_prob=0.05, mask_feature_prob=0.0, add_adapter=False)
 
 
-def _checked_config(cfg):
+def _checked_config(cfg, family="wav2vec 2.0", head_dims=ATTENTION_HEAD_DIMS):
+    """The config over the defaults, or NotImplementedError / ValueError naming what the kernels do not take.  ``family`` names
+    the model in the messages; ``head_dims``: the instantiations of the family's attention kernel."""
     cfg = {**_DEFAULTS, **cfg}
     if cfg["add_adapter"]:
-        raise NotImplementedError("wav2vec 2.0 with add_adapter (the convolutional adapter after the encoder)")
+        raise NotImplementedError(f"{family} with add_adapter (the convolutional adapter after the encoder)")
     for key in ("hidden_act", "feat_extract_activation"):
         if cfg[key] != "gelu":
-            raise NotImplementedError(f"wav2vec 2.0 with {key}={cfg[key]!r}: activations other than GELU are not fused")
+            raise NotImplementedError(f"{family} with {key}={cfg[key]!r}: activations other than GELU are not fused")
     if cfg["feat_extract_norm"] not in ("group", "layer"):
         raise ValueError(f"feat_extract_norm={cfg['feat_extract_norm']!r}: 'group' or 'layer'")
     d, G, H = cfg["hidden_size"], cfg["num_conv_pos_embedding_groups"], cfg["num_attention_heads"]
@@ -161,8 +164,8 @@ def _checked_config(cfg):
                                   f"{native.W2V_POSCONV_GROUP_WIDTHS}")
     if cfg["num_conv_pos_embeddings"] > native.W2V_POSCONV_MAX_KERNEL:
         raise NotImplementedError(f"positional-conv kernel size {cfg['num_conv_pos_embeddings']} > {native.W2V_POSCONV_MAX_KERNEL}")
-    if d % H or d // H not in ATTENTION_HEAD_DIMS:
-        raise NotImplementedError(f"attention head dim {d}/{H}: the attention kernel is instantiated for {ATTENTION_HEAD_DIMS}")
+    if d % H or d // H not in head_dims:
+        raise NotImplementedError(f"attention head dim {d}/{H}: the attention kernel is instantiated for {head_dims}")
     k0, s0 = cfg["conv_kernel"][0], cfg["conv_stride"][0]
     if not (1 <= s0 <= k0 <= native.W2V_CONV0_MAX_KERNEL) or cfg["conv_dim"][0] > 1024:
         raise NotImplementedError(f"first convolution kernel {k0} / stride {s0} / {cfg['conv_dim'][0]} channels: the waveform "
@@ -171,16 +174,33 @@ def _checked_config(cfg):
 
 
 class Wav2Vec2Model(nn.Module):
-    """The parameter tree of HuggingFace's Wav2Vec2Model and its forward on the kernels."""
+    """The parameter tree of HuggingFace's Wav2Vec2Model and its forward on the kernels.  The HuBERT and WavLM models
+    (hubert.py, wavlm.py) are this class with ``check_config``, ``projection_layer_norm``, ``new_attention`` and ``attend``
+    of their own."""
+
+    def check_config(self, cfg):
+        return _checked_config(cfg)
+
+    def projection_layer_norm(self, cfg):
+        """feature_projection.layer_norm exists (and runs)."""
+        return True
+
+    def new_attention(self, cfg, layer):
+        return _Attention(cfg["hidden_size"], cfg["num_attention_heads"])
+
+    def attend(self, att, a, qkv, key_len):
+        """The attention step of one layer: ``a`` [B,T',d] the hidden states the attention module received, ``qkv`` their stacked
+        projection -> context [B,T',d]."""
+        return native.rope_attention(qkv, None, None, key_len, att.num_heads, att.head_dim ** -0.5)[0]
 
     def __init__(self, cfg):
         super().__init__()
-        self.config = cfg = _checked_config(cfg)
+        self.config = cfg = self.check_config(cfg)
         if cfg["mask_time_prob"] > 0.0 or cfg["mask_feature_prob"] > 0.0:  # (present in the state dict; SpecAugment is training)
             self.masked_spec_embed = nn.Parameter(torch.empty(cfg["hidden_size"]).uniform_())
         self.feature_extractor = _FeatureEncoder(cfg)
-        self.feature_projection = _FeatureProjection(cfg)
-        self.encoder = _Encoder(cfg)
+        self.feature_projection = _FeatureProjection(cfg, self.projection_layer_norm(cfg))
+        self.encoder = _Encoder(cfg, self.new_attention)
 
     def feat_lengths(self, n):
         """_get_feat_extract_output_lengths."""
@@ -223,7 +243,9 @@ class Wav2Vec2Model(nn.Module):
             n = torch.where(n <= 0, torch.full_like(n, T), n).clamp(max=T)  # (HuggingFace marks frame n-1: index -1 is the last)
             key_len = n.to(device=wav.device, dtype=torch.int32)
         fp, enc = self.feature_projection, self.encoder
-        h = native.layernorm(feats, fp.layer_norm.weight, fp.layer_norm.bias, fp.layer_norm.eps)
+        h = feats
+        if fp.layer_norm is not None:
+            h = native.layernorm(feats, fp.layer_norm.weight, fp.layer_norm.bias, fp.layer_norm.eps)
         h = native.gemm_nt(h, fp.projection.weight, fp.projection.bias)
         stable = bool(cfg["do_stable_layer_norm"])
         pc = enc.pos_conv_embed.conv
@@ -238,7 +260,7 @@ class Wav2Vec2Model(nn.Module):
             ln1, ln2 = layer.layer_norm, layer.final_layer_norm
             a = native.layernorm(x, ln1.weight, ln1.bias, ln1.eps) if stable else x
             qkv = native.gemm_nt(a, w_in, b_in)
-            ctx, _ = native.rope_attention(qkv, None, None, key_len, att.num_heads, att.head_dim ** -0.5)
+            ctx = self.attend(att, a, qkv, key_len)
             x = native.gemm_nt(ctx, att.out_proj.weight, att.out_proj.bias, residual=x)
             if stable:
                 f = native.layernorm(x, ln2.weight, ln2.bias, ln2.eps)
@@ -268,6 +290,10 @@ def _rename_weight_norm(state, prefix=""):
     return state
 
 
+# HuggingFace model_type -> the wrapper that runs it
+_WRAPPERS = {"wav2vec2": "wav2vec2.Wav2Vec2", "hubert": "hubert.HuBERT", "wavlm": "wavlm.WavLM"}
+
+
 class Wav2Vec2(nn.Module):
     """speechbrain.integrations.huggingface.wav2vec2.Wav2Vec2 on the MI355X kernels.
 
@@ -275,6 +301,8 @@ class Wav2Vec2(nn.Module):
     pytorch_model.bin); nothing is downloaded.  ``forward(wav, wav_lens)`` / ``extract_features(wav, wav_lens)`` return what the
     reference returns: the last hidden state [B,T',d], or with ``output_all_hiddens`` the stack [layers+1,B,T',d]; with
     ``output_norm`` normalised over each utterance's [T',d] block (padded frames included, as the reference does)."""
+
+    MODEL, MODEL_TYPE = Wav2Vec2Model, "wav2vec2"  # (the model class; config.json's model_type = the checkpoint's key prefix)
 
     def __init__(self, source, save_path=None, output_norm=False, freeze=False, freeze_feature_extractor=False,
                  apply_spec_augment=False, output_all_hiddens=False, **kwargs):
@@ -285,9 +313,10 @@ class Wav2Vec2(nn.Module):
             raise NotImplementedError("apply_spec_augment: SpecAugment inside the encoder is a training-time option")
         with open(os.path.join(source, "config.json")) as f:
             cfg = json.load(f)
-        if cfg.get("model_type", "wav2vec2") != "wav2vec2":
-            raise NotImplementedError(f"model_type {cfg['model_type']!r}: the HuBERT and WavLM wrappers are not implemented; "
-                                      "this class runs wav2vec 2.0 checkpoints")
+        kind = cfg.get("model_type", self.MODEL_TYPE)
+        if kind != self.MODEL_TYPE:  # (every wrapper runs its own model type only: the parameter trees differ)
+            hint = f" — load it with speechbrain.integrations.huggingface.{_WRAPPERS[kind]}" if kind in _WRAPPERS else ""
+            raise NotImplementedError(f"{type(self).__name__}: model_type {kind!r}{hint}")
         self.normalize_wav = False
         pp = os.path.join(source, "preprocessor_config.json")
         if os.path.exists(pp):
@@ -295,7 +324,8 @@ class Wav2Vec2(nn.Module):
                 self.normalize_wav = bool(json.load(f).get("do_normalize", True))
         self._setup(cfg, output_norm, freeze, freeze_feature_extractor, output_all_hiddens)
         own = self.model.state_dict()
-        state = {(k[len("wav2vec2."):] if k.startswith("wav2vec2.") else k): v for k, v in _read_checkpoint(source).items()}
+        pre = self.MODEL_TYPE + "."
+        state = {(k[len(pre):] if k.startswith(pre) else k): v for k, v in _read_checkpoint(source).items()}
         state = {k: v.float() for k, v in _rename_weight_norm(state).items() if k in own}  # (heads of task models are not ours)
         missing = sorted(set(own) - set(state) - {"masked_spec_embed"})
         if missing:
@@ -303,7 +333,7 @@ class Wav2Vec2(nn.Module):
         self.model.load_state_dict(state, strict=False)
 
     def _setup(self, cfg, output_norm, freeze, freeze_feature_extractor, output_all_hiddens):
-        self.model = Wav2Vec2Model(cfg)
+        self.model = self.MODEL(cfg)
         self.output_norm, self.freeze, self.freeze_feature_extractor = output_norm, freeze, freeze_feature_extractor
         self.output_all_hiddens = output_all_hiddens
         for p in self.model.parameters():  # inference path: parameters are constants

@@ -10,6 +10,7 @@ from __future__ import annotations
 import collections
 import contextlib
 import ctypes
+import math
 import os
 import threading
 import weakref
@@ -190,6 +191,8 @@ def _declare(lib):
         "sbk_w2v_conv0_f32": ([p, p, p, p, i, p, p, p, f, p, i, i, i, i, i, p], c_int),
         "sbk_w2v_posconv_f32": ([p, p, p, p, p, p, f, p, i, i, i, i, i, p], c_int),
         "sbk_w2v_utt_norm_f32": ([p, p, i, ctypes.c_long, f, p], c_int),
+        "sbk_wavlm_attention_max_frames": ([], c_int),
+        "sbk_wavlm_attention_f32": ([p, p, p, p, p, p, p, p, i, i, i, i, f, p], c_int),
         "sbk_layernorm_f32": ([p, p, p, p, i, i, f, i, p], c_int),
         "sbk_log_softmax_f32": ([p, p, i, i, f, f, p], c_int),
         "sbk_ctc_greedy_decode_f32": ([p, p, p, p, i, i, i, i, p], c_int),
@@ -1351,6 +1354,70 @@ def w2v_utt_norm(x, eps=1e-5):
     y = torch.empty_like(x)
     _chk(lib.sbk_w2v_utt_norm_f32(_p(x), _p(y), x.numel() // n if n else 0, n, float(eps), _stream(x)), "sbk_w2v_utt_norm_f32")
     return y
+
+
+# ------------------------------------------------------------------ WavLM (csrc/wavlm.hip)
+WAVLM_HEAD_DIMS = (16, 32, 64)  # the instantiations of the gated relative-position attention
+
+
+def wavlm_attention(qkv, x, gate_w, gate_b, gate_const, tab, key_len, H, scale, out=None):
+    """WavLM's self-attention: qkv [B,T,3*d] (per-head interleaved), x [B,T,d] the hidden states the attention module received,
+    gate_w [8,Dh] / gate_b [8] (gru_rel_pos_linear), gate_const [H] (gru_rel_pos_const, any shape of H values), tab [H,2T-1]
+    (``wavlm_bias_table``) -> context [B,T,d].  score = scale * q.k + gate(x)[b,h,i] * tab[h, j - i + T - 1] over the keys
+    j < key_len[b]; no [T,T] tensor is formed."""
+    lib = load()
+    _dev_ok(qkv, x, gate_w, gate_b, gate_const, tab, key_len, out)
+    _f32(qkv), _f32(x), _f32(gate_w), _f32(tab)
+    B, T, d3 = qkv.shape
+    d = d3 // 3
+    Dh = d // H
+    if Dh not in WAVLM_HEAD_DIMS:
+        raise NotImplementedError(f"wavlm_attention: head dim {d}/{H} not instantiated {WAVLM_HEAD_DIMS}")
+    max_t = lib.sbk_wavlm_attention_max_frames()
+    if T > max_t:
+        raise SbkError(f"wavlm_attention: T={T} frames exceed the {max_t} whose bias table row fits the kernel's 64 KiB of LDS")
+    if tuple(x.shape) != (B, T, d) or tuple(gate_w.shape) != (8, Dh) or gate_b.numel() != 8 or gate_const.numel() != H \
+            or (T and tuple(tab.shape) != (H, 2 * T - 1)):
+        raise SbkError(f"wavlm_attention: x {tuple(x.shape)}, gate_w {tuple(gate_w.shape)}, gate_b {tuple(gate_b.shape)}, "
+                       f"gate_const {tuple(gate_const.shape)}, tab {tuple(tab.shape)} for B={B} T={T} H={H} Dh={Dh}")
+    _f32(gate_b), _f32(gate_const)
+    if out is None:
+        out = torch.empty(B, T, d, dtype=torch.float32, device=qkv.device)
+    _chk(lib.sbk_wavlm_attention_f32(_p(qkv), _p(x), _p(gate_w), _p(gate_b), _p(gate_const), _p(tab), _p(key_len), _p(out),
+                                     B, T, H, Dh, float(scale), _stream(qkv)), "sbk_wavlm_attention_f32")
+    return out
+
+
+def wavlm_relative_buckets(rel, num_buckets, max_distance):
+    """transformers' WavLMAttention._relative_positions_bucket on an int64 CPU tensor of relative positions (key - query): half
+    the buckets per sign, exact below num_buckets/4, logarithmic up to max_distance, then saturated.  float32 on the host, the
+    reference's operation order: the bucket edges do not depend on a device's ``log``."""
+    nb = num_buckets // 2
+    buckets = (rel > 0).to(torch.long) * nb
+    rel = torch.abs(rel)
+    max_exact = nb // 2
+    large = torch.log(rel.float() / max_exact)
+    large = large / math.log(max_distance / max_exact)
+    large = large * (nb - max_exact)
+    large = (max_exact + large).to(torch.long)
+    large = torch.min(large, torch.full_like(large, nb - 1))
+    return buckets + torch.where(rel < max_exact, rel, large)
+
+
+def wavlm_bias_table(rel_attn_embed_weight, T, num_buckets, max_distance, derived=None):
+    """rel_attn_embed.weight [num_buckets, H] -> tab [H, 2T-1] on the weight's device: tab[h, r + T - 1] =
+    weight[bucket(r), h] for r = key - query in [-(T-1), T-1] (= compute_bias(T, T)[h, i, i + r]).  ``derived``: a
+    ``Derived`` to cache it in, keyed on the parameter and (T, num_buckets, max_distance)."""
+    w = rel_attn_embed_weight
+
+    def build():
+        idx = wavlm_relative_buckets(torch.arange(-(T - 1), T, dtype=torch.long), num_buckets, max_distance)
+        return w.detach().float().t().contiguous()[:, idx.to(w.device)].contiguous()
+
+    if derived is None:
+        with torch.no_grad():
+            return build()
+    return derived.get((w,), build, extra=(int(T), int(num_buckets), int(max_distance)))
 
 
 # ------------------------------------------------------------------ decoder / searchers

@@ -172,7 +172,9 @@ BEAM_DECODING = """test_beam_search:
 decoding_function: !name:speechbrain.decoders.ctc.CTCBeamSearcher"""
 
 
-def pretrained_ctc_tiny(hub):
+def pretrained_ctc_tiny(hub, family="wav2vec2", wrapper=None, yaml=CTC_YAML, seeds=(23, 24)):
+    """pretrained_<family>_ctc_tiny/ and its _expected.npz around the reference wrapper ``wrapper(hub, output_norm=True)``
+    (default: ``ref_wrapper``); ``seeds``: of the head's initialisation and of the batch's noise."""
     from speechbrain.dataio.encoder import CTCTextEncoder
     from speechbrain.decoders.ctc import CTCBeamSearcher, ctc_greedy_decode
     from speechbrain.inference.ASR import EncoderASR
@@ -181,18 +183,18 @@ def pretrained_ctc_tiny(hub):
     from speechbrain.nnet.containers import LengthsCapableSequential
     from speechbrain.nnet.linear import Linear
 
-    out_dir = os.path.join(OUT, "pretrained_wav2vec2_ctc_tiny")
+    out_dir = os.path.join(OUT, f"pretrained_{family}_ctc_tiny")
     shutil.rmtree(out_dir, ignore_errors=True)
     os.makedirs(out_dir)
-    w2v = ref_wrapper(hub, output_norm=True)
-    torch.manual_seed(23)
+    w2v = (wrapper or ref_wrapper)(hub, output_norm=True)
+    torch.manual_seed(seeds[0])
     enc = VanillaNN(input_shape=[None, None, 96], activation=torch.nn.LeakyReLU, dnn_blocks=2, dnn_neurons=48)
     ctc_lin = Linear(input_size=48, n_neurons=31)
     model = torch.nn.ModuleList([enc, ctc_lin]).eval()
     import speechbrain.dataio.dataio as sbio
 
     sig = sbio.read_audio(os.path.join(OUT, "ref_spk1_snt1.wav"))
-    g = torch.Generator().manual_seed(24)
+    g = torch.Generator().manual_seed(seeds[1])
     n = 12000
     wav = torch.zeros(3, n)
     lens = torch.tensor([1.0, 0.8, 0.55])
@@ -228,7 +230,7 @@ def pretrained_ctc_tiny(hub):
     tok.save(os.path.join(out_dir, "tokenizer.ckpt"))
     for name, dec in (("hyperparams.yaml", GREEDY_DECODING), ("hyperparams_beam.yaml", BEAM_DECODING)):
         with open(os.path.join(out_dir, name), "w", encoding="utf-8") as f:
-            f.write(CTC_YAML.replace("%DECODING%", dec))
+            f.write(yaml.replace("%DECODING%", dec))
 
     greedy = EncoderASR(modules={"encoder": encoder}, hparams={
         "tokenizer": tok, "decoding_function": functools.partial(ctc_greedy_decode, blank_id=0)}, run_opts={"device": "cpu"})
@@ -258,7 +260,7 @@ def pretrained_ctc_tiny(hub):
     pad = lambda toks, T: np.array([t + [-1] * (T - len(t)) for t in toks], dtype=np.int64)  # noqa: E731
     model_keys = [[k, list(v.shape)] for k, v in model.state_dict().items()]
     print("  model.ckpt keys:", [k for k, _ in model_keys])
-    np.savez_compressed(os.path.join(OUT, "pretrained_wav2vec2_ctc_tiny_expected.npz"), wav=wav.numpy(), lens=lens.numpy(),
+    np.savez_compressed(os.path.join(OUT, f"pretrained_{family}_ctc_tiny_expected.npz"), wav=wav.numpy(), lens=lens.numpy(),
                         logp=logp.numpy(), greedy_words=np.array(g_words), greedy_tokens=pad(g_tokens, logp.shape[1]),
                         beam_words=np.array(b_words), file_logp=file_logp.numpy(), file_greedy_words=np.array(f_words),
                         file_greedy_tokens=pad(f_tokens, file_logp.shape[1]), file_beam_words=np.array(fb_words),
