@@ -234,6 +234,10 @@ def _declare(lib):
 
 
 EXPORTS: tuple = ()
+# path -> (CDLL, its exports): ONE object per loaded library for the life of the process.  dlopen hands every load of a path the
+# same library (one table of stream workspaces inside it), and _ws_key identifies the library by this object: a second CDLL of
+# the same path would register -- and keep -- a second ~134 MB workspace per stream for the same table.
+_LIBS: dict = {}
 
 
 def load(path: Optional[str] = None):
@@ -242,17 +246,19 @@ def load(path: Optional[str] = None):
     if _lib is not None and path is None:
         return _lib
     path = path or LIB_PATH
-    if not os.path.exists(path):
-        raise SbkError(
-            f"{path} is missing: the MI355X kernels are not built. Run `python -m speechbrain_amd.csrc.build` "
-            "(hipcc, gfx950). There is no CPU fallback."
-        )
-    lib = ctypes.CDLL(path)
-    EXPORTS = tuple(_declare(lib).keys())
-    if lib.sbk_abi_version() != 11:
-        raise SbkError(f"ABI version mismatch: {lib.sbk_abi_version()}")
-    _lib = lib
-    return lib
+    if path not in _LIBS:
+        if not os.path.exists(path):
+            raise SbkError(
+                f"{path} is missing: the MI355X kernels are not built. Run `python -m speechbrain_amd.csrc.build` "
+                "(hipcc, gfx950). There is no CPU fallback."
+            )
+        lib = ctypes.CDLL(path)
+        exports = tuple(_declare(lib).keys())
+        if lib.sbk_abi_version() != 11:
+            raise SbkError(f"ABI version mismatch: {lib.sbk_abi_version()}")
+        _LIBS[path] = (lib, exports)
+    _lib, EXPORTS = _LIBS[path]
+    return _lib
 
 
 # name -> key of the library's tuning switches (include/sbk.h, enum sbk_knob: SBK_KNOB_<NAME>)

@@ -282,10 +282,11 @@ def test_rope_attention_kernel_variants(backend, T, lens, chunk):
     assert _md(plain, ref) <= 5e-6
 
 
-@pytest.mark.parametrize("B,T,d,ks", [(2, 50, 32, 31), (1, 70, 72, 31), (1, 33, 144, 7)])
+@pytest.mark.parametrize("B,T,d,ks", [(2, 50, 32, 31), (1, 70, 72, 31), (1, 33, 144, 7), (1, 40, 80, 15)])
 def test_glu_dwconv(backend, B, T, d, ks):
     nat, dev = backend
-    h, w, b = torch.randn(B, T, 2 * d), torch.randn(d, ks) * 0.2, torch.randn(d)
+    g = torch.Generator().manual_seed(T + d)
+    h, w, b = torch.randn(B, T, 2 * d, generator=g), torch.randn(d, ks, generator=g) * 0.2, torch.randn(d, generator=g)
     ref = F.conv1d(F.glu(h.transpose(1, 2), dim=1), w.unsqueeze(1), b, padding=(ks - 1) // 2, groups=d).transpose(1, 2)
     assert _md(nat.glu_dwconv(h.to(dev), w.to(dev), b.to(dev), ks), ref) <= 1e-5
 
@@ -956,6 +957,21 @@ def test_no_stream_workspace_is_an_error_not_an_allocation(backend):
         nat._stream(a)  # registered again
     assert call() == 0
     assert _md(out, (a.double().cpu() @ w.double().cpu().t()).float()) <= 2e-6 * float((a.abs().double().cpu() @ w.abs().double().cpu().t()).max()) + 1e-5
+
+
+def test_loading_the_library_again_keeps_its_stream_workspace(backend):
+    """native.load() of a path already loaded returns the SAME library object, so the stream's registered workspace is found again
+    (_ws_key identifies the library by that object).  A fresh ctypes.CDLL per load registered -- and kept -- another ~134 MB
+    workspace per stream every time this suite's `backend` fixture switched libraries: 280 GiB after 2 100 gpu tests."""
+    nat, dev = backend
+    x = torch.zeros(4).to(dev)
+    lib = nat.load()
+    nat._stream(x)
+    keys = set(nat._STREAM_WS)
+    nat._lib = None  # what tests/emu_utils.py detach() / attach() do between two tests
+    assert nat.load(lib._name) is lib and nat.load() is lib
+    nat._stream(x)
+    assert set(nat._STREAM_WS) == keys
 
 
 _CONCURRENT_FIRST_CALLS = """
