@@ -474,6 +474,27 @@ int sbk_wavlm_attention_f32(const float* qkv, const float* x, const float* gate_
                             const float* tab, const int32_t* key_len, float* out, int B, int T, int H, int Dh, float scale,
                             sbk_stream_t stream);
 
+/* ---- HyperMixing (csrc/hypermix.hip; additive entries, ABI 11 unchanged) -------------------------------------------------
+ * The token mixer of the HyperConformer recipes (nnet/hypermixing.py: HyperMixing, untied, multi-head) with the LayerNorm
+ * behind it and the layer's skip fused.  d = H*Dh; per head m the generators g = 1, 2 are fc1 [H,Dh,Dh], b1 [H,Dh],
+ * fc2 [H,k,Dh], b2 [H,k] (w1_* / w2_*):
+ *   u[t]   = h[b,t] for t < key_len[b] (int32 [B], or NULL: every frame), else 0;      p[t] = u[t] + pe[t]    pe [T,d]
+ *   W_g[t] = GELU(p[t,m] fc1_g[m]^T + b1_g[m]) fc2_g[m]^T + b2_g[m]  for t < key_len[b], else 0            [k]   (erf GELU)
+ *   A      = GELU(sum_t u[t,m]^T W_1[t])  [Dh,k];     y[t,m] = A W_2[t];     out = LayerNorm_d(y; ln_w, ln_b, eps) + residual
+ * h, out, residual (or NULL) [B,T,d].  Rows t >= key_len[b] come out as ln_b + residual; what h holds there is never read.
+ * W_1 / W_2 are not formed: the kernels contract over k once per (utterance, head), not per frame (hypermix.hip).  The only
+ * intermediates are [B,H,Dh,Dh+1] matrices in `workspace` (sbk_hypermix_workspace_bytes(B,T,H,Dh) bytes, 4-byte aligned,
+ * the caller's; contents undefined before and after).  The time axis is summed in ceil(T / sbk_hypermix_split_frames())
+ * pieces combined in order: a function of T alone, no atomics, two runs are bit-identical.
+ * Limits: Dh <= 64, k <= 256, T <= 3000, d <= 1024.  out may alias residual, not h. */
+int sbk_hypermix_split_frames(void);
+size_t sbk_hypermix_workspace_bytes(int B, int T, int H, int Dh);
+int sbk_hypermix_f32(const float* h, const int32_t* key_len, const float* pe, const float* w1_fc1_w, const float* w1_fc1_b,
+                     const float* w1_fc2_w, const float* w1_fc2_b, const float* w2_fc1_w, const float* w2_fc1_b,
+                     const float* w2_fc2_w, const float* w2_fc2_b, const float* ln_w, const float* ln_b, float eps,
+                     const float* residual, float* out, void* workspace, size_t workspace_bytes, int B, int T, int H, int Dh,
+                     int k, sbk_stream_t stream);
+
 /* ---- CTC decoding (csrc/ctc_decode.hip; additive entries, ABI 11 unchanged) ---------------------------------------------
  * ctc_greedy_decode (decoders/ctc.py:335-380): x [B,T,V] (log-)probabilities, rel_len [B] relative lengths (device; NULL =
  * 1.0).  Utterance b uses its first int(round(fp32(rel_len[b] * T))) frames (round half to even, as torch.round); per frame

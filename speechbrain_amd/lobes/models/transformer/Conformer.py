@@ -15,6 +15,7 @@ import torch.nn as nn
 from speechbrain_amd import native
 from speechbrain_amd.nnet.activations import Swish
 from speechbrain_amd.nnet.attention import PositionalwiseFeedForward, RelPosMHAXL, RoPEMHA, _act_code
+from speechbrain_amd.nnet.hypermixing import HyperMixing
 from speechbrain_amd.nnet.normalization import LayerNorm
 
 
@@ -114,8 +115,13 @@ class ConformerEncoderLayer(nn.Module):
             self.mha_layer = RelPosMHAXL(num_heads=nhead, embed_dim=d_model, dropout=dropout, mask_pos_future=causal)
         elif attention_type == "RoPEMHA":
             self.mha_layer = RoPEMHA(num_heads=nhead, embed_dim=d_model, dropout=dropout)
+        elif attention_type == "hypermixing":
+            if causal:
+                raise NotImplementedError("attention_type='hypermixing' with causal=True is not implemented")
+            self.mha_layer = HyperMixing(input_output_dim=d_model, hypernet_size=d_ffn, tied=False, num_heads=nhead,
+                                         fix_tm_hidden_size=False)
         else:
-            raise NotImplementedError(f"attention_type={attention_type}: RelPosMHAXL and RoPEMHA are implemented")
+            raise NotImplementedError(f"attention_type={attention_type}: RelPosMHAXL, RoPEMHA and hypermixing are implemented")
         self.attention_type = attention_type
         self.convolution_module = ConvolutionModule(d_model, kernel_size, bias, activation, dropout, causal=causal)
         self.ffn_module1 = nn.Sequential(
@@ -148,6 +154,7 @@ class ConformerEncoderLayer(nn.Module):
         attention kernel gets the chunk geometry instead of a [T,T] tensor; other masks are not supported."""
         if src_mask is not None and dynchunktrain_config is None:
             raise NotImplementedError("src_mask without dynchunktrain_config (causal masks) is a training-time feature")
+        self._hypermixing_refusals(dynchunktrain_config)
         if key_len is None and src_key_padding_mask is not None:
             key_len = (~src_key_padding_mask).sum(-1, dtype=torch.int32)
         chunk = dynchunktrain_config.kernel_args() if dynchunktrain_config is not None else (0, -1)
@@ -157,8 +164,22 @@ class ConformerEncoderLayer(nn.Module):
         y = self._ffn(self.ffn_module2, x)
         return native.layernorm(y, self.norm2.norm.weight, self.norm2.norm.bias, self.norm2.eps), attn
 
+    def _hypermixing_refusals(self, dynchunktrain_config=None):
+        """What HyperMixing cannot do, by name and before anything is launched."""
+        if self.attention_type != "hypermixing":
+            return
+        if dynchunktrain_config is not None:
+            raise NotImplementedError("dynchunktrain_config with attention_type='hypermixing': HyperMixing mixes over the "
+                                      "whole utterance, Dynamic Chunk Training is not implemented for it")
+        if self.collect_attention:
+            raise NotImplementedError("collect_attention=True with attention_type='hypermixing': HyperMixing has no attention "
+                                      "map")
+
     def _mha(self, x, pos_embs, key_len, chunk=(0, -1)):
         """x + MHA(norm1(x))."""
+        if self.attention_type == "hypermixing":  # x + LayerNorm(mix(norm1(x))): the mixer's own norm and the skip are fused
+            ln = self.norm1.norm
+            return self.mha_layer.core(native.layernorm(x, ln.weight, ln.bias, ln.eps), key_len, residual=x), None
         h = _norm(x, self.norm1.norm, self.mha_layer.in_proj_weight)
         if self.attention_type == "RoPEMHA":
             return self.mha_layer.core(h, key_len, residual=x, want_attn=self.collect_attention, chunk=chunk)
@@ -170,12 +191,22 @@ class ConformerEncoderLayer(nn.Module):
         tables end to end, segs = [(row0, B, T, key_len, pos0)]): every row-wise launch (LayerNorms, projections,
         feed-forward) covers all the batches at once -- large GEMMs whose tiles fill the chip -- and only the two
         kernels that see the time axis (attention, depthwise convolution) run per batch."""
+        self._hypermixing_refusals(dynchunktrain_config)
         chunk = dynchunktrain_config.kernel_args() if dynchunktrain_config is not None else (0, -1)
         x = self._ffn(self.ffn_module1, x)
-        h = _norm(x, self.norm1.norm, self.mha_layer.in_proj_weight)
-        if self.attention_type == "RoPEMHA":
+        if self.attention_type == "hypermixing":  # one call per batch, with that batch's T and key lengths
+            ln, d = self.norm1.norm, x.shape[-1]
+            h = native.layernorm(x, ln.weight, ln.bias, ln.eps)
+            y = torch.empty_like(x)
+            for row0, B, T, key_len, _ in segs:
+                rows = slice(row0, row0 + B * T)
+                self.mha_layer.core(h[rows].view(B, T, d), key_len, residual=x[rows].view(B, T, d), out=y[rows].view(B, T, d))
+            x = y
+        elif self.attention_type == "RoPEMHA":
+            h = _norm(x, self.norm1.norm, self.mha_layer.in_proj_weight)
             x = self.mha_layer.core_group(h, segs, residual=x, chunk=chunk)
         else:
+            h = _norm(x, self.norm1.norm, self.mha_layer.in_proj_weight)
             x = self.mha_layer.core_group(h, pos2d, segs, residual=x, chunk=chunk)
         x = self.convolution_module.forward_group(x, segs, dynchunktrain_config=dynchunktrain_config)
         y = self._ffn(self.ffn_module2, x)
@@ -185,6 +216,8 @@ class ConformerEncoderLayer(nn.Module):
         """One chunk through the layer with the left-context caches of ``context`` (Conformer.py:501-586): the MHA
         runs unmasked over (cached inputs | chunk), the convolution module over (cached inputs | chunk), and the
         outputs of the cached frames are dropped."""
+        if self.attention_type == "hypermixing":
+            raise NotImplementedError("streaming with attention_type='hypermixing' is not implemented")
         orig_len = x.shape[-2]
         x = self._ffn(self.ffn_module1, x.contiguous())
         if context.mha_left_context is not None:
@@ -203,6 +236,8 @@ class ConformerEncoderLayer(nn.Module):
         return native.layernorm(y, self.norm2.norm.weight, self.norm2.norm.bias, self.norm2.eps), attn
 
     def make_streaming_context(self, mha_left_context_size: int):
+        if self.attention_type == "hypermixing":
+            raise NotImplementedError("streaming with attention_type='hypermixing' is not implemented")
         return ConformerEncoderLayerStreamingContext(mha_left_context_size=mha_left_context_size)
 
 

@@ -225,7 +225,7 @@ class TransformerDecoder(nn.Module):
 
 
 class TransformerInterface(nn.Module):
-    """Transformer.py:35-250: encoder_module="conformer" + RelPosMHAXL | RoPEMHA, encoder_module="branchformer" +
+    """Transformer.py:35-250: encoder_module="conformer" + RelPosMHAXL | RoPEMHA | hypermixing, encoder_module="branchformer" +
     RelPosMHAXL or encoder_module="transformer" + regularMHA (TransformerASR: the transformer.yaml recipe; TransformerLM)."""
 
     def __init__(self, d_model=512, nhead=8, num_encoder_layers=6, num_decoder_layers=6, d_ffn=2048, dropout=0.1,
@@ -255,11 +255,17 @@ class TransformerInterface(nn.Module):
                 raise NotImplementedError("encoder_module='branchformer' with use_linear_after_conv=True is not implemented")
             if causal:
                 raise NotImplementedError("encoder_module='branchformer' with causal=True is not implemented")
-        elif not lm_like and (encoder_module != "conformer" or attention_type not in ("RelPosMHAXL", "RoPEMHA") or causal):
+        elif not lm_like and (encoder_module != "conformer" or attention_type not in ("RelPosMHAXL", "RoPEMHA", "hypermixing")
+                              or causal):
+            if attention_type == "hypermixing" and encoder_module == "transformer":
+                raise NotImplementedError("encoder_module='transformer' with attention_type='hypermixing' is not implemented: "
+                                          "hypermixing runs in encoder_module='conformer'")
+            if attention_type == "hypermixing" and encoder_module == "conformer":
+                raise NotImplementedError("attention_type='hypermixing' with causal=True is not implemented")
             raise NotImplementedError(
-                "implemented: encoder_module='conformer' with attention_type='RelPosMHAXL' | 'RoPEMHA', causal=False and "
-                "encoder_module='branchformer' with attention_type='RelPosMHAXL' (ASR); encoder_module='transformer' with "
-                "attention_type='regularMHA' (TransformerLM)")
+                "implemented: encoder_module='conformer' with attention_type='RelPosMHAXL' | 'RoPEMHA' | 'hypermixing', "
+                "causal=False and encoder_module='branchformer' with attention_type='RelPosMHAXL' (ASR); "
+                "encoder_module='transformer' with attention_type='regularMHA' (TransformerLM)")
         if positional_encoding == "fixed_abs_sine":
             self.positional_encoding = PositionalEncoding(d_model, max_length)
         if attention_type == "RelPosMHAXL":

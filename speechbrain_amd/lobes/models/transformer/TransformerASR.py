@@ -105,6 +105,9 @@ class TransformerASR(TransformerInterface):
                 torch.nn.init.xavier_normal_(p)
 
     def _no_chunks_for_regular_mha(self, dynchunktrain_config):
+        if dynchunktrain_config is not None and self.attention_type == "hypermixing":  # (before anything is launched)
+            raise NotImplementedError("dynchunktrain_config with attention_type='hypermixing': HyperMixing mixes over the "
+                                      "whole utterance, Dynamic Chunk Training is not implemented for it")
         if dynchunktrain_config is not None and self.attention_type == "regularMHA":  # (before anything is launched)
             raise NotImplementedError("dynchunktrain_config: Dynamic Chunk Training unsupported for the Transformer encoder")
 
@@ -123,8 +126,10 @@ class TransformerASR(TransformerInterface):
             if self.positional_encoding_type == "fixed_abs_sine":
                 src = src + self.positional_encoding.pe[:, : src.size(1)]
             pos_embs_source = None
+        elif self.attention_type in ("RoPEMHA", "hypermixing"):  # nothing is added to src and no table is passed (:520-524);
+            pos_embs_source = None                                # HyperMixing adds its own per-layer table inside the mixer
         else:
-            pos_embs_source = None if self.attention_type == "RoPEMHA" else self.positional_encoding(src)
+            pos_embs_source = self.positional_encoding(src)
         outputs = self.encoder(src=src, src_mask=src_mask, src_key_padding_mask=src_key_padding_mask,
                                pos_embs=pos_embs_source, dynchunktrain_config=dynchunktrain_config)
         if self.output_hidden_states:
@@ -168,6 +173,8 @@ class TransformerASR(TransformerInterface):
 
     def encode_streaming(self, src, context: TransformerASRStreamingContext):
         """One chunk [B,chunk,F(,C)] -> [B,chunk,d] (TransformerASR.py:546-640); ``context`` is mutated."""
+        if self.attention_type == "hypermixing":
+            raise NotImplementedError("streaming with attention_type='hypermixing' is not implemented")
         if not hasattr(self.encoder, "forward_streaming"):
             raise NotImplementedError(f"{type(self.encoder).__name__} has no streaming path (the Conformer encoder has)")
         if src.dim() == 4:
@@ -181,13 +188,15 @@ class TransformerASR(TransformerInterface):
         if self.attention_type == "RelPosMHAXL":
             pos_embs_source = self.positional_encoding.make_pe(n_pos)
         elif self.attention_type != "RoPEMHA":
-            raise NotImplementedError("streaming: RelPosMHAXL and RoPEMHA encoders are implemented")
+            raise NotImplementedError("streaming: RelPosMHAXL and RoPEMHA encoders are implemented (hypermixing offline only)")
         encoder_out, _ = self.encoder.forward_streaming(src=src, pos_embs=pos_embs_source,
                                                         context=context.encoder_context)
         return encoder_out
 
     def make_streaming_context(self, dynchunktrain_config, encoder_kwargs={}):
         """TransformerASR.py:642-670."""
+        if self.attention_type == "hypermixing":
+            raise NotImplementedError("streaming with attention_type='hypermixing' is not implemented")
         if not hasattr(self.encoder, "make_streaming_context"):
             raise NotImplementedError(f"{type(self.encoder).__name__} has no streaming path (the Conformer encoder has)")
         return TransformerASRStreamingContext(

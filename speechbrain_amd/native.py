@@ -193,6 +193,9 @@ def _declare(lib):
         "sbk_w2v_utt_norm_f32": ([p, p, i, ctypes.c_long, f, p], c_int),
         "sbk_wavlm_attention_max_frames": ([], c_int),
         "sbk_wavlm_attention_f32": ([p, p, p, p, p, p, p, p, i, i, i, i, f, p], c_int),
+        "sbk_hypermix_split_frames": ([], c_int),
+        "sbk_hypermix_workspace_bytes": ([i, i, i, i], ctypes.c_size_t),
+        "sbk_hypermix_f32": ([p] * 13 + [f, p, p, p, ctypes.c_size_t, i, i, i, i, i, p], c_int),
         "sbk_layernorm_f32": ([p, p, p, p, i, i, f, i, p], c_int),
         "sbk_log_softmax_f32": ([p, p, i, i, f, f, p], c_int),
         "sbk_ctc_greedy_decode_f32": ([p, p, p, p, i, i, i, i, p], c_int),
@@ -1391,6 +1394,73 @@ def wavlm_attention(qkv, x, gate_w, gate_b, gate_const, tab, key_len, H, scale, 
         out = torch.empty(B, T, d, dtype=torch.float32, device=qkv.device)
     _chk(lib.sbk_wavlm_attention_f32(_p(qkv), _p(x), _p(gate_w), _p(gate_b), _p(gate_const), _p(tab), _p(key_len), _p(out),
                                      B, T, H, Dh, float(scale), _stream(qkv)), "sbk_wavlm_attention_f32")
+    return out
+
+
+# ------------------------------------------------------------------ HyperMixing (csrc/hypermix.hip)
+HYPERMIX_MAX_HEAD_DIM, HYPERMIX_MAX_HYPER_PER_HEAD, HYPERMIX_MAX_FRAMES, HYPERMIX_MAX_WIDTH = 64, 256, 3000, 1024
+HYPERMIX_SPLIT_FRAMES = 256  # csrc/hypermix.hip kSplitFrames (sbk_hypermix_split_frames; tests check the two agree)
+_GEN_KEYS = ("fc1_weights", "fc1_biases", "fc2_weights", "fc2_biases")
+
+
+def hypermix_split_frames() -> int:
+    """Frames of one piece of the time reduction: ``hypermix`` sums T frames in ceil(T / this) pieces, combined in order."""
+    return int(load().sbk_hypermix_split_frames())
+
+
+def hypermix(h, key_len, pe, w1_gen, w2_gen, ln_w, ln_b, eps, H, residual=None, out=None):
+    """HyperMixing token mixing + LayerNorm (+ skip) in two launches (three when T exceeds ``hypermix_split_frames()``).
+    h [B,T,d] the normed input; key_len int32 [B] or None; pe [>=T,d] the mixer's position table (its first T rows are read);
+    w1_gen / w2_gen the two generators as (fc1_weights [H,Dh,Dh], fc1_biases [H,Dh], fc2_weights [H,k,Dh], fc2_biases [H,k]) or a
+    mapping with those keys; ln_w, ln_b [d].  Returns LayerNorm(mix(h)) + residual, [B,T,d]; rows past key_len[b] are ln_b +
+    residual and never read h.  ``out`` may be ``residual`` itself, never ``h``.  The generated [B,H,T,k] weights are not formed;
+    the intermediates ([B,H,Dh,Dh+1] matrices) live in the current stream's grow-only workspace."""
+    lib = load()
+    gens = [tuple(g[k] for k in _GEN_KEYS) if hasattr(g, "keys") else tuple(g) for g in (w1_gen, w2_gen)]
+    flat = [t for g in gens for t in g]
+    _dev_ok(h, key_len, pe, ln_w, ln_b, residual, out, *flat)
+    for t in (h, pe, ln_w, ln_b, residual, out, *flat):
+        if t is not None:
+            _f32(t)
+    if h.dim() != 3:
+        raise SbkError(f"hypermix: h {tuple(h.shape)} is not [B,T,d]")
+    B, T, d = h.shape
+    H = int(H)
+    if H <= 0 or d % H:
+        raise SbkError(f"hypermix: d={d} is not divisible by num_heads={H} (d % H == 0 is required)")
+    Dh = d // H
+    k = gens[0][2].shape[1] if gens[0][2].dim() == 3 else -1
+    if Dh > HYPERMIX_MAX_HEAD_DIM:
+        raise SbkError(f"hypermix: head width Dh={Dh} exceeds the limit Dh <= {HYPERMIX_MAX_HEAD_DIM}")
+    if k > HYPERMIX_MAX_HYPER_PER_HEAD:
+        raise SbkError(f"hypermix: hypernet width per head k={k} exceeds the limit k <= {HYPERMIX_MAX_HYPER_PER_HEAD}")
+    if T > HYPERMIX_MAX_FRAMES:
+        raise SbkError(f"hypermix: T={T} frames exceed the limit T <= {HYPERMIX_MAX_FRAMES}")
+    if d > HYPERMIX_MAX_WIDTH:
+        raise SbkError(f"hypermix: d={d} exceeds the limit d <= {HYPERMIX_MAX_WIDTH}")
+    want = ((H, Dh, Dh), (H, Dh), (H, k, Dh), (H, k))
+    for name, g in zip(("w1_gen", "w2_gen"), gens):
+        if len(g) != 4 or any(tuple(t.shape) != w for t, w in zip(g, want)):
+            raise SbkError(f"hypermix: {name} {[tuple(t.shape) for t in g]} is not {want} for d={d} H={H}")
+    if pe.dim() != 2 or pe.shape[1] != d or pe.shape[0] < T or ln_w.numel() != d or ln_b.numel() != d:
+        raise SbkError(f"hypermix: pe {tuple(pe.shape)}, ln_w {tuple(ln_w.shape)}, ln_b {tuple(ln_b.shape)} for T={T} d={d}")
+    if key_len is not None and (key_len.dtype != torch.int32 or key_len.numel() != B):
+        raise SbkError(f"hypermix: key_len must be int32 [{B}]")
+    if residual is not None and tuple(residual.shape) != (B, T, d):
+        raise SbkError(f"hypermix: residual {tuple(residual.shape)} for h {tuple(h.shape)}")
+    if out is None:
+        out = torch.empty(B, T, d, dtype=torch.float32, device=h.device)
+    elif tuple(out.shape) != (B, T, d):
+        raise SbkError(f"hypermix: out {tuple(out.shape)} for h {tuple(h.shape)}")
+    if B * T and out.data_ptr() == h.data_ptr():
+        raise SbkError("hypermix: out must not alias h (it may alias residual)")
+    if B == 0 or T == 0:
+        return out
+    nbytes = lib.sbk_hypermix_workspace_bytes(B, T, H, Dh)
+    st = _stream(h)
+    with _Workspace(nbytes, h.device, per_stream=True) as ws:
+        _chk(lib.sbk_hypermix_f32(_p(h), _p(key_len), _p(pe), *[_p(t) for t in flat], _p(ln_w), _p(ln_b), float(eps),
+                                  _p(residual), _p(out), ws.ptr, nbytes, B, T, H, Dh, k, st), "sbk_hypermix_f32")
     return out
 
 
