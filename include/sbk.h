@@ -495,6 +495,45 @@ int sbk_hypermix_f32(const float* h, const int32_t* key_len, const float* pe, co
                      const float* residual, float* out, void* workspace, size_t workspace_bytes, int B, int T, int H, int Dh,
                      int k, sbk_stream_t stream);
 
+/* ---- One recurrent layer for every utterance and every direction (csrc/rnn.hip; additive entries, ABI 11 unchanged)
+ * The LSTM stack of a CRDNN encoder (lobes/models/CRDNN.py:158-185, nnet/RNN.py:187-302): torch.nn.LSTM semantics, gate order
+ * i, f, g, o, over the PADDED length (CRDNN is a plain Sequential: nothing is packed).
+ *   xp   [B,T,D,4H]  x . W_ih^T of every direction, without bias (one contraction for both directions: the weight_ih of the
+ *                    directions stacked to [D*4H, in])
+ *   w_hh [D,4H,H]    weight_hh_l<l> | weight_hh_l<l>_reverse;   b_ih, b_hh [D,4H] (both or neither; NULL = no bias)
+ *   h0, c0 [D,B,H]   initial state (NULL = zeros; each on its own)
+ *   out  [B,T,D*H]   direction d owns columns d*H .. (d+1)*H; direction 1 scans t = T-1 .. 0 and writes at its own t
+ *   hn, cn [D,B,H]   final state (cn also carries c between the steps; c0 may be cn, h0 must not be hn or out)
+ * route 1 (and 0, the default): one launch per time step for both directions and the whole batch; a workgroup owns 8 hidden
+ * units with their four gate rows and 32 utterances on v_mfma_f32_32x32x2_f32, the cell update fused behind the product; h of the
+ * previous step is read from `out`.  Fixed summation order: two runs give the same bits.  sbk_rnn_layer_route: the route that
+ * route = 0 takes for a shape (0: the shape is refused).
+ * Limits (SBK_EINVAL): 1 <= H <= 2048, D 1 or 2, B >= 1 (any remainder against the 32-row tile), T >= 1, cell SBK_RNN_LSTM. */
+enum { SBK_RNN_LSTM = 0 }; /* (room for GRU / LiGRU cells) */
+int sbk_rnn_layer_route(int B, int T, int H, int D);
+int sbk_rnn_layer_f32(const float* xp, const float* w_hh, const float* b_ih, const float* b_hh, const float* h0, const float* c0,
+                      float* out, float* hn, float* cn, int B, int T, int H, int D, int cell, int route, sbk_stream_t stream);
+
+/* ---- The convolution blocks of a CRDNN encoder (csrc/crdnn.hip; additive entries, ABI 11 unchanged)
+ * lobes/models/CRDNN.py:199-278: [reflect-pad(1) + Conv2d(3x3, stride 1, bias) (nnet/CNN.py:654-751) -> LayerNorm over (F,C)
+ * (nnet/normalization.py:185-242) -> LeakyReLU(slope)] twice -> Pooling1d max over frequency (nnet/pooling.py:21-133, kernel =
+ * stride, floor); CRDNN.py:128-137: Pooling1d max over time behind the last block.  Activations [B,T,F,C] over the padded batch.
+ *   sbk_crdnn_conv1_f32: the first convolution (ONE input channel) with its LayerNorm and LeakyReLU in one pass: x [B,T,F],
+ *     w [9,C] = conv.weight[C,1,kF,kT] as row kf*3+kt, bias [C], gamma / beta [F*C] -> y [B,T,F,C].
+ *   sbk_crdnn_im2col_f32: the patch rows of frames [frame0, frame0 + frames) of x [B,T,F,Cin] (frame = b*T + t):
+ *     col [frames*F, 9*Cin], column (kf*3+kt)*Cin + ci = x[b, refl(t+kt-1), refl(f+kf-1), ci]; the convolution is then
+ *     sbk_gemm_nt_f32 (or its routed kin) of col with conv.weight re-laid-out to [Cout, 9*Cin], bias in the epilogue.
+ *   sbk_crdnn_norm_pool_f32: x [B,T,F,C] (a convolution's output) -> y [B,T/pool_t,F/pool_f,C] =
+ *     max over pool_t frames and pool_f bins of LeakyReLU(LayerNorm_(F,C)(x)); only the pooled tensor is written.
+ *     pool_f = pool_t = 1: the LayerNorm + LeakyReLU between the two convolutions (y may then be x).
+ * Limits (SBK_EINVAL): T >= 2 and F >= 2 (reflect padding), F*C <= 16384 (a frame is held in LDS), B <= 65535, a pooled
+ * size of at least 1. */
+int sbk_crdnn_conv1_f32(const float* x, const float* w, const float* bias, const float* gamma, const float* beta, float* y,
+                        int B, int T, int F, int C, float eps, float slope, sbk_stream_t stream);
+int sbk_crdnn_im2col_f32(const float* x, float* col, int B, int T, int F, int Cin, int frame0, int frames, sbk_stream_t stream);
+int sbk_crdnn_norm_pool_f32(const float* x, const float* gamma, const float* beta, float* y, int B, int T, int F, int C,
+                            int pool_f, int pool_t, float eps, float slope, sbk_stream_t stream);
+
 /* ---- CTC decoding (csrc/ctc_decode.hip; additive entries, ABI 11 unchanged) ---------------------------------------------
  * ctc_greedy_decode (decoders/ctc.py:335-380): x [B,T,V] (log-)probabilities, rel_len [B] relative lengths (device; NULL =
  * 1.0).  Utterance b uses its first int(round(fp32(rel_len[b] * T))) frames (round half to even, as torch.round); per frame

@@ -15,7 +15,7 @@ _MODULES = [
     "lobes.models.transformer", "lobes.models.transformer.Conformer", "lobes.models.transformer.Branchformer",
     "lobes.models.transformer.Transformer",
     "lobes.models.transformer.TransformerASR", "lobes.models.transformer.TransformerLM", "lobes.models.RNNLM", "nnet", "nnet.attention", "nnet.activations", "nnet.CNN",
-    "nnet.hypermixing",
+    "nnet.hypermixing", "lobes.models.CRDNN", "nnet.pooling", "nnet.dropout",
     "nnet.containers", "nnet.embedding", "nnet.linear", "nnet.normalization", "decoders", "decoders.seq2seq",
     "decoders.scorer", "decoders.utils", "inference", "inference.ASR", "inference.interfaces", "utils",
     "utils.data_utils", "utils.parameter_transfer", "utils.metric_stats", "utils.edit_distance",

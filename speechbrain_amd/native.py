@@ -196,6 +196,11 @@ def _declare(lib):
         "sbk_hypermix_split_frames": ([], c_int),
         "sbk_hypermix_workspace_bytes": ([i, i, i, i], ctypes.c_size_t),
         "sbk_hypermix_f32": ([p] * 13 + [f, p, p, p, ctypes.c_size_t, i, i, i, i, i, p], c_int),
+        "sbk_rnn_layer_route": ([i, i, i, i], c_int),
+        "sbk_rnn_layer_f32": ([p] * 9 + [i] * 6 + [p], c_int),
+        "sbk_crdnn_conv1_f32": ([p] * 6 + [i, i, i, i, f, f, p], c_int),
+        "sbk_crdnn_im2col_f32": ([p, p, i, i, i, i, i, i, p], c_int),
+        "sbk_crdnn_norm_pool_f32": ([p] * 4 + [i] * 6 + [f, f, p], c_int),
         "sbk_layernorm_f32": ([p, p, p, p, i, i, f, i, p], c_int),
         "sbk_log_softmax_f32": ([p, p, i, i, f, f, p], c_int),
         "sbk_ctc_greedy_decode_f32": ([p, p, p, p, i, i, i, i, p], c_int),
@@ -1462,6 +1467,108 @@ def hypermix(h, key_len, pe, w1_gen, w2_gen, ln_w, ln_b, eps, H, residual=None, 
         _chk(lib.sbk_hypermix_f32(_p(h), _p(key_len), _p(pe), *[_p(t) for t in flat], _p(ln_w), _p(ln_b), float(eps),
                                   _p(residual), _p(out), ws.ptr, nbytes, B, T, H, Dh, k, st), "sbk_hypermix_f32")
     return out
+
+
+# ------------------------------------------------------------------ recurrent layers (csrc/rnn.hip)
+RNN_LSTM = 0  # SBK_RNN_LSTM
+RNN_MAX_HIDDEN = 2048  # csrc/rnn.hip kMaxH
+
+
+def rnn_layer_route(B, T, H, D) -> int:
+    """The route ``rnn_layer(route=0)`` takes for a shape: 1 = step launches; 0 = the shape is refused."""
+    return int(load().sbk_rnn_layer_route(int(B), int(T), int(H), int(D)))
+
+
+def rnn_layer(xp, w_hh, b_ih=None, b_hh=None, h0=None, c0=None, route=0):
+    """One LSTM layer for every utterance and direction (sbk_rnn_layer_f32): xp [B,T,D,4H] = x . W_ih^T per direction without
+    bias, w_hh [D,4H,H], b_ih / b_hh [D,4H] or None, h0 / c0 [D,B,H] or None (zeros)
+    -> (out [B,T,D*H], hn [D,B,H], cn [D,B,H]); direction 1 runs backwards in time and writes at its own t."""
+    lib = load()
+    if xp.ndim != 4 or w_hh.ndim != 3:
+        raise SbkError(f"rnn_layer: xp {tuple(xp.shape)} is not [B,T,D,4H] or w_hh {tuple(w_hh.shape)} is not [D,4H,H]")
+    B, T, D, G = xp.shape
+    H = w_hh.shape[2]
+    if G != 4 * H or tuple(w_hh.shape) != (D, 4 * H, H):
+        raise SbkError(f"rnn_layer: xp {tuple(xp.shape)} and w_hh {tuple(w_hh.shape)} do not agree on D and H")
+    for name, t, want in (("b_ih", b_ih, (D, 4 * H)), ("b_hh", b_hh, (D, 4 * H)), ("h0", h0, (D, B, H)), ("c0", c0, (D, B, H))):
+        if t is not None and tuple(t.shape) != want:
+            raise SbkError(f"rnn_layer: {name} {tuple(t.shape)} is not {want}")
+    _dev_ok(xp, w_hh, b_ih, b_hh, h0, c0)
+    for t in (xp, w_hh, b_ih, b_hh, h0, c0):
+        if t is not None:
+            _f32(t)
+    out = torch.empty(B, T, D * H, dtype=torch.float32, device=xp.device)
+    hn = torch.empty(D, B, H, dtype=torch.float32, device=xp.device)
+    cn = torch.empty(D, B, H, dtype=torch.float32, device=xp.device)
+    _chk(lib.sbk_rnn_layer_f32(_p(xp), _p(w_hh), _p(b_ih), _p(b_hh), _p(h0), _p(c0), _p(out), _p(hn), _p(cn), B, T, H, D,
+                               RNN_LSTM, int(route), _stream(xp)), "sbk_rnn_layer_f32")
+    return out, hn, cn
+
+
+# ------------------------------------------------------------------ CRDNN convolution blocks (csrc/crdnn.hip)
+CRDNN_MAX_FRAME = 16384  # csrc/crdnn.hip kMaxFrame: F * C floats of a frame held in LDS
+CRDNN_COL_BYTES = 256 << 20  # budget of the patch matrix of one chunk of frames
+
+
+def _crdnn_time_check(T, F):
+    if T < 2 or F < 2:  # (F.pad(mode="reflect") of the reference refuses a padding that is not smaller than the dimension)
+        raise ValueError(f"CRDNN convolution: reflect padding of 1 needs at least 2 frames and 2 bins, got T={T} F={F}")
+
+
+def crdnn_conv1(x, w9, bias, gamma, beta, eps=1e-5, slope=0.01):
+    """reflect-pad(1) + Conv2d(3x3) of ONE input channel + LayerNorm over (F,C) + LeakyReLU (sbk_crdnn_conv1_f32):
+    x [B,T,F], w9 [9,C] (row kf*3+kt), bias [C], gamma / beta [F*C] -> [B,T,F,C]."""
+    lib = load()
+    B, T, F = x.shape
+    C = w9.shape[1]
+    _crdnn_time_check(T, F)
+    _dev_ok(x, w9, bias, gamma, beta)
+    y = torch.empty(B, T, F, C, dtype=torch.float32, device=x.device)
+    _chk(lib.sbk_crdnn_conv1_f32(_p(_f32(x)), _p(w9), _p(bias), _p(gamma), _p(beta), _p(y), B, T, F, C, float(eps),
+                                 float(slope), _stream(x)), "sbk_crdnn_conv1_f32")
+    return y
+
+
+def crdnn_conv(x, wk, bias, col_bytes=None):
+    """reflect-pad(1) + Conv2d(3x3, stride 1, bias) as a contraction on the matrix cores: x [B,T,F,Cin], wk [Cout, 9*Cin] =
+    conv.weight permuted to (Cout, kF, kT, Cin) -> [B,T,F,Cout].  The patch matrix (sbk_crdnn_im2col_f32) is formed for a run
+    of frames that fits ``col_bytes`` (CRDNN_COL_BYTES) at a time and contracted by ``gemm_nt``'s routing."""
+    lib = load()
+    B, T, F, Cin = x.shape
+    Cout, K = wk.shape
+    if K != 9 * Cin:
+        raise SbkError(f"crdnn_conv: weight {tuple(wk.shape)} for {Cin} input channels (expected [Cout, {9 * Cin}])")
+    _crdnn_time_check(T, F)
+    _dev_ok(x, wk, bias)
+    _f32(x)
+    y = torch.empty(B, T, F, Cout, dtype=torch.float32, device=x.device)
+    y2 = y.view(B * T * F, Cout)
+    per = min(B * T, max(1, int(col_bytes or CRDNN_COL_BYTES) // (F * K * 4)))
+    st = _stream(x)
+    # the patch matrix lives in the current stream's grow-only buffer: one bounded allocation per stream, reused by every chunk,
+    # every convolution and every later batch (stream order makes the reuse safe)
+    with _Workspace(per * F * K * 4, x.device, per_stream=True) as ws:
+        for f0 in range(0, B * T, per):
+            n = min(per, B * T - f0)
+            col = ws.buf[ws.off:ws.off + n * F * K * 4].view(torch.float32).view(n * F, K)
+            _chk(lib.sbk_crdnn_im2col_f32(_p(x), _p(col), B, T, F, Cin, f0, n, st), "sbk_crdnn_im2col_f32")
+            with precision_scope("fp32"):
+                gemm_nt(col, wk, bias, out=y2[f0 * F:(f0 + n) * F])
+    return y
+
+
+def crdnn_norm_pool(x, gamma, beta, pool_f=1, pool_t=1, eps=1e-5, slope=0.01):
+    """max-pool over pool_t frames and pool_f bins of LeakyReLU(LayerNorm over (F,C)) in one pass (sbk_crdnn_norm_pool_f32):
+    x [B,T,F,C] -> [B,T//pool_t,F//pool_f,C]."""
+    lib = load()
+    B, T, F, C = x.shape
+    if T // pool_t < 1 or F // pool_f < 1:
+        raise ValueError(f"CRDNN pooling: T={T} F={F} pooled by ({pool_t}, {pool_f}) leaves an empty output")
+    _dev_ok(x, gamma, beta)
+    y = torch.empty(B, T // pool_t, F // pool_f, C, dtype=torch.float32, device=x.device)
+    _chk(lib.sbk_crdnn_norm_pool_f32(_p(_f32(x)), _p(gamma), _p(beta), _p(y), B, T, F, C, int(pool_f), int(pool_t), float(eps),
+                                     float(slope), _stream(x)), "sbk_crdnn_norm_pool_f32")
+    return y
 
 
 def wavlm_relative_buckets(rel, num_buckets, max_distance):
