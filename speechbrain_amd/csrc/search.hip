@@ -814,6 +814,9 @@ __global__ void __launch_bounds__(256) beam_finalize_kernel(BeamState s, int cur
 }
 
 // ---------------------------------------------------------------- greedy helpers
+// Arg-max of a logits row.  Equal maxima: the LOWER token index wins (`better` in the per-thread scan, the wave reduction and the
+// merge of the four waves), as torch.argmax returns the first maximum on the reference's side
+// (tests/test_search_shapes.py::test_greedy_pick_of_tied_maxima).
 __global__ void __launch_bounds__(256) greedy_pick_kernel(const float* __restrict__ logits, int32_t* __restrict__ tok_out,
                                                           int32_t* __restrict__ ended, int32_t* __restrict__ hyp,
                                                           float* __restrict__ score, int32_t* __restrict__ n_ended,

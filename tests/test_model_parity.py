@@ -1324,16 +1324,18 @@ def test_fused_scoring_equals_separate_kernels(backend, tag):
 def test_fused_scoring_large_vocabulary(backend, vocab):
     """The register-list widths the recipe sizes need (20 entries per thread up to V = 5 120, 32 up to 8 192; the golden
     models' vocabularies fit 4): beam 10 + CTC + eos threshold on a random model, fused pass against separate kernels,
-    bit for bit."""
+    bit for bit; at V = 1 300 also against the oracle's search."""
     nat, dev = backend
     from speechbrain_amd.decoders import CTCScorer, S2STransformerBeamSearcher, ScorerBuilder
     from speechbrain_amd.inference.builders import build_modules
 
     torch.manual_seed(11)
     m = build_modules(dict(d_model=32, nhead=2, d_ffn=64, n_enc=1, n_dec=2, n_fft=512, win_length=32), vocab=vocab)
-    mods = torch.nn.ModuleDict({k: m[k] for k in ("Transformer", "seq_lin", "ctc_lin")}).to(dev).eval()
-    enc = (torch.randn(3, 24, 32, generator=torch.Generator().manual_seed(2)) * 1.5).to(dev)
-    wl = torch.tensor([1.0, 0.7, 0.9]).to(dev)
+    mods = torch.nn.ModuleDict({k: m[k] for k in ("Transformer", "seq_lin", "ctc_lin")}).eval()
+    sd = {f"{p}.{k}": v.detach().clone() for p in mods for k, v in mods[p].state_dict().items()}  # (CPU copy for the oracle)
+    mods = mods.to(dev)
+    enc_h, wl_h = torch.randn(3, 24, 32, generator=torch.Generator().manual_seed(2)) * 1.5, torch.tensor([1.0, 0.7, 0.9])
+    enc, wl = enc_h.to(dev), wl_h.to(dev)
     scorer = ScorerBuilder(full_scorers=[CTCScorer(ctc_fc=mods["ctc_lin"], blank_index=0, eos_index=2)], weights={"ctc": 0.4})
     bs = S2STransformerBeamSearcher(modules=[mods["Transformer"], mods["seq_lin"]], bos_index=1, eos_index=2,
                                     min_decode_ratio=0.0, max_decode_ratio=0.3, beam_size=10, using_eos_threshold=True,
@@ -1345,6 +1347,24 @@ def test_fused_scoring_large_vocabulary(backend, vocab):
     for x, y in zip(out[1], out[0]):
         assert torch.equal(x.cpu(), y.cpu()) if torch.is_tensor(x) else x == y
     assert int(out[1][0].max()) > 2  # (something was decoded)
+    if vocab == 1300:
+        # both paths call the same block_topk, so a mistake they share passes the comparison above: the V = 1 300 lists must
+        # also be the oracle's.  Fairness of the seed, on the CPU: the oracle in fp64 and in fp32 returns the same lists, and
+        # neighbouring fp64 scores lie further apart than the 1e-4 allowed below -- no rank hangs on fp32 rounding.
+        cfg = O.ModelCfg(d_model=32, nhead=2, num_encoder_layers=1, num_decoder_layers=2, d_ffn=64, vocab=vocab)
+        sc = O.SearchCfg(beam=10, ctc_weight=0.4, using_eos_threshold=True, max_decode_ratio=0.3, return_topk=True, topk=4)
+        hyps_ref, lens_ref, sc_ref, _ = O.beam_search(enc_h, wl_h, sd, cfg, sc)
+        keep = torch.get_default_dtype()
+        torch.set_default_dtype(torch.float64)  # (the oracle builds its constants in the default dtype)
+        try:
+            hyps64, _, sc64, _ = O.beam_search(enc_h.double(), wl_h.double(), {k: v.double() for k, v in sd.items()}, cfg, sc)
+        finally:
+            torch.set_default_dtype(keep)
+        assert torch.equal(hyps_ref, hyps64) and float((sc64[:, :-1] - sc64[:, 1:]).min()) > 1e-4
+        hyps, lens, scores, _ = out[1]
+        assert hyps.shape == hyps_ref.shape and torch.equal(hyps.cpu(), hyps_ref)
+        assert float((scores.cpu() - sc_ref).abs().max()) <= 1e-4
+        assert float((lens.cpu() - lens_ref).abs().max()) <= 1e-6
 
 
 @pytest.mark.parametrize("tag", ["tiny_ctc", "tiny_noctc"])
