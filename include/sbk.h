@@ -232,6 +232,8 @@ int sbk_gemm_nt_f32x3(const float* A, int lda, const uint16_t* W3, const float* 
  *   sbk_gemm_nt_x3p: epilogue / seq_len exactly as sbk_gemm_nt_f32; the result goes to C (fp32, may be NULL when PC is given)
  *   and / or to PC, the panel image of the [M, N] result (N % 16 == 0) = the A operand of the next contraction
  *   (PositionalwiseFeedForward, nnet/attention.py:941-945: linear -> activation -> linear without an fp32 round trip).
+ *   K % 16 == 0, K >= 32; rows of C / residual / bias are moved as 16-byte vectors exactly as by sbk_gemm_nt_f32x3
+ *   (N % 4 == 0, ldc >= N, ldc % 4 == 0, ldr >= N, ldr % 4 == 0, 16-byte aligned; SBK_EINVAL otherwise).
  *   Needs the stream workspace when the launch has more tiles than CUs. */
 size_t sbk_x3p_panel_bytes(int rows, int K);
 /* ABI 8: y = act(LayerNorm(x)) (nn.LayerNorm of Conformer.py:129,155,310,318 / attention.py:915) written DIRECTLY as the
@@ -248,7 +250,10 @@ int sbk_gemm_nt_x3p(const uint16_t* PA, const uint16_t* PW, const float* bias, c
 /* ABI 8 (signature of ABI 10): the same arithmetic for FEW rows -- the linear layers of a decoding step (Transformer.py:751-834:
  * self-attention in / out projections, cross-attention query / out projections, the feed-forward pair; a few hundred to a few
  * thousand hypothesis rows).  A fp32 [M, K] (row stride lda; split in registers), PW the panel image of W [N, K]
- * (sbk_split_x3p); 64 x 64 tiles whose four waves split K; N % 4 == 0, K % 256 == 0.  Epilogue: residual + alpha * act(. + bias).
+ * (sbk_split_x3p); 64 x 64 tiles whose four waves split K; N % 4 == 0, K % 256 == 0; lda >= K, lda % 4 == 0, A and PW
+ * 16-byte aligned; rows of C (and of residual / bias) are moved as 16-byte vectors: ldc >= N, ldc % 4 == 0, ldr >= N,
+ * ldr % 4 == 0, 16-byte aligned (SBK_EINVAL otherwise; the same holds for sbk_gemm_ln_nt_x3r below).
+ * Epilogue: residual + alpha * act(. + bias).
  * No workspace: K is never split across workgroups (fixed summation order: the four waves' K quarters in order).
  * (ABI 8-9 also took A as a panel image and could write the result as one: measured no faster and removed in ABI 10.) */
 int sbk_gemm_nt_x3r(const float* A, int lda, const uint16_t* PW, const float* bias, const float* residual, int ldr, float* C,
@@ -331,8 +336,9 @@ int sbk_gemm_nt_splitk_f32(const float* A, int lda, const float* W, int ldw, con
                            float alpha, float* workspace, size_t workspace_floats, sbk_stream_t stream);
 
 /* LayerNorm fused into the few-row contraction: C = epilogue(LN(A) . W^T + b) with gamma/beta pre-folded
- * by the caller: Wf[n,k] = W[n,k]*gamma[k], bf[n] = b[n] + sum_k W[n,k]*beta[k].  K in {128,256,512},
- * M <= 512 (SBK_EINVAL otherwise). */
+ * by the caller: Wf[n,k] = W[n,k]*gamma[k], bf[n] = b[n] + sum_k W[n,k]*beta[k].  K in {128,256,512}; M <= 512, or
+ * M <= 4096 with fewer than 256 tiles of 128 x 128; M * N < 1 900 000; lda % 4 == 0, ldw % 4 == 0, A and Wf 16-byte
+ * aligned; lda >= K, ldw >= K, ldc >= N, ldr >= N (SBK_EINVAL otherwise).  C and the residual are moved as scalars. */
 int sbk_gemm_ln_nt_f32(const float* A, int lda, const float* Wf, int ldw, const float* bf, const float* residual,
                        int ldr, float* C, int ldc, int M, int N, int K, float eps, int act, float alpha,
                        sbk_stream_t stream);
@@ -784,7 +790,8 @@ typedef struct {
  *                         once per matrix);
  *   sbk_layernorm_fp8o:   act(LayerNorm(x)) written in that form (the next contraction's A operand, no fp32 round trip);
  *   sbk_gemm_nt_fp8a:     C = residual + alpha * act(a_scale[m] w_scale[n] (A8 . W8^T) + bias), fp32 accumulation on
- *                         v_mfma_scale_f32_32x32x64_f8f6f4 with unit block scales; K % 128 == 0; a_scale / w_scale may be
+ *                         v_mfma_scale_f32_32x32x64_f8f6f4 with unit block scales; K % 128 == 0, lda % 16 == 0,
+ *                         ldw % 16 == 0, A8 and W8 16-byte aligned; a_scale / w_scale may be
  *                         NULL (= 1); outputs: C fp32 and / or Cb bf16 and / or C8 = e4m3(result / c8_scale) with a FIXED
  *                         scale (the hidden layer of a feed-forward pair, whose row maxima are unknown before the last
  *                         column tile: with c8_scale = 1 it is the A operand of the next call with a_scale = NULL).

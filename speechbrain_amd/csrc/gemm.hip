@@ -1254,7 +1254,8 @@ extern "C" int sbk_gemm_nt_f32(const float* A, int lda, const float* W, int ldw,
   SBK_REQUIRE(A && W && C, "gemm: null operand");
   SBK_REQUIRE(M >= 0 && N >= 0 && K > 0, "gemm: bad shape M=%d N=%d K=%d", M, N, K);
   // lda < K is allowed: rows of A then overlap (a strided window over a time-major signal = a 1-D convolution read in place)
-  SBK_REQUIRE(lda > 0 && ldw >= K && ldc >= N, "gemm: leading dimension smaller than the row");
+  SBK_REQUIRE(lda > 0 && ldw >= K, "gemm: leading dimension of an operand smaller than the row (lda=%d ldw=%d)", lda, ldw);
+  SBK_REQUIRE(ldc >= N, "gemm: leading dimension smaller than the row (ldc=%d, N=%d)", ldc, N);
   SBK_REQUIRE(!residual || ldr >= N, "gemm: residual stride");
   SBK_REQUIRE(act >= SBK_ACT_NONE && act <= SBK_ACT_LEAKY_RELU, "gemm: unknown activation %d", act);
   SBK_REQUIRE(!seq_len || rows_per_seq > 0, "gemm: seq_len given without rows_per_seq");
@@ -1267,7 +1268,10 @@ extern "C" int sbk_gemm_ln_nt_f32(const float* A, int lda, const float* Wf, int 
                                   int act, float alpha, sbk_stream_t stream) {
   if (M == 0 || N == 0) return 0;  // empty batch: nothing to launch, the data pointers may be NULL
   SBK_REQUIRE(A && Wf && C, "gemm_ln: null operand");
-  SBK_REQUIRE(M >= 0 && N >= 0 && K > 0 && lda >= K && ldw >= K && ldc >= N, "gemm_ln: bad shape");
+  SBK_REQUIRE(M >= 0 && N >= 0 && K > 0, "gemm_ln: bad shape M=%d N=%d K=%d", M, N, K);
+  SBK_REQUIRE(lda >= K && ldw >= K, "gemm_ln: leading dimension of an operand smaller than the row (lda=%d ldw=%d)", lda, ldw);
+  SBK_REQUIRE(ldc >= N, "gemm_ln: leading dimension smaller than the row (ldc=%d, N=%d)", ldc, N);
+  SBK_REQUIRE(!residual || ldr >= N, "gemm_ln: residual stride");
   const int rc = sbk::gemm_ln_nt(A, lda, Wf, ldw, bf, residual, ldr, C, ldc, M, N, K, eps, act, alpha,
                                  sbk::as_stream(stream));
   if (rc == -1) return sbk::fail(SBK_EINVAL, "gemm_ln: shape M=%d N=%d K=%d not eligible for the fused kernel", M, N, K);
@@ -1280,7 +1284,8 @@ extern "C" int sbk_gemm_nt_splitk_f32(const float* A, int lda, const float* W, i
   if (M == 0 || N == 0) return 0;  // empty batch: nothing to launch, the data pointers may be NULL
   SBK_REQUIRE(A && W && C, "gemm: null operand");
   SBK_REQUIRE(M >= 0 && N >= 0 && K > 0, "gemm: bad shape M=%d N=%d K=%d", M, N, K);
-  SBK_REQUIRE(lda >= K && ldw >= K && ldc >= N, "gemm: leading dimension smaller than the row");
+  SBK_REQUIRE(lda >= K && ldw >= K, "gemm: leading dimension of an operand smaller than the row (lda=%d ldw=%d)", lda, ldw);
+  SBK_REQUIRE(ldc >= N, "gemm: leading dimension smaller than the row (ldc=%d, N=%d)", ldc, N);
   SBK_REQUIRE(!residual || ldr >= N, "gemm: residual stride");
   SBK_REQUIRE(act >= SBK_ACT_NONE && act <= SBK_ACT_LEAKY_RELU, "gemm: unknown activation %d", act);
   return sbk::gemm_nt_ws(A, lda, W, ldw, bias, residual, ldr, C, ldc, M, N, K, act, alpha, nullptr, 0, workspace,
@@ -1330,8 +1335,9 @@ extern "C" int sbk_gemm_nt_f32x3(const float* A, int lda, const uint16_t* W3, co
   if (M == 0 || N == 0) return 0;
   SBK_REQUIRE(A && W3 && C, "gemm_f32x3: null operand");
   SBK_REQUIRE(M >= 0 && N >= 0 && K >= 64 && K % 32 == 0, "gemm_f32x3: bad shape M=%d N=%d K=%d (K: a multiple of 32, >= 64)", M, N, K);
-  SBK_REQUIRE(lda > 0 && lda % 4 == 0 && ldc >= N && sbk::aligned16(A) && sbk::aligned16(W3),
+  SBK_REQUIRE(lda > 0 && lda % 4 == 0 && sbk::aligned16(A) && sbk::aligned16(W3),
               "gemm_f32x3: operand rows must be 16-byte aligned (lda=%d)", lda);
+  SBK_REQUIRE(ldc >= N, "gemm_f32x3: leading dimension smaller than the row (ldc=%d, N=%d)", ldc, N);
   SBK_REQUIRE(N % 4 == 0 && ldc % 4 == 0 && sbk::aligned16(C) && (!bias || sbk::aligned16(bias)),
               "gemm_f32x3: N and ldc must be multiples of 4, C / bias 16-byte aligned (rows are stored as 16-byte vectors)");
   SBK_REQUIRE(!residual || (ldr >= N && ldr % 4 == 0 && sbk::aligned16(residual)), "gemm_f32x3: residual stride / alignment");

@@ -665,7 +665,8 @@ int require_lp(const char* who, bool operands, int kq, const float* A, int lda, 
                int ldc, int M, int N, int K, int act, const int32_t* seq_len, int rows_per_seq) {
   SBK_REQUIRE(operands, "%s: null operand", who);
   SBK_REQUIRE(M >= 0 && N >= 0 && K > 0 && K % kq == 0, "%s: bad shape M=%d N=%d K=%d (K must be a multiple of %d)", who, M, N, K, kq);
-  SBK_REQUIRE(lda > 0 && ldw >= K && ldc >= N && lda % 4 == 0 && ldw % kq == 0, "%s: leading dimensions", who);
+  SBK_REQUIRE(lda > 0 && ldw >= K && lda % 4 == 0 && ldw % kq == 0, "%s: leading dimensions of the operands (lda=%d ldw=%d)", who, lda, ldw);
+  SBK_REQUIRE(ldc >= N, "%s: leading dimension smaller than the row (ldc=%d, N=%d)", who, ldc, N);
   SBK_REQUIRE(sbk::aligned16(A) && sbk::aligned16(W), "%s: operands must be 16-byte aligned", who);
   SBK_REQUIRE(!residual || ldr >= N, "%s: residual stride", who);
   SBK_REQUIRE(act >= SBK_ACT_NONE && act <= SBK_ACT_LEAKY_RELU, "%s: unknown activation %d", who, act);
@@ -691,7 +692,8 @@ extern "C" int sbk_gemm_nt_bf16a(const uint16_t* A, int lda, const uint16_t* Wb,
   SBK_REQUIRE(M > 0 && N > 0 && K > 0 && K % 64 == 0, "gemm_bf16a: K must be a multiple of 64 (M=%d N=%d K=%d)", M, N, K);
   SBK_REQUIRE(lda >= K && ldw >= K && lda % 8 == 0 && ldw % 8 == 0 && sbk::aligned16(A) && sbk::aligned16(Wb),
               "gemm_bf16a: operand rows must be 16-byte aligned (lda=%d ldw=%d)", lda, ldw);
-  SBK_REQUIRE((!C || ldc >= N) && (!Cb || ldcb >= N) && (!residual || ldr >= N), "gemm_bf16a: leading dimension smaller than the row");
+  SBK_REQUIRE((!C || ldc >= N) && (!Cb || ldcb >= N), "gemm_bf16a: leading dimension smaller than the row (ldc=%d ldcb=%d, N=%d)", ldc, ldcb, N);
+  SBK_REQUIRE(!residual || ldr >= N, "gemm_bf16a: residual stride");
   SBK_REQUIRE(act >= SBK_ACT_NONE && act <= SBK_ACT_LEAKY_RELU, "gemm_bf16a: unknown activation %d", act);
   hipStream_t st = sbk::as_stream(stream);
   sbk::ProfScope prof("gemm_nt_bf16a", 2.0 * M * (double)N * K,
@@ -712,8 +714,10 @@ extern "C" int sbk_gemm_nt_fp8a(const uint8_t* A8, int lda, const float* a_scale
   SBK_REQUIRE(M > 0 && N > 0 && K > 0 && K % 128 == 0, "gemm_fp8a: K must be a multiple of 128 (M=%d N=%d K=%d)", M, N, K);
   SBK_REQUIRE(lda >= K && ldw >= K && lda % 16 == 0 && ldw % 16 == 0 && sbk::aligned16(A8) && sbk::aligned16(W8),
               "gemm_fp8a: operand rows must be 16-byte aligned (lda=%d ldw=%d)", lda, ldw);
-  SBK_REQUIRE((!C || ldc >= N) && (!Cb || ldcb >= N) && (!C8 || (ldc8 >= N && c8_scale > 0.0f)) && (!residual || ldr >= N),
-              "gemm_fp8a: leading dimension smaller than the row / non-positive fp8 output scale");
+  SBK_REQUIRE((!C || ldc >= N) && (!Cb || ldcb >= N) && (!C8 || ldc8 >= N),
+              "gemm_fp8a: leading dimension smaller than the row (ldc=%d ldcb=%d ldc8=%d, N=%d)", ldc, ldcb, ldc8, N);
+  SBK_REQUIRE(!C8 || c8_scale > 0.0f, "gemm_fp8a: non-positive fp8 output scale");
+  SBK_REQUIRE(!residual || ldr >= N, "gemm_fp8a: residual stride");
   SBK_REQUIRE(act >= SBK_ACT_NONE && act <= SBK_ACT_LEAKY_RELU, "gemm_fp8a: unknown activation %d", act);
   hipStream_t st = sbk::as_stream(stream);
   sbk::ProfScope prof("gemm_nt_fp8a", 2.0 * M * (double)N * K,
