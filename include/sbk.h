@@ -965,7 +965,10 @@ int sbk_prompted_greedy_search_f32(const sbk_decoder_weights* W, const float* en
                                    sbk_stream_t stream);
 
 /* TransformerASR.decode (TransformerASR.py:426-473) through the KV-cached step:
- * tokens [n,L] int32, enc [n,T,d], enc_len [n] -> pred [n,L,d] (decoder.norm output). */
+ * tokens [n,L] int32, enc [n,T,d], enc_len [n] -> pred [n,L,d] (decoder.norm output).
+ * enc_len outside [1, T] (here and in the searches above): the decoder's cross-attention attends to min(max(enc_len, 1), T)
+ * frames -- every kernel of it, the persistent few-row step and the launch-per-operation ones alike (the reference would
+ * return NaN for a fully masked memory and cannot be given more frames than it has). */
 size_t sbk_decoder_prefix_workspace_bytes(const sbk_decoder_weights* W, int n, int T, int L);
 int sbk_decoder_prefix_f32(const sbk_decoder_weights* W, const int32_t* tokens, const float* enc,
                            const int32_t* enc_len, void* workspace, size_t workspace_bytes, float* pred, int n, int T,
