@@ -325,6 +325,8 @@ int sbk_f32_to_f16(const float* x, uint16_t* y, long n, sbk_stream_t stream);
 int sbk_gemm_nt_fp8(const float* A, int lda, const float* a_absmax, const uint8_t* Wq, int ldw, float w_scale,
                     const float* bias, const float* residual, int ldr, float* C, int ldc, int M, int N, int K, int act,
                     float alpha, const int32_t* seq_len, int rows_per_seq, sbk_stream_t stream);
+/* y = e4m3(x * mul), n even: round to nearest even, saturating at +-448 (+-inf included); a NaN becomes the NaN code
+ * (byte & 0x7f == 0x7f) -- it is never clamped to a finite value. */
 int sbk_f32_to_fp8(const float* x, uint8_t* y, long n, float mul, sbk_stream_t stream);
 int sbk_absmax_f32(const float* x, long n, float* out, sbk_stream_t stream);
 
@@ -795,6 +797,9 @@ typedef struct {
  *                         NULL (= 1); outputs: C fp32 and / or Cb bf16 and / or C8 = e4m3(result / c8_scale) with a FIXED
  *                         scale (the hidden layer of a feed-forward pair, whose row maxima are unknown before the last
  *                         column tile: with c8_scale = 1 it is the A operand of the next call with a_scale = NULL).
+ * Every conversion to e4m3 here (q, C8) rounds to nearest even and saturates at +-448, +-inf included; a NaN becomes the NaN
+ * code (byte & 0x7f == 0x7f), never a finite value.  The row maximum behind scale[r] ignores NaNs: the other elements of
+ * such a row are scaled by its largest finite magnitude.
  * Not a parity path: e4m3 keeps 3 significand bits (tolerances in tests/test_whisper.py). */
 int sbk_quant_rows_fp8(const float* x, int ldx, uint8_t* q, float* scale, int rows, int d, sbk_stream_t stream);
 /* the same from bf16 rows (the bf16 attention kernel's context -> the out-projection's fp8 operand); ldx in elements */

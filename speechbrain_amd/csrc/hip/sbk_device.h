@@ -79,10 +79,11 @@ __device__ __forceinline__ i32x8 i32x8_from_u4(uint4 lo, uint4 hi) {
   i32x8 r = {(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
   return r;
 }
-// two floats -> two e4m3 bytes (low byte = a), round to nearest even, saturating at +-448 (v_cvt_pk_fp8_f32)
+// two floats -> two e4m3 bytes (low byte = a), round to nearest even, saturating at +-448 (+-inf included); a NaN becomes
+// the NaN code (v_cvt_pk_fp8_f32).  The select keeps the NaN out of the clamp: fmaxf(NaN, -448) is -448.
 __device__ __forceinline__ unsigned short f32x2_to_fp8(float a, float b) {
-  a = fminf(fmaxf(a, -448.0f), 448.0f);
-  b = fminf(fmaxf(b, -448.0f), 448.0f);
+  a = a != a ? a : fminf(fmaxf(a, -448.0f), 448.0f);
+  b = b != b ? b : fminf(fmaxf(b, -448.0f), 448.0f);
   return (unsigned short)(__builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false) & 0xffff);
 }
 

@@ -819,21 +819,29 @@ def _e4m3(q):  # uint8 e4m3 bits -> float32 (torch's own decoder)
 def test_layernorm_and_row_quantisation_to_fp8(backend, rows, d, act):
     """sbk_layernorm_fp8o / sbk_quant_rows_fp8: e4m3 rows with one fp32 scale per row.  scale = row maximum / 448 (the largest
     element maps to +-448 exactly), every element is the e4m3 rounding of value / scale (at most half an e4m3 step: 2^-4
-    relative, plus the subnormal step), an all-zero row gets scale 1."""
+    relative, plus the subnormal step), an all-zero row gets scale 1.  The LayerNorm form is measured against the fp64
+    LayerNorm (tests/norm_host_ref.py), with the project's bound -- max(4 x the fp32 torch composition's error, 1e-5) -- added."""
+    import norm_host_ref as R
+
     nat, dev = backend
     g = torch.Generator().manual_seed(rows + d)
     x = torch.randn(rows, d, generator=g) * 2.5 + 0.3
     x[1] = 0.0
     gamma, beta = torch.randn(d, generator=g), torch.randn(d, generator=g) * 0.2
     code = nat.ACT_SWISH if act else nat.ACT_NONE
-    ref = nat.layernorm(x.to(dev), gamma.to(dev), beta.to(dev), 1e-5, act=code).cpu()
-    for name, got, want in (("ln", nat.layernorm_fp8(x.to(dev), gamma.to(dev), beta.to(dev), 1e-5, act=code), ref),
-                            ("plain", nat.quant_rows_fp8(x.to(dev)), x)):
-        sc = got.scale.cpu()
+    ref = R.layernorm(x.double(), gamma.double(), beta.double(), 1e-5, code)
+    err32 = float((R.layernorm(x, gamma, beta, 1e-5, code).double() - ref).abs().max())
+    bound = max(4.0 * err32, 1e-5)
+    for name, got, want, slack in (("ln", nat.layernorm_fp8(x.to(dev), gamma.to(dev), beta.to(dev), 1e-5, act=code), ref, bound),
+                                   ("plain", nat.quant_rows_fp8(x.to(dev)), x.double(), 0.0)):
+        sc = got.scale.cpu().double()
         amax = want.abs().amax(1)
-        assert torch.allclose(sc, torch.where(amax > 0, amax / 448.0, torch.ones(())), rtol=1e-6, atol=0), name
-        deq = _e4m3(got.q).view(rows, d) * sc[:, None]
-        assert float(((deq - want).abs() - (want.abs() * 2.0 ** -4 + sc[:, None] * 2.0 ** -10)).max()) <= 0.0, name
+        want_sc = torch.where(amax > 0, amax / 448.0, torch.ones((), dtype=torch.float64))
+        assert float(((sc - want_sc).abs() - (1e-6 * want_sc + slack / 448.0)).max()) <= 0.0, name
+        deq = _e4m3(got.q).view(rows, d).double() * sc[:, None]
+        over = float(((deq - want).abs() - (want.abs() * 2.0 ** -4 + sc[:, None] * 2.0 ** -10)).max())
+        print(f"fp8 rows {name} {rows}x{d} act={act}: beyond the e4m3 step {over:.3e}, bound {slack:.3e}")
+        assert over <= slack, name
         assert float(_e4m3(got.q).abs().max()) == 448.0
     if d <= 2048:  # bf16 rows in (the attention context): the same scales and bytes as from the widened values
         xb = x.to(torch.bfloat16)

@@ -272,7 +272,11 @@ static inline unsigned char f32_to_fp8_(float x) {  // nearest even, saturating 
   }
   return s | best;
 }
+// (the device header's written form: saturating at +-448, +-inf included; a NaN passes the clamp and becomes the NaN code;
+// f32_to_fp8_ above stands in for v_cvt_pk_fp8_f32)
 static inline unsigned short f32x2_to_fp8(float a, float b) {
+  a = a != a ? a : fminf(fmaxf(a, -448.0f), 448.0f);
+  b = b != b ? b : fminf(fmaxf(b, -448.0f), 448.0f);
   return (unsigned short)(f32_to_fp8_(a) | ((unsigned)f32_to_fp8_(b) << 8));
 }
 struct __attribute__((aligned(16))) f16x8 {
