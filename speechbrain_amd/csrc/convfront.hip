@@ -19,6 +19,7 @@
 // activation never goes to HBM.
 #include "common.h"
 #include "device.h"
+#include "kernel_util.h"
 
 namespace {
 
@@ -35,15 +36,8 @@ struct ConvArgs {
   float eps, slope;
 };
 
-__device__ __forceinline__ int reflect1(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
-
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = sbk::wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
+using sbk::block_sum;
+using sbk::reflect1;
 
 template <int KS>  // KS x KS taps, stride 2, reflect padding KS / 2 (3 or 5)
 __global__ void __launch_bounds__(256) conv_block_kernel(ConvArgs a) {

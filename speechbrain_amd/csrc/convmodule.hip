@@ -9,6 +9,7 @@
 // (Conv1d zero padding); frames past an utterance's true length are NOT
 // masked here, exactly like the reference (Conformer.py:315-328 masks only
 // the module output).
+#include "act.h"
 #include "common.h"
 
 namespace {
@@ -36,7 +37,7 @@ __global__ void __launch_bounds__(256) glu_dwconv_kernel(const float* __restrict
     if (ch_ok && t >= 0 && t < T) {
       const float a = hb[(size_t)t * 2 * d + ch];
       const float gate = hb[(size_t)t * 2 * d + d + ch];
-      v = a * (1.0f / (1.0f + expf(-gate)));
+      v = a * sbk::sigmoid(gate);
     }
     g[r][c] = v;
   }

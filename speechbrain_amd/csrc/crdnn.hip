@@ -17,6 +17,7 @@
 // LayerNorm statistics in the two-pass form of sbk_layernorm_f32 (biased variance, eps inside the root).
 #include "common.h"
 #include "device.h"
+#include "kernel_util.h"
 
 namespace {
 
@@ -33,15 +34,8 @@ struct FrameArgs {
   float eps, slope;
 };
 
-__device__ __forceinline__ int reflect1(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
-
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = sbk::wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
+using sbk::block_sum;
+using sbk::reflect1;
 
 template <bool CONV1>
 __global__ void __launch_bounds__(256) crdnn_frame_kernel(FrameArgs a) {

@@ -14,6 +14,7 @@
 //     fastest: a wave reads and writes 64 consecutive banks), each thread keeps the ksize taps of its channel and a
 //     window of 16 + ksize - 1 staged frames in registers, slides over its 16 output frames, applies the gate
 //     activation and multiplies by x1 on the way out.
+#include "act.h"
 #include "common.h"
 
 namespace {
@@ -22,10 +23,12 @@ constexpr int kTT = 64;             // output frames per workgroup
 constexpr int kCT = 64;             // channels per workgroup
 constexpr int kNOUT = kTT / 4;      // output frames per thread (4 waves = 4 frame quarters)
 
+// The gate's activation: NONE, SWISH, GELU or RELU (sbk_csgu_f32 refuses the rest).  Not sbk::act: its LEAKY_RELU arm, which
+// no launch can reach, would add 580 bytes to every instantiation of csgu_kernel.
 __device__ __forceinline__ float gate_f(float v, int act) {
-  if (act == SBK_ACT_SWISH) return v / (1.0f + expf(-v));
-  if (act == SBK_ACT_GELU) return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
-  if (act == SBK_ACT_RELU) return v > 0.0f ? v : 0.0f;
+  if (act == SBK_ACT_SWISH) return sbk::swish(v);
+  if (act == SBK_ACT_GELU) return sbk::gelu_erf(v);
+  if (act == SBK_ACT_RELU) return sbk::relu(v);
   return v;
 }
 

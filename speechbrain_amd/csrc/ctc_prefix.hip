@@ -29,6 +29,7 @@
 // zeros here and map back to -1e20 whenever a log-domain number leaves the kernels.
 #include "common.h"
 #include "internal.h"
+#include "kernel_util.h"
 
 namespace {
 
@@ -667,11 +668,6 @@ __global__ void __launch_bounds__(256) am_only_kernel(const float* __restrict__ 
 // the full scorers) and gives every other token minus_inf; <eos> always gets its score, blank never does.  Here the
 // dense psi of the full scorer is computed anyway (it is one matrix product), so the partial scorer is a mask:
 // thr[n] = k-th largest entry of row n, found by bisection over the order-preserving integer image of the floats.
-__device__ __forceinline__ unsigned order_key(float x) {
-  const unsigned u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 __global__ void __launch_bounds__(256) row_kth_largest_kernel(const float* __restrict__ x, float* __restrict__ thr, int V,
                                                               int k) {
   __shared__ int cnt[4];
@@ -681,7 +677,7 @@ __global__ void __launch_bounds__(256) row_kth_largest_kernel(const float* __res
   for (int bit = 31; bit >= 0; --bit) {
     const unsigned t = prefix | (1u << bit);
     int c = 0;
-    for (int i = threadIdx.x; i < V; i += 256) c += order_key(xr[i]) >= t ? 1 : 0;
+    for (int i = threadIdx.x; i < V; i += 256) c += sbk::order_key(xr[i]) >= t ? 1 : 0;
     c = (int)sbk::wave_sum((float)c);  // counts <= V < 2^24: exact in fp32
     if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = c;
     __syncthreads();

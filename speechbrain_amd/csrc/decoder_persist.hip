@@ -22,6 +22,7 @@
 // Results: same algorithm, another summation order than the launch-per-operation kernels (tests: ids equal, 1e-4).
 #include <math.h>
 
+#include "act.h"
 #include "internal.h"
 
 #include <string.h>
@@ -62,16 +63,6 @@ constexpr int kWB = 16;  // operand loads (16 bytes each, 16 k apart) a wave kee
 struct WPref {           // the first block of this wave's first tile of the NEXT projection
   float4 w[kWB];
 };
-
-__device__ __forceinline__ float act_of(float v, int act) {
-  switch (act) {
-    case SBK_ACT_SWISH: return v / (1.0f + expf(-v));
-    case SBK_ACT_GELU: return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
-    case SBK_ACT_RELU: return v > 0.0f ? v : 0.0f;
-    case SBK_ACT_LEAKY_RELU: return v > 0.0f ? v : 0.01f * v;
-    default: return v;
-  }
-}
 
 // address of this lane's first operand of tile `tile` (16 columns from tile * 16; rows past N re-read row N - 1)
 __device__ __forceinline__ const float* w_lane_ptr(const float* W, int K, int N, int tile) {
@@ -211,7 +202,7 @@ __device__ __forceinline__ void tiles_gemm(const PStepArgs& a, const float* xs, 
     __syncthreads();
     if (out_ok) {
       float v = (red[tid] + red[256 + tid]) + (red[512 + tid] + red[768 + tid]);
-      v = act_of(v + (bias ? bias[col] : 0.0f), act) + rv;
+      v = sbk::act(v + (bias ? bias[col] : 0.0f), act) + rv;
       sbk::st_agent(C + (size_t)row * N + col, v);
     }
   }

@@ -9,6 +9,7 @@
 // into registers one K tile ahead, so HBM latency hides under the MFMAs.
 // The epilogue (bias, activation, scaled residual) runs on the accumulators in
 // registers and writes 128-byte rows (32 lanes x 4 B) per store instruction.
+#include "act.h"
 #include "common.h"
 #include "internal.h"
 
@@ -39,25 +40,7 @@ __device__ __forceinline__ void tile_epilogue_32x32(const GemmArgs& g, float (&v
   }
 #pragma unroll
   for (int q = 0; q < 16; ++q) v[q] += bv;
-  switch (g.act) {  // uniform
-    case SBK_ACT_SWISH:
-#pragma unroll
-      for (int q = 0; q < 16; ++q) v[q] = v[q] / (1.0f + expf(-v[q]));
-      break;
-    case SBK_ACT_GELU:
-#pragma unroll
-      for (int q = 0; q < 16; ++q) v[q] = 0.5f * v[q] * (1.0f + erff(v[q] * 0.70710678118654752440f));
-      break;
-    case SBK_ACT_RELU:
-#pragma unroll
-      for (int q = 0; q < 16; ++q) v[q] = v[q] > 0.0f ? v[q] : 0.0f;
-      break;
-    case SBK_ACT_LEAKY_RELU:
-#pragma unroll
-      for (int q = 0; q < 16; ++q) v[q] = v[q] > 0.0f ? v[q] : 0.01f * v[q];
-      break;
-    default: break;
-  }
+  sbk::act_tile<16>(v, g.act);  // (one uniform switch)
   if (g.seq_len) {  // uniform
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
@@ -248,7 +231,7 @@ __device__ __forceinline__ void gemm_nt_tile(const GemmArgs& g, int* tile_x = nu
       for (int r = 0; r < 16; ++r) {
         const int row = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
         if (row >= g.M) continue;
-        float v = apply_act(acc[i][j][r] + bv, g.act) * g.alpha;
+        float v = sbk::act(acc[i][j][r] + bv, g.act) * g.alpha;
         if (g.seq_len && (row % g.rows_per_seq) >= g.seq_len[row / g.rows_per_seq]) v = 0.0f;
         if (g.R) v += g.R[(size_t)row * g.ldr + col];
         g.C[(size_t)row * g.ldc + col] = v;
@@ -581,25 +564,7 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_sk_kernel(SkArgs s) {
           v[4 * g + 2] = acc[0][j][4 * g + 2] + bv[g].z;
           v[4 * g + 3] = acc[0][j][4 * g + 3] + bv[g].w;
         }
-        switch (act) {  // uniform
-          case SBK_ACT_SWISH:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = v[r] / (1.0f + expf(-v[r]));
-            break;
-          case SBK_ACT_GELU:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = 0.5f * v[r] * (1.0f + erff(v[r] * 0.70710678118654752440f));
-            break;
-          case SBK_ACT_RELU:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = v[r] > 0.0f ? v[r] : 0.0f;
-            break;
-          case SBK_ACT_LEAKY_RELU:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = v[r] > 0.0f ? v[r] : 0.01f * v[r];
-            break;
-          default: break;
-        }
+        sbk::act_tile<16>(v, act);  // (one uniform switch)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           const int col = n0 + wn0 + j * 32 + 8 * g + 4 * half;
@@ -621,25 +586,7 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_sk_kernel(SkArgs s) {
         float v[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) v[r] = acc[i][j][r] + bv;
-        switch (act) {  // uniform
-          case SBK_ACT_SWISH:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = v[r] / (1.0f + expf(-v[r]));
-            break;
-          case SBK_ACT_GELU:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = 0.5f * v[r] * (1.0f + erff(v[r] * 0.70710678118654752440f));
-            break;
-          case SBK_ACT_RELU:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = v[r] > 0.0f ? v[r] : 0.0f;
-            break;
-          case SBK_ACT_LEAKY_RELU:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = v[r] > 0.0f ? v[r] : 0.01f * v[r];
-            break;
-          default: break;
-        }
+        sbk::act_tile<16>(v, act);  // (one uniform switch)
         if (seq_len) {  // uniform
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
@@ -843,7 +790,7 @@ __global__ void __launch_bounds__(256, 2) gemm_skinny_kernel(GemmArgs g, float* 
     if (to_partial) {
       P[(size_t)row * g.N + col] = sum;
     } else {
-      float v = apply_act(sum + bv, g.act) * g.alpha;
+      float v = sbk::act(sum + bv, g.act) * g.alpha;
       if (g.seq_len && (row % g.rows_per_seq) >= g.seq_len[row / g.rows_per_seq]) v = 0.0f;
       if (g.R) v += g.R[(size_t)row * g.ldr + col];
       g.C[(size_t)row * g.ldc + col] = v;
@@ -1020,7 +967,7 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(GemmArgs g, const fl
     const int row = (int)(i / g.N), col = (int)(i % g.N);
     float acc = partial[i];
     for (int ks = 1; ks < SK; ++ks) acc += partial[(size_t)ks * total + i];
-    float v = apply_act(acc + (g.bias ? g.bias[col] : 0.0f), g.act) * g.alpha;
+    float v = sbk::act(acc + (g.bias ? g.bias[col] : 0.0f), g.act) * g.alpha;
     if (g.seq_len && (row % g.rows_per_seq) >= g.seq_len[row / g.rows_per_seq]) v = 0.0f;
     if (g.R) v += g.R[(size_t)row * g.ldr + col];
     g.C[(size_t)row * g.ldc + col] = v;
@@ -1257,7 +1204,7 @@ extern "C" int sbk_gemm_nt_f32(const float* A, int lda, const float* W, int ldw,
   SBK_REQUIRE(lda > 0 && ldw >= K, "gemm: leading dimension of an operand smaller than the row (lda=%d ldw=%d)", lda, ldw);
   SBK_REQUIRE(ldc >= N, "gemm: leading dimension smaller than the row (ldc=%d, N=%d)", ldc, N);
   SBK_REQUIRE(!residual || ldr >= N, "gemm: residual stride");
-  SBK_REQUIRE(act >= SBK_ACT_NONE && act <= SBK_ACT_LEAKY_RELU, "gemm: unknown activation %d", act);
+  SBK_REQUIRE(sbk::act_known(act), "gemm: unknown activation %d", act);
   SBK_REQUIRE(!seq_len || rows_per_seq > 0, "gemm: seq_len given without rows_per_seq");
   return sbk::gemm_nt_ws(A, lda, W, ldw, bias, residual, ldr, C, ldc, M, N, K, act, alpha, seq_len, rows_per_seq,
                          nullptr, 0, sbk::as_stream(stream));
@@ -1287,7 +1234,7 @@ extern "C" int sbk_gemm_nt_splitk_f32(const float* A, int lda, const float* W, i
   SBK_REQUIRE(lda >= K && ldw >= K, "gemm: leading dimension of an operand smaller than the row (lda=%d ldw=%d)", lda, ldw);
   SBK_REQUIRE(ldc >= N, "gemm: leading dimension smaller than the row (ldc=%d, N=%d)", ldc, N);
   SBK_REQUIRE(!residual || ldr >= N, "gemm: residual stride");
-  SBK_REQUIRE(act >= SBK_ACT_NONE && act <= SBK_ACT_LEAKY_RELU, "gemm: unknown activation %d", act);
+  SBK_REQUIRE(sbk::act_known(act), "gemm: unknown activation %d", act);
   return sbk::gemm_nt_ws(A, lda, W, ldw, bias, residual, ldr, C, ldc, M, N, K, act, alpha, nullptr, 0, workspace,
                          workspace ? workspace_floats : 0, sbk::as_stream(stream));
 }
@@ -1341,7 +1288,7 @@ extern "C" int sbk_gemm_nt_f32x3(const float* A, int lda, const uint16_t* W3, co
   SBK_REQUIRE(N % 4 == 0 && ldc % 4 == 0 && sbk::aligned16(C) && (!bias || sbk::aligned16(bias)),
               "gemm_f32x3: N and ldc must be multiples of 4, C / bias 16-byte aligned (rows are stored as 16-byte vectors)");
   SBK_REQUIRE(!residual || (ldr >= N && ldr % 4 == 0 && sbk::aligned16(residual)), "gemm_f32x3: residual stride / alignment");
-  SBK_REQUIRE(act >= SBK_ACT_NONE && act <= SBK_ACT_LEAKY_RELU, "gemm_f32x3: unknown activation %d", act);
+  SBK_REQUIRE(sbk::act_known(act), "gemm_f32x3: unknown activation %d", act);
   SBK_REQUIRE(!seq_len || rows_per_seq > 0, "gemm_f32x3: seq_len given without rows_per_seq");
   const int rc = sbk::gemm_nt_x3(A, lda, W3, bias, residual, ldr, C, ldc, M, N, K, act, alpha, seq_len, rows_per_seq,
                                  sbk::as_stream(stream));

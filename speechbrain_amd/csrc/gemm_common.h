@@ -1,18 +1,9 @@
-// Shared by the contraction translation units (gemm.hip, gemm_lp.hip): the epilogue's activation and the fp32 launch record.
+// Shared by the contraction translation units (gemm.hip, gemm_lp.hip): the fp32 launch record (the epilogue's activation is act.h).
 #pragma once
+#include "act.h"
 #include "common.h"
 
 namespace {
-
-__device__ __forceinline__ float apply_act(float v, int act) {
-  switch (act) {
-    case SBK_ACT_SWISH: return v / (1.0f + expf(-v));
-    case SBK_ACT_GELU: return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
-    case SBK_ACT_RELU: return v > 0.0f ? v : 0.0f;
-    case SBK_ACT_LEAKY_RELU: return v > 0.0f ? v : 0.01f * v;
-    default: return v;
-  }
-}
 
 struct GemmArgs {
   const float* A;

@@ -178,7 +178,7 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_lp_kernel(GemmBf16Args g) {
       for (int r = 0; r < 16; ++r) {
         const int row = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
         if (row >= g.M) continue;
-        float v = apply_act(acc[i][j][r] * out_mul + bv, g.act) * g.alpha;
+        float v = sbk::act(acc[i][j][r] * out_mul + bv, g.act) * g.alpha;
         if (g.seq_len && (row % g.rows_per_seq) >= g.seq_len[row / g.rows_per_seq]) v = 0.0f;
         if (g.R) v += g.R[(size_t)row * g.ldr + col];
         g.C[(size_t)row * g.ldc + col] = v;
@@ -317,25 +317,7 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_bf16dma_kernel(Bf16DmaArgs s) 
         float v[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) v[r] = acc[i][jj][r] + bv;
-        switch (act) {  // uniform
-          case SBK_ACT_SWISH:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = v[r] / (1.0f + expf(-v[r]));
-            break;
-          case SBK_ACT_GELU:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = sbk::gelu_erfc(v[r]);
-            break;
-          case SBK_ACT_RELU:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = v[r] > 0.0f ? v[r] : 0.0f;
-            break;
-          case SBK_ACT_LEAKY_RELU:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = v[r] > 0.0f ? v[r] : 0.01f * v[r];
-            break;
-          default: break;
-        }
+        sbk::act_tile<16, sbk::Gelu::erfc>(v, act);  // (one uniform switch)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int row = rbase + (r & 3) + 8 * (r >> 2);
@@ -516,25 +498,7 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_fp8dma_kernel(Fp8DmaArgs s) {
         float v[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) v[r] = acc[i][jj][r] * (rs[r] * cs) + bv;
-        switch (act) {  // uniform
-          case SBK_ACT_SWISH:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = v[r] / (1.0f + expf(-v[r]));
-            break;
-          case SBK_ACT_GELU:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = sbk::gelu_erfc(v[r]);
-            break;
-          case SBK_ACT_RELU:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = v[r] > 0.0f ? v[r] : 0.0f;
-            break;
-          case SBK_ACT_LEAKY_RELU:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = v[r] > 0.0f ? v[r] : 0.01f * v[r];
-            break;
-          default: break;
-        }
+        sbk::act_tile<16, sbk::Gelu::erfc>(v, act);  // (one uniform switch)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int row = rbase + (r & 3) + 8 * (r >> 2);
@@ -669,7 +633,7 @@ int require_lp(const char* who, bool operands, int kq, const float* A, int lda, 
   SBK_REQUIRE(ldc >= N, "%s: leading dimension smaller than the row (ldc=%d, N=%d)", who, ldc, N);
   SBK_REQUIRE(sbk::aligned16(A) && sbk::aligned16(W), "%s: operands must be 16-byte aligned", who);
   SBK_REQUIRE(!residual || ldr >= N, "%s: residual stride", who);
-  SBK_REQUIRE(act >= SBK_ACT_NONE && act <= SBK_ACT_LEAKY_RELU, "%s: unknown activation %d", who, act);
+  SBK_REQUIRE(sbk::act_known(act), "%s: unknown activation %d", who, act);
   SBK_REQUIRE(!seq_len || rows_per_seq > 0, "%s: seq_len given without rows_per_seq", who);
   return 0;
 }
@@ -694,7 +658,7 @@ extern "C" int sbk_gemm_nt_bf16a(const uint16_t* A, int lda, const uint16_t* Wb,
               "gemm_bf16a: operand rows must be 16-byte aligned (lda=%d ldw=%d)", lda, ldw);
   SBK_REQUIRE((!C || ldc >= N) && (!Cb || ldcb >= N), "gemm_bf16a: leading dimension smaller than the row (ldc=%d ldcb=%d, N=%d)", ldc, ldcb, N);
   SBK_REQUIRE(!residual || ldr >= N, "gemm_bf16a: residual stride");
-  SBK_REQUIRE(act >= SBK_ACT_NONE && act <= SBK_ACT_LEAKY_RELU, "gemm_bf16a: unknown activation %d", act);
+  SBK_REQUIRE(sbk::act_known(act), "gemm_bf16a: unknown activation %d", act);
   hipStream_t st = sbk::as_stream(stream);
   sbk::ProfScope prof("gemm_nt_bf16a", 2.0 * M * (double)N * K,
                       2.0 * ((double)M * K + (double)N * K) + ((C ? 4.0 : 0.0) + (Cb ? 2.0 : 0.0) + (residual ? 4.0 : 0.0)) * M * (double)N, st);
@@ -718,7 +682,7 @@ extern "C" int sbk_gemm_nt_fp8a(const uint8_t* A8, int lda, const float* a_scale
               "gemm_fp8a: leading dimension smaller than the row (ldc=%d ldcb=%d ldc8=%d, N=%d)", ldc, ldcb, ldc8, N);
   SBK_REQUIRE(!C8 || c8_scale > 0.0f, "gemm_fp8a: non-positive fp8 output scale");
   SBK_REQUIRE(!residual || ldr >= N, "gemm_fp8a: residual stride");
-  SBK_REQUIRE(act >= SBK_ACT_NONE && act <= SBK_ACT_LEAKY_RELU, "gemm_fp8a: unknown activation %d", act);
+  SBK_REQUIRE(sbk::act_known(act), "gemm_fp8a: unknown activation %d", act);
   hipStream_t st = sbk::as_stream(stream);
   sbk::ProfScope prof("gemm_nt_fp8a", 2.0 * M * (double)N * K,
                       1.0 * ((double)M * K + (double)N * K) + ((C ? 4.0 : 0.0) + (Cb ? 2.0 : 0.0) + (C8 ? 1.0 : 0.0) + (residual ? 4.0 : 0.0)) * M * (double)N, st);

@@ -27,6 +27,7 @@
 // Arithmetic, epilogue and outputs are gemm_nt_bf16dma_kernel's / gemm_nt_fp8dma_kernel's (fp32 accumulation; per-row scales of
 // both fp8 operands applied to the accumulators; bias, activation, alpha, fp32 residual; fp32 / bf16 / e4m3 outputs): the same sums
 // in the same order per output element (K ascending, one accumulator), so the two kernels agree bit for bit.
+#include "act.h"
 #include "common.h"
 #include "internal.h"
 
@@ -244,7 +245,7 @@ __global__ void __launch_bounds__(512, 2) gemm_nt_lp256_kernel(sbk::Lp256Args s)
         }
         if constexpr (ACT == SBK_ACT_SWISH) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = v[e] / (1.0f + expf(-v[e]));
+          for (int e = 0; e < 4; ++e) v[e] = sbk::swish(v[e]);
         } else if constexpr (ACT == SBK_ACT_GELU) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = sbk::gelu_erfc(v[e]);

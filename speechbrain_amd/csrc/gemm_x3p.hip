@@ -29,6 +29,7 @@
 // XCD's eighth of the tile indices is a block of rows x one column group and its L2 keeps that group's W panels: 155.6 / 160.9 us
 // against 156.3 at (12 800, 2 048, 512), 135.5 / 136.0 against 135.0 at (14 016, 1 536, 512), 101.3 / 102.2 against 99.6 at
 // (14 016, 1 024, 512), profiles/r05_q_*: the kernel is not bound by what crosses the fabric.  Not kept.)
+#include "act.h"
 #include "common.h"
 #include "internal.h"
 
@@ -292,25 +293,7 @@ __global__ void __launch_bounds__(512, 2) gemm_nt_x3p_kernel(X3pArgs s) {
           v[4 * g + 2] = acc[i][jj][4 * g + 2] + bv[g].z;
           v[4 * g + 3] = acc[i][jj][4 * g + 3] + bv[g].w;
         }
-        switch (act) {  // uniform
-          case SBK_ACT_SWISH:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = v[r] / (1.0f + expf(-v[r]));
-            break;
-          case SBK_ACT_GELU:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = 0.5f * v[r] * (1.0f + erff(v[r] * 0.70710678118654752440f));
-            break;
-          case SBK_ACT_RELU:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = v[r] > 0.0f ? v[r] : 0.0f;
-            break;
-          case SBK_ACT_LEAKY_RELU:
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = v[r] > 0.0f ? v[r] : 0.01f * v[r];
-            break;
-          default: break;
-        }
+        sbk::act_tile<16>(v, act);  // (one uniform switch)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           const int col = n0 + wcol0 + jj * 32 + 8 * g + 4 * half;
@@ -391,7 +374,7 @@ __global__ void __launch_bounds__(512, 2) gemm_nt_x3p_kernel(X3pArgs s) {
         }
         if constexpr (ACT == SBK_ACT_SWISH) {
 #pragma unroll
-          for (int r = 0; r < 16; ++r) v[r] = v[r] / (1.0f + expf(-v[r]));
+          for (int r = 0; r < 16; ++r) v[r] = sbk::swish(v[r]);
         } else {
           static_assert(ACT == SBK_ACT_NONE, "x3p: activation not instantiated in the straight-line epilogue");
         }
@@ -624,7 +607,7 @@ extern "C" int sbk_gemm_nt_x3p(const uint16_t* PA, const uint16_t* PW, const flo
               "gemm_x3p: N and ldc must be multiples of 4, C / bias 16-byte aligned (rows are stored as 16-byte vectors)");
   SBK_REQUIRE(!PC || (N % 16 == 0 && sbk::aligned16(PC)), "gemm_x3p: a panel result needs N %% 16 == 0");
   SBK_REQUIRE(!residual || (ldr >= N && ldr % 4 == 0 && sbk::aligned16(residual)), "gemm_x3p: residual stride / alignment");
-  SBK_REQUIRE(act >= SBK_ACT_NONE && act <= SBK_ACT_LEAKY_RELU, "gemm_x3p: unknown activation %d", act);
+  SBK_REQUIRE(sbk::act_known(act), "gemm_x3p: unknown activation %d", act);
   SBK_REQUIRE(!seq_len || rows_per_seq > 0, "gemm_x3p: seq_len given without rows_per_seq");
   const int rc = sbk::gemm_nt_x3p(PA, PW, bias, residual, ldr, C, ldc, PC, M, N, K, act, alpha, seq_len, rows_per_seq,
                                   sbk::as_stream(stream));

@@ -1,6 +1,7 @@
 // Few-row fp32 contraction on the bf16 matrix pipe: sbk_gemm_nt_x3r / sbk_gemm_ln_nt_x3r (the decode step's projections of the
 // grouped searches; reference: the Linear layers of TransformerDecoderLayer.forward, lobes/models/transformer/Transformer.py:751-834).
 // Moved out of gemm.hip in round 5 together with the removal of its measured-and-lost variants.
+#include "act.h"
 #include "common.h"
 #include "internal.h"
 
@@ -269,22 +270,23 @@ __global__ void __launch_bounds__(256, 2) gemm_x3r_kernel(X3rArgs g) {
   for (int q4 = 0; q4 < 4; ++q4) {
     o[4 * q4] = v[q4].x + bv[q4].x, o[4 * q4 + 1] = v[q4].y + bv[q4].y, o[4 * q4 + 2] = v[q4].z + bv[q4].z, o[4 * q4 + 3] = v[q4].w + bv[q4].w;
   }
+  // (sbk::act_tile<16> written out: through the template the K = 1 280 LayerNorm instantiation, which spills, came out 304 bytes shorter)
   switch (g.act) {  // uniform
     case SBK_ACT_SWISH:
 #pragma unroll
-      for (int q = 0; q < 16; ++q) o[q] = o[q] / (1.0f + expf(-o[q]));
+      for (int q = 0; q < 16; ++q) o[q] = sbk::swish(o[q]);
       break;
     case SBK_ACT_GELU:
 #pragma unroll
-      for (int q = 0; q < 16; ++q) o[q] = 0.5f * o[q] * (1.0f + erff(o[q] * 0.70710678118654752440f));
+      for (int q = 0; q < 16; ++q) o[q] = sbk::gelu_erf(o[q]);
       break;
     case SBK_ACT_RELU:
 #pragma unroll
-      for (int q = 0; q < 16; ++q) o[q] = o[q] > 0.0f ? o[q] : 0.0f;
+      for (int q = 0; q < 16; ++q) o[q] = sbk::relu(o[q]);
       break;
     case SBK_ACT_LEAKY_RELU:
 #pragma unroll
-      for (int q = 0; q < 16; ++q) o[q] = o[q] > 0.0f ? o[q] : 0.01f * o[q];
+      for (int q = 0; q < 16; ++q) o[q] = sbk::leaky_relu(o[q]);
       break;
     default: break;
   }
@@ -401,7 +403,7 @@ extern "C" int sbk_gemm_nt_x3r(const float* A, int lda, const uint16_t* PW, cons
   SBK_REQUIRE(ldc >= N && ldc % 4 == 0 && sbk::aligned16(C), "gemm_x3r: C rows are stored as 16-byte vectors (ldc=%d)", ldc);
   SBK_REQUIRE(!residual || (ldr >= N && ldr % 4 == 0 && sbk::aligned16(residual)), "gemm_x3r: residual stride / alignment");
   SBK_REQUIRE(!bias || sbk::aligned16(bias), "gemm_x3r: bias alignment");
-  SBK_REQUIRE(act >= SBK_ACT_NONE && act <= SBK_ACT_LEAKY_RELU, "gemm_x3r: unknown activation %d", act);
+  SBK_REQUIRE(sbk::act_known(act), "gemm_x3r: unknown activation %d", act);
   const int rc = sbk::gemm_nt_x3r(A, lda, PW, bias, residual, ldr, C, ldc, M, N, K, act, alpha, sbk::as_stream(stream));
   if (rc == -1) return sbk::fail(SBK_EINVAL, "gemm_x3r: shape not eligible");
   return rc;
@@ -419,7 +421,7 @@ extern "C" int sbk_gemm_ln_nt_x3r(const float* A, int lda, const uint16_t* PWf, 
   SBK_REQUIRE(ldc >= N && ldc % 4 == 0 && sbk::aligned16(C), "gemm_ln_x3r: C rows are stored as 16-byte vectors (ldc=%d)", ldc);
   SBK_REQUIRE(!residual || (ldr >= N && ldr % 4 == 0 && sbk::aligned16(residual)), "gemm_ln_x3r: residual stride / alignment");
   SBK_REQUIRE(!bf || sbk::aligned16(bf), "gemm_ln_x3r: bias alignment");
-  SBK_REQUIRE(act >= SBK_ACT_NONE && act <= SBK_ACT_LEAKY_RELU, "gemm_ln_x3r: unknown activation %d", act);
+  SBK_REQUIRE(sbk::act_known(act), "gemm_ln_x3r: unknown activation %d", act);
   const int rc = sbk::gemm_ln_nt_x3r(A, lda, PWf, bf, residual, ldr, C, ldc, M, N, K, eps, act, alpha, sbk::as_stream(stream));
   if (rc == -1) return sbk::fail(SBK_EINVAL, "gemm_ln_x3r: shape not eligible");
   return rc;

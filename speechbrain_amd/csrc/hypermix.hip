@@ -25,6 +25,7 @@
 //                     one wave per frame normalises the d channels, adds the skip and stores.
 // Determinism: no atomics; splits = ceil(T / kSplitFrames) depends on T only; a thread's sums run in index order.
 // Contractions are vector FMAs on LDS operands (every operand is zero-padded to 16 columns in LDS, never read out of range).
+#include "act.h"
 #include "common.h"
 #include "internal.h"
 
@@ -53,8 +54,6 @@ struct HmArgs {
   int B, T, H, Dh, k, splits;
   float eps;
 };
-
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
 // acc[a][c] += sum_{r < R} X[r * ldx + tf + 16 a] * Y[r * ldy + te + 16 c]
 template <int NA, int NC>
@@ -122,7 +121,7 @@ __device__ __forceinline__ void finalise(const HmArgs& a, float* lds, int b, int
 #pragma unroll
       for (int x = 0; x < 2 * NA; ++x) {
         const int f = tg + 8 * x;
-        At_s[tj * (DP + 1) + f] = (tj < nj && f < Dh) ? gelu_erf(s[x]) : 0.0f;
+        At_s[tj * (DP + 1) + f] = (tj < nj && f < Dh) ? sbk::gelu_erf(s[x]) : 0.0f;
       }
     }
     __syncthreads();
@@ -217,7 +216,7 @@ __global__ void __launch_bounds__(256) hypermix_reduce_kernel(HmArgs a) {
           const int e = te + 16 * c;
           float v = 0.0f;
           if (r < nt) {
-            if (c < NA && e < Dh) v = gelu_erf(zz[x][c < NA ? c : 0] + b_s[e]);
+            if (c < NA && e < Dh) v = sbk::gelu_erf(zz[x][c < NA ? c : 0] + b_s[e]);
             else if (e == Dh) v = 1.0f;
           }
           z_s[r * EP + e] = v;
@@ -330,7 +329,7 @@ __global__ void __launch_bounds__(256) hypermix_apply_kernel(HmArgs a) {
         const int e = te + 16 * c;
         float v = 0.0f;
         if (row_ok) {
-          if (c < NA && e < Dh) v = gelu_erf(zz[c < NA ? c : 0] + b_s[e]);
+          if (c < NA && e < Dh) v = sbk::gelu_erf(zz[c < NA ? c : 0] + b_s[e]);
           else if (e == Dh) v = 1.0f;
         }
         z_s[tt * EP + e] = v;

@@ -23,10 +23,12 @@
 // row: vector loads straight from HBM/L2 into registers, no LDS staging.
 #include "common.h"
 #include "internal.h"
+#include "kernel_util.h"
 
 namespace {
 
 using sbk::f32x16;
+using sbk::load_run;
 
 struct AttnArgs {
   const float* qkv;       // [B,T,H,3*DH]
@@ -52,26 +54,6 @@ __device__ __forceinline__ void key_range(const AttnArgs& a, int i, int klen, in
     const int c = i / a.chunk;
     hi = min((c + 1) * a.chunk, klen);
     if (a.left >= 0) lo = max(0, (c - a.left) * a.chunk);
-  }
-}
-
-template <int N>
-__device__ __forceinline__ void load_run(float (&dst)[N], const float* __restrict__ p) {
-  if constexpr (N % 4 == 0) {
-#pragma unroll
-    for (int i = 0; i < N / 4; ++i) {
-      const float4 v = reinterpret_cast<const float4*>(p)[i];
-      dst[4 * i] = v.x; dst[4 * i + 1] = v.y; dst[4 * i + 2] = v.z; dst[4 * i + 3] = v.w;
-    }
-  } else if constexpr (N % 2 == 0) {
-#pragma unroll
-    for (int i = 0; i < N / 2; ++i) {
-      const float2 v = reinterpret_cast<const float2*>(p)[i];
-      dst[2 * i] = v.x; dst[2 * i + 1] = v.y;
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < N; ++i) dst[i] = p[i];
   }
 }
 

@@ -18,6 +18,7 @@
 //
 // Per step and direction the workgroups together read W_hh once per batch tile (16 MiB at H 1024: it stays in the Infinity Cache
 // between steps) and the [B,H] state once per workgroup.
+#include "act.h"
 #include "common.h"
 #include "device.h"
 
@@ -47,8 +48,6 @@ __device__ __forceinline__ float4 load_k4(const float* row, int k, int K, bool v
   return make_float4(k < K ? row[k] : 0.0f, k + 1 < K ? row[k + 1] : 0.0f, k + 2 < K ? row[k + 2] : 0.0f,
                      k + 3 < K ? row[k + 3] : 0.0f);
 }
-
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // The slice product and the cell update of one (direction, slice of hidden units, batch tile) at one step.  hprev: the rows of
 // h_{t-1} (row stride ldh) or nullptr for zeros; part: LDS [4 waves][32 rows][33].
@@ -110,8 +109,8 @@ __device__ __forceinline__ void lstm_slice_step(const RnnArgs& a, int d, int j0,
     }
     const size_t si = ((size_t)d * a.B + b) * H + j;
     const float c_prev = first ? (a.c0 != nullptr ? a.c0[si] : 0.0f) : a.cn[si];
-    const float c_new = sigmoid_f(g4[1]) * c_prev + sigmoid_f(g4[0]) * tanhf(g4[2]);
-    const float h_new = sigmoid_f(g4[3]) * tanhf(c_new);
+    const float c_new = sbk::sigmoid(g4[1]) * c_prev + sbk::sigmoid(g4[0]) * tanhf(g4[2]);
+    const float h_new = sbk::sigmoid(g4[3]) * tanhf(c_new);
     a.cn[si] = c_new;
     a.out[((size_t)b * a.T + t) * ((size_t)a.D * H) + (size_t)d * H + j] = h_new;
     if (last) a.hn[si] = h_new;

@@ -13,8 +13,10 @@
 // cannot change the result because full lists accept no further hypotheses.
 #include <limits.h>
 
+#include "argmax.h"
 #include "common.h"
 #include "internal.h"
+#include "kernel_util.h"
 
 #define SBK_HIP(expr)                                                              \
   do {                                                                             \
@@ -105,7 +107,7 @@ struct Cand {
   float v;
   int i;
 };
-__device__ __forceinline__ bool better(float v, int i, float v2, int i2) { return v > v2 || (v == v2 && i < i2); }
+using sbk::better;
 
 // Block-wide selection of the `k` best (value, index) pairs among the candidates a loader yields.
 // Every thread keeps a sorted top-16 list of its strided share (registers); the lists go to LDS, every
@@ -423,11 +425,6 @@ __global__ void __launch_bounds__(256) score_topk_row_kernel(ScoreArgs a) {
 // image of the candidate scores find the beam-th largest key, a fifth pass collects the winners
 // (ties on the threshold: lowest candidate index first, in index order), and a bitonic sort in LDS
 // emits them in descending order.
-__device__ __forceinline__ unsigned order_key(float v) {
-  const unsigned u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 __global__ void __launch_bounds__(1024) beam_topk_large_kernel(const float* __restrict__ comb,
                                                                const float* __restrict__ seq,
                                                                float* __restrict__ out_val,
@@ -462,7 +459,7 @@ __global__ void __launch_bounds__(1024) beam_topk_large_kernel(const float* __re
     __syncthreads();
     const unsigned prefix = s_prefix;
     for (int e = tid; e < total; e += 1024) {
-      const unsigned k = order_key(value(e));
+      const unsigned k = sbk::order_key(value(e));
       if (pass == 0 || (k >> (shift + 8)) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1);
     }
     __syncthreads();
@@ -494,7 +491,7 @@ __global__ void __launch_bounds__(1024) beam_topk_large_kernel(const float* __re
   __syncthreads();
   for (int e = tid; e < total; e += 1024) {
     const float v = value(e);
-    const unsigned k = order_key(v);
+    const unsigned k = sbk::order_key(v);
     if (k > thr) {
       const int slot = atomicAdd(&s_count, 1);
       if (slot < kMaxBeamLarge) {
@@ -526,7 +523,7 @@ __global__ void __launch_bounds__(1024) beam_topk_large_kernel(const float* __re
     __syncthreads();
     for (int e0 = 0; e0 < total; e0 += 1024) {
       const int e = e0 + tid;
-      const int is_eq = (e < total && order_key(value(e)) == thr) ? 1 : 0;
+      const int is_eq = (e < total && sbk::order_key(value(e)) == thr) ? 1 : 0;
       scan[tid] = is_eq;
       __syncthreads();
       for (int off = 1; off < 1024; off <<= 1) {  // inclusive Hillis-Steele scan of the tie flags

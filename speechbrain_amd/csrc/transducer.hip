@@ -7,6 +7,7 @@
 #include <math.h>
 #include <string.h>
 
+#include "act.h"
 #include "argmax.h"
 #include "common.h"
 #include "device.h"
@@ -45,17 +46,6 @@ struct TdArgs {
   float* score;     // [B]
   int B, T, F, S, blank, act, start;
 };
-
-__device__ __forceinline__ float sigmoid_f32(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-__device__ __forceinline__ float joint_act(float x, int act) {
-  switch (act) {
-    case SBK_ACT_GELU: return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
-    case SBK_ACT_LEAKY_RELU: return x > 0.0f ? x : x * 0.01f;
-    case SBK_ACT_RELU: return x <= 0.0f ? 0.0f : x;  // (NaN stays NaN, as torch.relu)
-    default: return tanhf(x);
-  }
-}
 
 // out[f * ldo + n] = bias[n] + sum_k w[n][k] * x[f * ldx + k] for f < nx, n < N; w [N][K] row-major (torch's layout), x in
 // LDS.  One wave per group of R rows, lanes across k (float4 loads of w when K % 4 == 0), then a fixed butterfly: every
@@ -107,7 +97,7 @@ __device__ __forceinline__ void gemv_rows(const float* __restrict__ w, const flo
       for (int f = 0; f < NX; ++f) {
         if (f >= nx) break;
         float v = acc[r][f];
-        for (int m = 32; m >= 1; m >>= 1) v += shfl_xor(v, m);
+        for (int m = 32; m >= 1; m >>= 1) v += shfl_xor(v, m);  // (sbk::wave_sum; its unroll pragma changes the greedy kernel's code)
         if (lane == 0 && n0 + r < N) out[(size_t)f * ldo + n0 + r] = bias ? v + bias[n0 + r] : v;
       }
     }
@@ -117,10 +107,10 @@ __device__ __forceinline__ void gemv_rows(const float* __restrict__ w, const flo
 // The cell update of one LSTM step from the gates' input part s_g and recurrent part s_gh (torch gate order i, f, g, o).
 __device__ __forceinline__ void lstm_update(const float* s_g, const float* s_gh, float* hl, float* cl, int H) {
   for (int m = threadIdx.x; m < H; m += kTdThreads) {
-    const float ig = sigmoid_f32(s_g[m] + s_gh[m]);
-    const float fg = sigmoid_f32(s_g[H + m] + s_gh[H + m]);
+    const float ig = sbk::sigmoid(s_g[m] + s_gh[m]);
+    const float fg = sbk::sigmoid(s_g[H + m] + s_gh[H + m]);
     const float gg = tanhf(s_g[2 * H + m] + s_gh[2 * H + m]);
-    const float og = sigmoid_f32(s_g[3 * H + m] + s_gh[3 * H + m]);
+    const float og = sbk::sigmoid(s_g[3 * H + m] + s_gh[3 * H + m]);
     const float cn = fg * cl[m] + ig * gg;
     cl[m] = cn;
     hl[m] = og * tanhf(cn);
@@ -156,10 +146,10 @@ __device__ __forceinline__ void log_softmax_stats(const float* x, int V, float& 
   const int lane = threadIdx.x & 63;
   m = -INFINITY;
   for (int v = lane; v < V; v += 64) m = fmaxf(m, x[v]);
-  for (int s = 32; s >= 1; s >>= 1) m = fmaxf(m, shfl_xor(m, s));
+  m = sbk::wave_max(m);
   float se = 0.0f;
   for (int v = lane; v < V; v += 64) se += expf(x[v] - m);
-  for (int s = 32; s >= 1; s >>= 1) se += shfl_xor(se, s);
+  se = sbk::wave_sum(se);
   ls = logf(se);
 }
 
@@ -199,18 +189,18 @@ __device__ void lm_step(const sbk_rnnlm_weights& M, int tok, float* s_h, float* 
     if (wave == 0) {
       float s = 0.0f;
       for (int k = lane; k < D; k += 64) s += y[k];
-      for (int m = 32; m >= 1; m >>= 1) s += shfl_xor(s, m);
+      s = sbk::wave_sum(s);
       const float mean = s / (float)D;
       float q = 0.0f;
       for (int k = lane; k < D; k += 64) q += (y[k] - mean) * (y[k] - mean);
-      for (int m = 32; m >= 1; m >>= 1) q += shfl_xor(q, m);
+      q = sbk::wave_sum(q);
       if (lane == 0) s_stat[0] = mean, s_stat[1] = 1.0f / sqrtf(q / (float)D + (i == 0 ? M.ln_eps[0] : M.ln_eps[1]));
     }
     __syncthreads();
     const float mean = s_stat[0], rstd = s_stat[1];
     const float* g = dnn_ptr(M.ln_g, i);
     const float* be = dnn_ptr(M.ln_b, i);
-    for (int k = tid; k < D; k += kTdThreads) y[k] = joint_act((y[k] - mean) * rstd * g[k] + be[k], M.act);
+    for (int k = tid; k < D; k += kTdThreads) y[k] = sbk::joint_act((y[k] - mean) * rstd * g[k] + be[k], M.act);
     __syncthreads();
     x = y, K = D;
   }
@@ -258,7 +248,7 @@ __global__ __launch_bounds__(kTdThreads) void transducer_greedy_kernel(TdArgs a)
     // 1. joint activations act(tn[t + f] + out_PN) of the block's frames
     for (int i = tid; i < fe * J; i += kTdThreads) {
       const int f = i / J, k = i - f * J;
-      s_z[i] = joint_act(tnb[(size_t)(t + f) * J + k] + s_pn[k], a.act);
+      s_z[i] = sbk::joint_act(tnb[(size_t)(t + f) * J + k] + s_pn[k], a.act);
     }
     __syncthreads();
     // 2. logits: one pass over the classifier's weights for the whole block
@@ -534,7 +524,7 @@ __global__ __launch_bounds__(kTdThreads) void transducer_beam_kernel(TbArgs a) {
       }
       // ---- the joint with tn[b, t], the classifier, log-softmax and top-k
       const float* tnf = tnb + (size_t)t * J;
-      for (int k = tid; k < J; k += kTdThreads) s_z[k] = joint_act(tnf[k] + s_pn[k], a.g.act);
+      for (int k = tid; k < J; k += kTdThreads) s_z[k] = sbk::joint_act(tnf[k] + s_pn[k], a.g.act);
       __syncthreads();
       gemv_rows<1, 8>(W.out, W.out_b, s_z, J, 1, J, V, s_logit, V);
       __syncthreads();
@@ -680,9 +670,7 @@ extern "C" int sbk_transducer_greedy_f32(const sbk_transducer_weights* W, const 
   SBK_REQUIRE((long long)T * (cfg->max_symbols_per_step + 1) < (1LL << 31), "transducer_greedy: T * (max_symbols + 1) too large");
   SBK_REQUIRE(cfg->frame_block >= 0 && cfg->frame_block <= kTdFrameMax, "transducer_greedy: frame_block %d outside [0, %d]",
               cfg->frame_block, kTdFrameMax);
-  SBK_REQUIRE(cfg->act == SBK_ACT_GELU || cfg->act == SBK_ACT_LEAKY_RELU || cfg->act == SBK_ACT_RELU ||
-                  cfg->act == SBK_ACT_TANH,
-              "transducer_greedy: joint activation %d is not supported", cfg->act);
+  SBK_REQUIRE(sbk::joint_act_known(cfg->act), "transducer_greedy: joint activation %d is not supported", cfg->act);
   int F = cfg->frame_block > 0 ? cfg->frame_block : kTdFrameDefault;
   F = min(F, T);
   while (F > 1 && td_lds_bytes(*W, F) > kTdDynLdsMax) --F;  // (the result does not depend on F)
@@ -761,9 +749,7 @@ int tb_check(const sbk_transducer_weights* W, const sbk_transducer_beam_config* 
   SBK_REQUIRE(cfg->max_expansions >= 1, "transducer_beam_search: max_expansions %d < 1", cfg->max_expansions);
   SBK_REQUIRE(cfg->max_tokens >= 1, "transducer_beam_search: max_tokens %d < 1", cfg->max_tokens);
   SBK_REQUIRE((long long)B * cfg->nbest * cfg->max_tokens < (1LL << 40), "transducer_beam_search: output too large");
-  SBK_REQUIRE(cfg->act == SBK_ACT_GELU || cfg->act == SBK_ACT_LEAKY_RELU || cfg->act == SBK_ACT_RELU ||
-                  cfg->act == SBK_ACT_TANH,
-              "transducer_beam_search: joint activation %d is not supported", cfg->act);
+  SBK_REQUIRE(sbk::joint_act_known(cfg->act), "transducer_beam_search: joint activation %d is not supported", cfg->act);
   return 0;
 }
 
@@ -786,8 +772,7 @@ int tb_lm_check(const sbk_transducer_weights* W, const sbk_rnnlm_weights* M, flo
   for (int i = 0; i < M->n_dnn; ++i)
     SBK_REQUIRE(M->dnn_w[i] && M->ln_g[i] && M->ln_b[i] && M->ln_eps[i] >= 0.0f,
                 "transducer_beam_search_lm: weights of the LM's DNN block %d missing (w, ln_g, ln_b; ln_eps >= 0)", i);
-  SBK_REQUIRE(M->act == SBK_ACT_GELU || M->act == SBK_ACT_LEAKY_RELU || M->act == SBK_ACT_RELU || M->act == SBK_ACT_TANH,
-              "transducer_beam_search_lm: the LM's activation %d is not supported", M->act);
+  SBK_REQUIRE(sbk::joint_act_known(M->act), "transducer_beam_search_lm: the LM's activation %d is not supported", M->act);
   return 0;
 }
 

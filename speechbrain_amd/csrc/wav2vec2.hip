@@ -30,11 +30,10 @@
 // instruction is permuted so that both are contiguous).  Taps whose 32 halo rows are all padding are skipped.  The two
 // parities are summed through LDS; bias, GELU and the residual (the halo's centre rows) are applied on the way out.
 // With (gamma, beta) the LayerNorm over d follows as a second launch, in place (a row needs all G groups).
+#include "act.h"
 #include "common.h"
 
 namespace {
-
-__device__ __forceinline__ float gelu_f(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
 
 constexpr int kMaxK = 16;                      // taps of layer 0
 constexpr int kPairs = kMaxK * (kMaxK + 1) / 2;
@@ -274,7 +273,7 @@ __global__ void __launch_bounds__(256) w2v_conv0_kernel(const float* __restrict_
 #pragma unroll
     for (int i = 0; i < CPT; ++i) {
       const int c = tid + 256 * i;
-      if (f < nf && c < C0) yb[(size_t)f * C0 + c] = gelu_f(fmaf(acc[i][f], gm[i], bt[i]));
+      if (f < nf && c < C0) yb[(size_t)f * C0 + c] = sbk::gelu_erf(fmaf(acc[i][f], gm[i], bt[i]));
     }
 }
 
@@ -396,7 +395,7 @@ __global__ void __launch_bounds__(256) w2v_posconv_kernel(const float* __restric
         for (int r = 0; r < 4; ++r) {
           const int t = t0 + rb + 16 * rt + 4 * ks + r;
           const float v = acc[rt][ct][r] + part[((rt * CT + ct) * 4 + r) * 128 + fh * 64 + lane] + bv;
-          if (t < T) yb[(size_t)t * d + c] = res[rt][ct][r] + gelu_f(v);
+          if (t < T) yb[(size_t)t * d + c] = res[rt][ct][r] + sbk::gelu_erf(v);
         }
       }
   }

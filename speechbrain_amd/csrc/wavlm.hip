@@ -22,12 +22,15 @@
 //   * the bias, after the MFMA score tile and before the mask and the maximum: one fused multiply-add per accumulator register.
 // LDS: 4 (2T + 30) bytes per workgroup -- 12 KB at T = 1499 (30 s of audio), 64 KiB at the bound T = 8177: two workgroups
 // per CU, as __launch_bounds__(256, 2) asks of the registers, at every accepted T, and no LDS opt-in.
+#include "act.h"
 #include "common.h"
 #include "internal.h"
+#include "kernel_util.h"
 
 namespace {
 
 using sbk::f32x16;
+using sbk::load_run;
 
 constexpr int kTabPad = 31;                          // zeros behind the table row: the masked keys of a ragged last tile
 constexpr int kMaxT = (65536 / 4 - kTabPad + 1) / 2;  // 2T - 1 + 31 floats <= 64 KiB: T <= 8177
@@ -44,18 +47,6 @@ struct WavlmArgs {
   int B, T, H;
   float scale;
 };
-
-template <int N>
-__device__ __forceinline__ void load_run(float (&dst)[N], const float* __restrict__ p) {
-  static_assert(N % 4 == 0, "runs of whole 16-byte pieces");
-#pragma unroll
-  for (int i = 0; i < N / 4; ++i) {
-    const float4 v = reinterpret_cast<const float4*>(p)[i];
-    dst[4 * i] = v.x; dst[4 * i + 1] = v.y; dst[4 * i + 2] = v.z; dst[4 * i + 3] = v.w;
-  }
-}
-
-__device__ __forceinline__ float sigmoid_(float v) { return 1.0f / (1.0f + expf(-v)); }
 
 template <int DH>
 __global__ void __launch_bounds__(256, 2) wavlm_flash_t_kernel(WavlmArgs a) {
@@ -91,7 +82,7 @@ __global__ void __launch_bounds__(256, 2) wavlm_flash_t_kernel(WavlmArgs a) {
       for (int c = 0; c < DH2; ++c) s = fmaf(w[c], xr[c], s);
       p[g] = s + sbk::shfl_xor(s, 32) + a.gate_b[g];
     }
-    const float ga = sigmoid_((p[0] + p[1]) + (p[2] + p[3])), gb = sigmoid_((p[4] + p[5]) + (p[6] + p[7]));
+    const float ga = sbk::sigmoid((p[0] + p[1]) + (p[2] + p[3])), gb = sbk::sigmoid((p[4] + p[5]) + (p[6] + p[7]));
     gate = ga * (gb * a.gate_const[h] - 1.0f) + 2.0f;
   }
 

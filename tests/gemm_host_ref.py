@@ -5,7 +5,9 @@ description of the arithmetic alone -- the operands and expectations of tests/te
   * the exact three-piece bf16 split of an fp32 number (hi = bf16(x), mid = bf16(x - hi), lo = x - hi - mid, round to
     nearest even) and the six-product contraction the x3 kernels run, with switches for planted mistakes;
   * the exact probes: operands whose product is known bit for bit whatever the summation order;
-  * the per-row / per-column error statistic.
+  * the per-row / per-column error statistic;
+  * the activation probes of tests/test_activation_edges.py: one-hot operands whose pre-activation values are chosen,
+    the error statistic in units of the fp32 spacing, and planted activation mistakes.
 
 Everything is plain torch on the CPU.  Denormal operands are out of scope: the lo piece of a number below about 2^-110
 is a bf16 denormal, and no probe here goes near it (|values| stay within 2^-30 .. 2^30).
@@ -16,7 +18,8 @@ import torch.nn.functional as F
 # the six partial products the x3 kernels form (relative size >= 2^-17); mid*lo, lo*mid and lo*lo are dropped by design
 SIX = (("hi", "hi"), ("hi", "mid"), ("mid", "hi"), ("hi", "lo"), ("lo", "hi"), ("mid", "mid"))
 
-ACTS = {"none": lambda v: v, "swish": F.silu, "gelu": F.gelu}
+ACTS = {"none": lambda v: v, "swish": F.silu, "gelu": F.gelu, "relu": F.relu, "leaky_relu": F.leaky_relu}
+ACT_CODES = {"none": 0, "swish": 1, "gelu": 2, "relu": 3, "leaky_relu": 4}  # SBK_ACT_* of include/sbk.h
 
 
 def _rn(x):  # fp32 -> nearest bf16 (ties to even), as fp32
@@ -246,3 +249,100 @@ def probe_epilogue(M, N, K, draw, seed, sig_bits=24):
     prod = a[:, k].double() * wj[None, :]
     _exact32(prod + bias[None, :])  # (the sum the epilogue forms first)
     return a, w, _exact32(bias), _exact32(res), _exact32(res + 0.5 * (prod + bias[None, :]))
+
+
+# ------------------------------------------------------------------ the activation probes (tests/test_activation_edges.py)
+# pre-activation values every probe holds: zero and its neighbourhood, the knee, the GELU / SWISH tails where 1 + erf
+# cancels (-5, -9, -12), and where expf(-v) underflows (+12, +80)
+ACT_TARGETS = (0.0, 2.0 ** -20, -(2.0 ** -20), 0.5, -0.5, 1.0, -1.0, 3.0, -3.0, -5.0, -9.0, -12.0, 12.0, 80.0)
+
+
+def _fits(x, sig_bits):
+    """x (fp64) is a number of ``sig_bits`` significand bits."""
+    m, _ = torch.frexp(x)
+    s = m * 2.0 ** sig_bits
+    return s == s.round()
+
+
+def probe_act(M, N, K, seed, sig_bits=24, by_row=False):
+    """probe_one_hot_w (draw 0) with chosen products: W one-hot +-2^e (e in -1..1; +-1 for sig_bits <= 4), a bias of +-0.5
+    in every fourth column, and a[i, k(j)] = (T - bias[j]) / w[j, k(j)] for a target T of ACT_TARGETS that moves with
+    (i, j), so that a . w^T + bias is T bit for bit -- the next target whose operand fits ``sig_bits`` where T's does not;
+    where columns share a k (N > K) the last column wins and the others hold another exact fp32 number.
+    ``by_row``: one |target| per row and the bias left out of the operand (rows that survive a per-row quantisation).
+    The residual is uniform in (-1, 1) with a third of its elements zero (there the result is the activation alone).
+    Returns (a, w, bias, residual, pre): ``pre`` fp64 [M, N], an fp32 number in every element."""
+    g = torch.Generator().manual_seed(seed)
+    a = full_mantissa(M, K, g, sig_bits, "pieces") if sig_bits > 4 else torch.zeros(M, K)
+    k = torch.arange(N) % K
+    sign = torch.randint(0, 2, (N,), generator=g).double() * 2 - 1
+    wval = sign * torch.exp2(torch.randint(-1, 2, (N,), generator=g).double() * (sig_bits > 4))
+    w = torch.zeros(N, K)
+    w[torch.arange(N), k] = wval.float()
+    bias = torch.zeros(N, dtype=torch.float64)
+    bias[3::8], bias[7::8] = 0.5, -0.5
+    T = torch.tensor(ACT_TARGETS, dtype=torch.float64)
+    i = torch.arange(M)
+    for j in range(N):
+        first = i % len(T) if by_row else (i * 5 + j * 3) % len(T)
+        val, done = torch.zeros(M, dtype=torch.float64), torch.zeros(M, dtype=torch.bool)
+        for s in range(len(T)):
+            cand = (T[(first + s) % len(T)] - (0.0 if by_row else bias[j])) / wval[j]
+            take = ~done & _fits(cand, sig_bits)
+            val, done = torch.where(take, cand, val), done | take
+        assert bool(done.all())
+        a[:, k[j]] = val.float()
+    r = torch.rand(M, N, generator=g) * 2 - 1
+    r[(i[:, None] + torch.arange(N)[None, :]) % 3 == 0] = 0.0
+    pre = a[:, k].double() * wval[None, :] + bias[None, :]
+    _exact32(pre)
+    return a, w, bias.float(), r, pre
+
+
+def probe_act_ln(M, N, K, seed):
+    """The LayerNorm-prologue entries: every row of A holds +-ACT_TARGETS and zeros (mean 0), rolled by 7 per row; W is
+    one-hot +-sqrt(var + eps), gamma = 1, beta = 0, so LayerNorm(A) . W^T + bias lies within a few fp32 spacings of the
+    targets and is known in fp64.  Returns (a, w, bias, residual, pre): pre fp64 [M, N]."""
+    g = torch.Generator().manual_seed(seed)
+    row = torch.zeros(K, dtype=torch.float64)
+    t = torch.tensor(ACT_TARGETS, dtype=torch.float64)
+    row[: 2 * len(t)] = torch.cat([t, -t])
+    a = torch.stack([row.roll(7 * i) for i in range(M)]).float()
+    k = torch.arange(N) % K
+    sign = torch.randint(0, 2, (N,), generator=g).double() * 2 - 1
+    w = torch.zeros(N, K)
+    w[torch.arange(N), k] = (sign * float((row.var(unbiased=False) + 1e-5).sqrt())).float()
+    bias = torch.zeros(N)
+    bias[3::8], bias[7::8] = 0.5, -0.5
+    r = torch.rand(M, N, generator=g) * 2 - 1
+    r[(torch.arange(M)[:, None] + torch.arange(N)[None, :]) % 3 == 0] = 0.0
+    ln = layernorm64(a, torch.ones(K), torch.zeros(K), 1e-5)
+    return a, w, bias, r, ln[:, k] * w[torch.arange(N), k].double()[None, :] + bias.double()[None, :]
+
+
+def spacing32(x):
+    """The distance between fp32 numbers at |x| (fp64 tensor); that of the smallest denormal at 0."""
+    e = torch.floor(torch.log2(x.abs().clamp_min(2.0 ** -126)))
+    return torch.exp2(e - 23)
+
+
+def act_stat(out, ref, pre, alpha, row_floor=False):
+    """max |out - ref| in units of the fp32 spacing at max(|alpha pre|, |ref|): the error against what the epilogue had in
+    its registers, so that the cancellation of 1 + erf in the negative tail counts as the absolute error it is.
+    ``row_floor`` (LayerNorm prologue: x - mean cancels at the size of the row's loudest element): the spacing at
+    alpha * max_j |pre_ij| where that is larger."""
+    size = torch.maximum((alpha * pre).abs(), ref.abs())
+    if row_floor:
+        size = torch.maximum(size, (alpha * pre).abs().amax(1, keepdim=True))
+    unit = spacing32(size)
+    return float(((out.double() - ref).abs() / unit).max())
+
+
+# planted activation mistakes: name -> (the activation they are planted into, fp64 function of (pre, alpha) -> alpha-scaled value)
+ACT_MISTAKES = {
+    "tanh-GELU for erf-GELU": ("gelu", lambda v, al: al * F.gelu(v, approximate="tanh")),
+    "slope 0.1 for 0.01": ("leaky_relu", lambda v, al: al * F.leaky_relu(v, 0.1)),
+    "RELU for LEAKY_RELU": ("leaky_relu", lambda v, al: al * F.relu(v)),
+    "SWISH after alpha": ("swish", lambda v, al: F.silu(al * v)),
+    "GELU after alpha": ("gelu", lambda v, al: F.gelu(al * v)),
+}

@@ -90,50 +90,50 @@ class _force_f32x3:
 
 # ------------------------------------------------------------------ launch forms (through the binding): parts A and B
 def _f32(**kn):
-    def run(nat, dev, a, w, b=None, r=None, alpha=1.0):
+    def run(nat, dev, a, w, b=None, r=None, alpha=1.0, act=0):
         with nat.knobs(**kn):
-            return nat.gemm_nt(a.to(dev), w.to(dev), _d(b, dev), _d(r, dev), alpha=alpha).cpu()
+            return nat.gemm_nt(a.to(dev), w.to(dev), _d(b, dev), _d(r, dev), act=act, alpha=alpha).cpu()
     return run
 
 
 def _splitk(slices, **kn):
-    def run(nat, dev, a, w, b=None, r=None, alpha=1.0):
+    def run(nat, dev, a, w, b=None, r=None, alpha=1.0, act=0):
         with nat.knobs(**kn):
-            return nat.gemm_nt_splitk(a.to(dev), w.to(dev), _d(b, dev), _d(r, dev), alpha=alpha, slices=slices).cpu()
+            return nat.gemm_nt_splitk(a.to(dev), w.to(dev), _d(b, dev), _d(r, dev), act=act, alpha=alpha, slices=slices).cpu()
     return run
 
 
-def _f32x3(nat, dev, a, w, b=None, r=None, alpha=1.0):
+def _f32x3(nat, dev, a, w, b=None, r=None, alpha=1.0, act=0):
     with _force_f32x3(nat):
         assert nat.f32x3_ok(a.shape[0], a.shape[1], w) and not nat.x3p_ok(a.shape[0], a.shape[1], w)
-        return nat.gemm_nt(a.to(dev), w.to(dev), _d(b, dev), _d(r, dev), alpha=alpha).cpu()
+        return nat.gemm_nt(a.to(dev), w.to(dev), _d(b, dev), _d(r, dev), act=act, alpha=alpha).cpu()
 
 
-def _x3p(nat, dev, a, w, b=None, r=None, alpha=1.0):
-    return nat.gemm_nt_x3p(nat.split_x3p(a.to(dev)), w.to(dev), _d(b, dev), _d(r, dev), alpha=alpha).cpu()
+def _x3p(nat, dev, a, w, b=None, r=None, alpha=1.0, act=0):
+    return nat.gemm_nt_x3p(nat.split_x3p(a.to(dev)), w.to(dev), _d(b, dev), _d(r, dev), act=act, alpha=alpha).cpu()
 
 
-def _x3p_panel(nat, dev, a, w, b=None, r=None, alpha=1.0):
-    pc = nat.gemm_nt_x3p(nat.split_x3p(a.to(dev)), w.to(dev), _d(b, dev), _d(r, dev), alpha=alpha, panel_out=True, fp32_out=False)
+def _x3p_panel(nat, dev, a, w, b=None, r=None, alpha=1.0, act=0):
+    pc = nat.gemm_nt_x3p(nat.split_x3p(a.to(dev)), w.to(dev), _d(b, dev), _d(r, dev), act=act, alpha=alpha, panel_out=True, fp32_out=False)
     return _unpanel(pc.data, a.shape[0], w.shape[0])
 
 
 def _x3r(**kn):
-    def run(nat, dev, a, w, b=None, r=None, alpha=1.0):
+    def run(nat, dev, a, w, b=None, r=None, alpha=1.0, act=0):
         with nat.knobs(**kn):
-            return nat.gemm_nt_x3r(a.to(dev), w.to(dev), _d(b, dev), _d(r, dev), alpha=alpha).cpu()
+            return nat.gemm_nt_x3r(a.to(dev), w.to(dev), _d(b, dev), _d(r, dev), act=act, alpha=alpha).cpu()
     return run
 
 
 def _lp(kind):
-    def run(nat, dev, a, w, b=None, r=None, alpha=1.0):
-        return nat.gemm_nt_bf16(a.to(dev), w.to(dev), _d(b, dev), _d(r, dev), alpha=alpha, kind=kind).cpu()
+    def run(nat, dev, a, w, b=None, r=None, alpha=1.0, act=0):
+        return nat.gemm_nt_bf16(a.to(dev), w.to(dev), _d(b, dev), _d(r, dev), act=act, alpha=alpha, kind=kind).cpu()
     return run
 
 
-def _bf16a(nat, dev, a, w, b=None, r=None, alpha=1.0):
+def _bf16a(nat, dev, a, w, b=None, r=None, alpha=1.0, act=0):
     assert torch.equal(a.bfloat16().float(), a)
-    return nat.gemm_nt_bf16a(a.bfloat16().to(dev), w.to(dev), _d(b, dev), _d(r, dev), alpha=alpha).cpu()
+    return nat.gemm_nt_bf16a(a.bfloat16().to(dev), w.to(dev), _d(b, dev), _d(r, dev), act=act, alpha=alpha).cpu()
 
 
 # The shapes: M in 1, 63, 65, 129, 257 and N in 4, 68, 132, 260 (the smallest with an interior and a ragged edge of the
