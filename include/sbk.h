@@ -979,6 +979,89 @@ int sbk_decoder_prefix_f32(const sbk_decoder_weights* W, const int32_t* tokens, 
                            const int32_t* enc_len, void* workspace, size_t workspace_bytes, float* pred, int n, int T,
                            int L, sbk_stream_t stream);
 
+/* ---- GRU attention decoder of the CRDNN seq2seq recipes (csrc/attn_rnn.hip; additive entries, ABI 11 unchanged) ----------
+ * One decode step of LocationAwareAttention.forward (nnet/attention.py:203-251) for n hypothesis rows; C == 0 selects
+ * ContentBasedAttention.forward (attention.py:80-117), the same kernels without the location term.
+ *   enc [B,T,E] encoder states; enc_h [B,T,A] = mlp_enc(enc) (one sbk_gemm_nt_f32 per search); enc_len [B] int32 absolute frame
+ *   counts; row_utt [n] int32: the utterance of each row (several rows may name one utterance, an utterance may have no
+ *   row), NULL = identity with n == B; dec_h [n,A] = mlp_dec(h) with its bias; prev_attn [n,T] the previous step's attention
+ *   (C > 0 only); conv_w [C,2k+1] = conv_loc.weight; loc_w [A,C], loc_b [A] = mlp_loc; attn_v [A] = mlp_attn.weight.
+ *     loc[c,t] = sum_j conv_w[c,j] * prev_attn[t+j-k], zeros outside [0,T)   (a cross-correlation, torch's Conv1d)
+ *     e[t]     = attn_v . tanh(enc_h[u,t,:] + dec_h[r,:] + loc_w . loc[:,t] + loc_b),  -inf for t >= enc_len[u]
+ *     attn     = softmax(scaling * e) over t  -> attn [n,T] (exactly 0 past enc_len; the caller swaps it with prev_attn)
+ *     ctx      = sum_t attn[t] * enc[u,t,:]  -> ctx [n,E]   (mlp_out is a contraction outside)
+ *   workspace: sbk_attn_rnn_attend_workspace_bytes(n, T) bytes (the energies [n,T]; nothing of size n*T*A is written).
+ * Fixed summation orders: two runs give the same bits.  The kernels clamp enc_len to [1,T] and row_utt to [0,B) where they
+ * index; this entry also checks both on the device (one 4-byte read-back per call) and refuses values outside.
+ * Limits (SBK_EINVAL, each named): 1 <= A, E <= 2048, 1 <= T <= 4096, 0 <= C <= 32, 0 <= k <= 128, 1 <= n <= 65535,
+ * 1 <= enc_len <= T, 0 <= row_utt < B; attn must not be prev_attn.
+ * sbk_attn_rnn_attn_init_f32: the first prev_attn (attention.py:226): 1 / enc_len[u] on the valid frames, 0 behind them
+ * (enc_len and row_utt clamped as above). */
+size_t sbk_attn_rnn_attend_workspace_bytes(int n, int T);
+int sbk_attn_rnn_attend_f32(const float* enc, const float* enc_h, const int32_t* enc_len, const int32_t* row_utt,
+                            const float* dec_h, const float* prev_attn, const float* conv_w, const float* loc_w,
+                            const float* loc_b, const float* attn_v, float scaling, float* attn, float* ctx, void* workspace,
+                            size_t workspace_bytes, int n, int B, int T, int A, int E, int C, int k, sbk_stream_t stream);
+int sbk_attn_rnn_attn_init_f32(const int32_t* enc_len, const int32_t* row_utt, float* attn, int n, int B, int T,
+                               sbk_stream_t stream);
+/* torch.nn.GRUCell's update (the cells of GRUCell, nnet/RNN.py:576-648): gi, gh [n,3H] = x . W_ih^T and h . W_hh^T without bias
+ * (e.g. from sbk_gemm_nt_f32), gate order r, z, n; b_ih, b_hh [3H] (both or neither);
+ *   r = sigmoid(gi_r + b_ir + gh_r + b_hr), z likewise, n = tanh(gi_n + b_in + r * (gh_n + b_hn)), h' = (1 - z) * n + z * h.
+ * h_prev [n,H] (NULL = zeros); h_out [n,H] may be h_prev.  1 <= H <= 2048. */
+int sbk_gru_cell_f32(const float* gi, const float* gh, const float* b_ih, const float* b_hh, const float* h_prev, float* h_out,
+                     int n, int H, sbk_stream_t stream);
+
+/* AttentionalRNNDecoder (nnet/RNN.py:832-1013, rnn_type "gru", attn_type "location" or "content") with the embedding and the
+ * output layer of S2SRNNGreedySearcher (decoders/seq2seq.py:638-708).  fp32 device memory, row-major in torch's layouts;
+ * H = hidden, A = attn_dim (also the width of the context c), E = enc_dim, in = the width of a step's input.
+ *   emb [n_emb,in]; w_ih[0] [3H,in+A], w_ih[l] [3H,H] above; w_hh[l] [3H,H]; b_ih[l], b_hh[l] [3H] (both or neither);
+ *   enc_w [A,E], enc_b = attn.mlp_enc; dec_w [A,H], dec_b = attn.mlp_dec; attn_v [A] = attn.mlp_attn.weight;
+ *   conv_w [C,2k+1], loc_w [A,C], loc_b [A] = attn.conv_loc / attn.mlp_loc (channels = 0: content attention, all NULL);
+ *   out_w [A,E], out_b = attn.mlp_out; proj_w [H,A+H], proj_b = proj; fc_w [V,H], fc_b = the output Linear.
+ *   Biases may be NULL; emb, fc_w, fc_b, vocab and n_emb are read by the search only. */
+#define SBK_ATTN_RNN_MAX_LAYERS 4
+typedef struct sbk_attn_rnn_weights {
+  const float* emb;
+  const float* w_ih[SBK_ATTN_RNN_MAX_LAYERS];
+  const float* w_hh[SBK_ATTN_RNN_MAX_LAYERS];
+  const float* b_ih[SBK_ATTN_RNN_MAX_LAYERS];
+  const float* b_hh[SBK_ATTN_RNN_MAX_LAYERS];
+  const float* enc_w;
+  const float* enc_b;
+  const float* dec_w;
+  const float* dec_b;
+  const float* attn_v;
+  const float* conv_w;
+  const float* loc_w;
+  const float* loc_b;
+  const float* out_w;
+  const float* out_b;
+  const float* proj_w;
+  const float* proj_b;
+  const float* fc_w;
+  const float* fc_b;
+  int32_t n_layers, hidden, in_dim, attn_dim, enc_dim, channels, kernel, vocab, n_emb;
+  float scaling;
+} sbk_attn_rnn_weights;
+/* S2SRNNGreedySearcher.forward (seq2seq.py:176-327, temperature 0) in one call.  Per step: embedding of the previous token
+ * (bos first) || c -> the GRU cells -> attend -> mlp_out -> proj([c || cell_out]) -> fc -> arg-max (torch.argmax: the first of
+ * equal maxima, NaN above everything) with its log_softmax value; every contraction through the routing of sbk_gemm_nt_f32.
+ * A row that has emitted eos, at this step or before, records (eos, 0) and feeds eos on.  max_steps = the length of the
+ * reference's range(int(T*min_decode_ratio), int(T*max_decode_ratio)) (>= 1); the count of ended rows is polled from the
+ * host every check_every steps (<= 0: 8) and the search stops once every row has ended.
+ *   out_tokens, out_scores [B,max_steps] (steps not run read (eos, 0)); *steps_run = steps issued (host memory).
+ *   workspace: sbk_attn_rnn_greedy_workspace_bytes(W, B, T) bytes, 16-byte aligned.  enc_len outside [1,T] is refused. */
+size_t sbk_attn_rnn_greedy_workspace_bytes(const sbk_attn_rnn_weights* W, int B, int T);
+int sbk_attn_rnn_greedy_f32(const sbk_attn_rnn_weights* W, const float* enc, const int32_t* enc_len, void* workspace,
+                            size_t workspace_bytes, int32_t* out_tokens, float* out_scores, int32_t* steps_run, int B, int T,
+                            int max_steps, int bos, int eos, int check_every, sbk_stream_t stream);
+/* AttentionalRNNDecoder.forward (nnet/RNN.py:969-1013), teacher forced: inp [B,L,in] the embedded tokens ->
+ * outputs [B,L,H], attn [B,L,T], and the state after the last step: hs [n_layers,B,H] and c [B,A] (either may be NULL). */
+size_t sbk_attn_rnn_decode_workspace_bytes(const sbk_attn_rnn_weights* W, int B, int T);
+int sbk_attn_rnn_decode_f32(const sbk_attn_rnn_weights* W, const float* inp, const float* enc, const int32_t* enc_len,
+                            void* workspace, size_t workspace_bytes, float* outputs, float* attn, float* hs, float* c, int B,
+                            int T, int L, sbk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

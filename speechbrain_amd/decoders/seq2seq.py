@@ -1,4 +1,5 @@
-"""speechbrain.decoders.seq2seq mirror: S2STransformerBeamSearcher / S2STransformerGreedySearcher.
+"""speechbrain.decoders.seq2seq mirror: S2STransformerBeamSearcher / S2STransformerGreedySearcher, the Whisper searchers and
+S2SRNNGreedySearcher (GRU attention decoder, csrc/attn_rnn.hip).
 
 Constructor signatures, ``forward(enc_states, wav_len)`` and return tuples follow the reference
 (decoders/seq2seq.py:711-1934).  One forward = one C-ABI call that runs the whole search on the
@@ -54,19 +55,70 @@ class S2STransformerGreedySearcher(S2SBaseSearcher):
         mn, mx = self._steps(T)
         tok, sc, steps = native.greedy_search(self._handle(), enc_states.contiguous(), enc_lens, mn, mx, self.bos_index,
                                               self.eos_index, self.check_every)
-        tok, sc = tok[:, :steps].cpu(), sc[:, :steps].cpu()
-        # the reference stops at the first step after which every utterance has ended (:277-278)
-        is_eos = tok == self.eos_index
-        first = torch.where(is_eos.any(1), is_eos.float().argmax(1), torch.full((B,), steps))
-        L = steps if (first == steps).any() else int(first.max()) + 1
-        L = max(L, 1) if steps > 0 else 0
-        tok, sc = tok[:, :L], sc[:, :L]
-        hyps, rel = [], []
-        for b in range(B):
-            n = min(int(first[b]), L)
-            rel.append(n / L if L else 0.0)
-            hyps.append(tok[b, :n].tolist())
-        return hyps, torch.tensor(rel).unsqueeze(1), sc.unsqueeze(1), None
+        return _greedy_result(tok, sc, steps, self.eos_index)
+
+
+def _greedy_result(tok, sc, steps, eos_index):
+    """What S2SGreedySearcher.forward returns (seq2seq.py:259-276) from the device's eos-latched tokens / scores [B, >= steps]
+    of which ``steps`` were run: (hyps, top_lengths [B,1], top_scores [B,1,L], None)."""
+    B = tok.shape[0]
+    tok, sc = tok[:, :steps].cpu(), sc[:, :steps].cpu()
+    # the reference stops at the first step after which every utterance has ended (:277-278)
+    is_eos = tok == eos_index
+    first = torch.where(is_eos.any(1), is_eos.float().argmax(1), torch.full((B,), steps))
+    L = steps if (first == steps).any() else int(first.max()) + 1
+    L = max(L, 1) if steps > 0 else 0
+    tok, sc = tok[:, :L], sc[:, :L]
+    hyps, rel = [], []
+    for b in range(B):
+        n = min(int(first[b]), L)
+        rel.append(n / L if L else 0.0)
+        hyps.append(tok[b, :n].tolist())
+    return hyps, torch.tensor(rel).unsqueeze(1), sc.unsqueeze(1), None
+
+
+class S2SRNNGreedySearcher(S2SBaseSearcher):
+    """seq2seq.py:638-708 on top of S2SGreedySearcher.forward (:176-327), temperature 0 (arg-max): greedy decoding with an
+    AttentionalRNNDecoder (GRU cells), the decoder of the CRDNN seq2seq recipes.  One forward = one sbk_attn_rnn_greedy_f32 call
+    (csrc/attn_rnn.hip).  Returns (hyps, top_lengths [B,1], top_scores [B,1,L], None), as S2STransformerGreedySearcher."""
+
+    def __init__(self, embedding, decoder, linear, temperature=0.0, **kwargs):
+        super().__init__(**kwargs)
+        if temperature != 0.0:
+            raise NotImplementedError("S2SRNNGreedySearcher: sampling (temperature != 0) is not on the ASR inference path")
+        self.emb, self.dec, self.fc, self.temperature = embedding, decoder, linear, temperature
+        self.check_every = 8
+        self._prepared = native.Derived()
+
+    def _tables(self):
+        """(embedding table, (output weight, output bias)) of a speechbrain or a torch Embedding / Linear."""
+        emb = self.emb.Embedding.weight if hasattr(self.emb, "Embedding") else self.emb.weight
+        lin = self.fc.w if hasattr(self.fc, "w") else self.fc
+        return emb, (lin.weight, lin.bias)
+
+    @torch.no_grad()
+    def forward(self, enc_states, wav_len, attention_mask=None):
+        if attention_mask is not None:
+            raise NotImplementedError("attention_mask is a Whisper/LLM decoder feature")
+        enc = enc_states.detach().float().contiguous()
+        T = enc.shape[1]
+        enc_lens = torch.round(T * wav_len).int().to(enc.device).contiguous()
+        mn, mx = self._steps(T)
+        if mx - mn < 1:
+            raise ValueError(f"S2SRNNGreedySearcher: no decoding steps (range({mn}, {mx}) from {T} encoder frames, "
+                             f"min_decode_ratio {self.min_decode_ratio}, max_decode_ratio {self.max_decode_ratio})")
+        emb, fc = self._tables()
+        with native.precision_scope("fp32"):  # an fp32 model, like CRDNN
+            prep = self.dec.prepared(enc.device, emb=emb, fc=fc, derived=self._prepared)
+            tok, sc, steps = native.attn_rnn_greedy(prep, enc, enc_lens, mx - mn, self.bos_index, self.eos_index,
+                                                    self.check_every)
+        return _greedy_result(tok, sc, steps, self.eos_index)
+
+
+class S2SRNNBeamSearcher(S2SBaseSearcher):
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError("S2SRNNBeamSearcher is not implemented: decode an AttentionalRNNDecoder with "
+                                  "S2SRNNGreedySearcher (same embedding, decoder and linear arguments)")
 
 
 class _WhisperPrompting:

@@ -118,9 +118,29 @@ class RNNLMWeights(ctypes.Structure):  # sbk_rnnlm_weights
         (n, c_int32) for n in ("n_layers", "hidden", "n_dnn", "dnn", "vocab", "n_emb", "act")]
 
 
+ATTN_RNN_MAX_LAYERS = 4  # SBK_ATTN_RNN_MAX_LAYERS
+
+
+class AttnRNNWeights(ctypes.Structure):  # sbk_attn_rnn_weights
+    _fields_ = [("emb", c_void_p)] + [(n, c_void_p * ATTN_RNN_MAX_LAYERS) for n in ("w_ih", "w_hh", "b_ih", "b_hh")] + [
+        (n, c_void_p) for n in ("enc_w", "enc_b", "dec_w", "dec_b", "attn_v", "conv_w", "loc_w", "loc_b", "out_w", "out_b",
+                                "proj_w", "proj_b", "fc_w", "fc_b")] + [
+        (n, c_int32) for n in ("n_layers", "hidden", "in_dim", "attn_dim", "enc_dim", "channels", "kernel", "vocab", "n_emb")] + [
+        ("scaling", c_float)]
+
+
 def _declare(lib):
     p, i, f = c_void_p, c_int, c_float
     sig = {
+        "sbk_attn_rnn_attend_workspace_bytes": ([i, i], ctypes.c_size_t),
+        "sbk_attn_rnn_attend_f32": ([p] * 10 + [f, p, p, p, ctypes.c_size_t] + [i] * 7 + [p], c_int),
+        "sbk_attn_rnn_attn_init_f32": ([p, p, p, i, i, i, p], c_int),
+        "sbk_gru_cell_f32": ([p] * 6 + [i, i, p], c_int),
+        "sbk_attn_rnn_greedy_workspace_bytes": ([POINTER(AttnRNNWeights), i, i], ctypes.c_size_t),
+        "sbk_attn_rnn_greedy_f32": ([POINTER(AttnRNNWeights), p, p, p, ctypes.c_size_t, p, p, POINTER(c_int32)] + [i] * 6 + [p],
+                                    c_int),
+        "sbk_attn_rnn_decode_workspace_bytes": ([POINTER(AttnRNNWeights), i, i], ctypes.c_size_t),
+        "sbk_attn_rnn_decode_f32": ([POINTER(AttnRNNWeights), p, p, p, p, ctypes.c_size_t, p, p, p, p, i, i, i, p], c_int),
         "sbk_abi_version": ([], c_int),
         "sbk_last_error": ([], c_char_p),
         "sbk_stream_workspace_bytes": ([], ctypes.c_size_t),
@@ -1503,6 +1523,147 @@ def rnn_layer(xp, w_hh, b_ih=None, b_hh=None, h0=None, c0=None, route=0):
     _chk(lib.sbk_rnn_layer_f32(_p(xp), _p(w_hh), _p(b_ih), _p(b_hh), _p(h0), _p(c0), _p(out), _p(hn), _p(cn), B, T, H, D,
                                RNN_LSTM, int(route), _stream(xp)), "sbk_rnn_layer_f32")
     return out, hn, cn
+
+
+# ------------------------------------------------------------------ GRU attention decoder (csrc/attn_rnn.hip)
+def attn_rnn_attend(enc, enc_h, enc_len, dec_h, attn_v, prev_attn=None, conv_w=None, loc_w=None, loc_b=None, scaling=1.0,
+                    row_utt=None):
+    """One attention step for n rows (sbk_attn_rnn_attend_f32): enc [B,T,E], enc_h [B,T,A], enc_len [B] int32, dec_h [n,A],
+    attn_v [A]; location-aware with prev_attn [n,T], conv_w [C,2k+1], loc_w [A,C], loc_b [A], content-based without them;
+    row_utt [n] int32 or None (identity, n == B) -> (attn [n,T], ctx [n,E])."""
+    lib = load()
+    B, T, E = enc.shape
+    n, A = dec_h.shape
+    C, k = (conv_w.shape[0], (conv_w.shape[-1] - 1) // 2) if conv_w is not None else (0, 0)
+    want = [("enc_h", enc_h, (B, T, A)), ("enc_len", enc_len, (B,)), ("attn_v", attn_v, (A,))]
+    if C:
+        conv_w = conv_w.reshape(C, 2 * k + 1)
+        want += [("prev_attn", prev_attn, (n, T)), ("loc_w", loc_w, (A, C)), ("loc_b", loc_b, (A,))]
+    if row_utt is not None:
+        want.append(("row_utt", row_utt, (n,)))
+    for name, t, shape in want:
+        if t is None or tuple(t.shape) != shape:
+            raise SbkError(f"attn_rnn_attend: {name} {None if t is None else tuple(t.shape)} is not {shape}")
+    _dev_ok(enc, enc_h, enc_len, dec_h, attn_v, prev_attn, conv_w, loc_w, loc_b, row_utt)
+    for t in (enc, enc_h, dec_h, attn_v, prev_attn, conv_w, loc_w, loc_b):
+        if t is not None:
+            _f32(t)
+    for t in (enc_len, row_utt):
+        if t is not None and t.dtype != torch.int32:
+            raise SbkError(f"attn_rnn_attend: expected int32 lengths / rows, got {t.dtype}")
+    attn = torch.empty(n, T, dtype=torch.float32, device=enc.device)
+    ctx = torch.empty(n, E, dtype=torch.float32, device=enc.device)
+    nbytes = lib.sbk_attn_rnn_attend_workspace_bytes(n, T)
+    ws = _Workspace(nbytes, enc.device)
+    _chk(lib.sbk_attn_rnn_attend_f32(_p(enc), _p(enc_h), _p(enc_len), _p(row_utt), _p(dec_h), _p(prev_attn), _p(conv_w), _p(loc_w),
+                                     _p(loc_b), _p(attn_v), float(scaling), _p(attn), _p(ctx), ws.ptr, nbytes, n, B, T, A, E, C, k,
+                                     _stream(enc)), "sbk_attn_rnn_attend_f32")
+    return attn, ctx
+
+
+def attn_rnn_attn_init(enc_len, T, row_utt=None):
+    """The first prev_attn (sbk_attn_rnn_attn_init_f32): 1 / enc_len[u] on the valid frames of each row, 0 behind -> [n,T]."""
+    lib = load()
+    _dev_ok(enc_len, row_utt)
+    B = enc_len.shape[0]
+    n = row_utt.shape[0] if row_utt is not None else B
+    attn = torch.empty(n, int(T), dtype=torch.float32, device=enc_len.device)
+    _chk(lib.sbk_attn_rnn_attn_init_f32(_p(enc_len), _p(row_utt), _p(attn), n, B, int(T), _stream(attn)),
+         "sbk_attn_rnn_attn_init_f32")
+    return attn
+
+
+def gru_cell(gi, gh, b_ih=None, b_hh=None, h_prev=None, out=None):
+    """torch.nn.GRUCell's update (sbk_gru_cell_f32): gi, gh [n,3H] without bias, b_ih / b_hh [3H] (both or neither), h_prev [n,H]
+    or None (zeros) -> h' [n,H]; ``out`` may be ``h_prev``."""
+    lib = load()
+    n, G = gi.shape
+    H = G // 3
+    if G != 3 * H or tuple(gh.shape) != (n, G):
+        raise SbkError(f"gru_cell: gi {tuple(gi.shape)} and gh {tuple(gh.shape)} are not both [n,3H]")
+    for name, t, shape in (("b_ih", b_ih, (G,)), ("b_hh", b_hh, (G,)), ("h_prev", h_prev, (n, H)), ("out", out, (n, H))):
+        if t is not None and tuple(t.shape) != shape:
+            raise SbkError(f"gru_cell: {name} {tuple(t.shape)} is not {shape}")
+    _dev_ok(gi, gh, b_ih, b_hh, h_prev, out)
+    for t in (gi, gh, b_ih, b_hh, h_prev, out):
+        if t is not None:
+            _f32(t)
+    if out is None:
+        out = torch.empty(n, H, dtype=torch.float32, device=gi.device)
+    _chk(lib.sbk_gru_cell_f32(_p(gi), _p(gh), _p(b_ih), _p(b_hh), _p(h_prev), _p(out), n, H, _stream(gi)), "sbk_gru_cell_f32")
+    return out
+
+
+class AttnRNNPrepared:
+    """An AttentionalRNNDecoder (GRU cells, location-aware or content-based attention), and for the search its embedding and
+    output layer, in the layouts of sbk_attn_rnn_weights (include/sbk.h).  The tensors are kept alive here for as long as the
+    struct points at them."""
+
+    def __init__(self, gru_layers, attn, proj_w, proj_b, scaling, emb=None, fc_w=None, fc_b=None):
+        """gru_layers: [(w_ih, w_hh, b_ih or None, b_hh or None)] * L; attn: a dict with enc_w, enc_b, dec_w, dec_b, attn_v,
+        out_w, out_b and -- location-aware -- conv_w [C,2k+1], loc_w, loc_b (all fp32 on one device)."""
+        if not 1 <= len(gru_layers) <= ATTN_RNN_MAX_LAYERS:
+            raise SbkError(f"AttentionalRNNDecoder: {len(gru_layers)} GRU layers (1..{ATTN_RNN_MAX_LAYERS} supported)")
+        self.W, self._keep = W, keep = AttnRNNWeights(), []
+        ptr = _keeper(keep, strict=False)
+        for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(gru_layers):
+            W.w_ih[l], W.w_hh[l], W.b_ih[l], W.b_hh[l] = ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh)
+        for name in ("enc_w", "enc_b", "dec_w", "dec_b", "attn_v", "conv_w", "loc_w", "loc_b", "out_w", "out_b"):
+            setattr(W, name, ptr(attn.get(name)))
+        W.proj_w, W.proj_b, W.emb, W.fc_w, W.fc_b = ptr(proj_w), ptr(proj_b), ptr(emb), ptr(fc_w), ptr(fc_b)
+        conv_w = attn.get("conv_w")
+        W.n_layers, W.hidden = len(gru_layers), gru_layers[0][1].shape[1]
+        W.attn_dim, W.enc_dim = attn["enc_w"].shape
+        W.in_dim = gru_layers[0][0].shape[1] - W.attn_dim
+        if tuple(attn["out_w"].shape) != (W.attn_dim, W.enc_dim) or tuple(proj_w.shape) != (W.hidden, W.attn_dim + W.hidden):
+            raise SbkError("AttentionalRNNDecoder: the context's width (mlp_out) must equal attn_dim, and proj takes [c || cell_out]")
+        W.channels, W.kernel = (conv_w.shape[0], (conv_w.shape[-1] - 1) // 2) if conv_w is not None else (0, 0)
+        W.vocab, W.n_emb = (fc_w.shape[0] if fc_w is not None else 0), (emb.shape[0] if emb is not None else 0)
+        if emb is not None and emb.shape[1] != W.in_dim:
+            raise SbkError(f"S2SRNNGreedySearcher: embedding width {emb.shape[1]} is not the decoder's input size {W.in_dim}")
+        W.scaling = float(scaling)
+        self.device = keep[0].device
+
+
+def attn_rnn_greedy(prep: AttnRNNPrepared, enc, enc_len, max_steps, bos, eos, check_every=8):
+    """sbk_attn_rnn_greedy_f32: enc [B,T,E], enc_len [B] int32 -> (tokens [B,max_steps] int32 (eos-latched), scores
+    [B,max_steps], steps_run)."""
+    lib = load()
+    _dev_ok(enc, enc_len)
+    _f32(enc)
+    B, T, _ = enc.shape
+    L = int(max_steps)
+    out_tok = torch.empty(B, L, dtype=torch.int32, device=enc.device)
+    out_sc = torch.empty(B, L, dtype=torch.float32, device=enc.device)
+    nbytes = lib.sbk_attn_rnn_greedy_workspace_bytes(ctypes.byref(prep.W), B, T)
+    ws = _Workspace(nbytes, enc.device)
+    steps = c_int32(0)
+    _chk(lib.sbk_attn_rnn_greedy_f32(ctypes.byref(prep.W), _p(enc), _p(enc_len), ws.ptr, nbytes, _p(out_tok), _p(out_sc),
+                                     ctypes.byref(steps), B, T, L, int(bos), int(eos), int(check_every), _stream(enc)),
+         "sbk_attn_rnn_greedy_f32")
+    return out_tok, out_sc, steps.value
+
+
+def attn_rnn_decode(prep: AttnRNNPrepared, inp, enc, enc_len):
+    """sbk_attn_rnn_decode_f32 (teacher forced): inp [B,L,in], enc [B,T,E], enc_len [B] int32 -> (outputs [B,L,H],
+    attn [B,L,T], hs [n_layers,B,H], c [B,A])."""
+    lib = load()
+    _dev_ok(inp, enc, enc_len)
+    _f32(inp), _f32(enc)
+    B, T, _ = enc.shape
+    L, W = inp.shape[1], prep.W
+    if inp.shape[0] != B or inp.shape[2] != W.in_dim:
+        raise SbkError(f"attn_rnn_decode: inp {tuple(inp.shape)} is not [{B},L,{W.in_dim}]")
+    dev = enc.device
+    outputs = torch.empty(B, L, W.hidden, dtype=torch.float32, device=dev)
+    attn = torch.empty(B, L, T, dtype=torch.float32, device=dev)
+    hs = torch.empty(W.n_layers, B, W.hidden, dtype=torch.float32, device=dev)
+    c = torch.empty(B, W.attn_dim, dtype=torch.float32, device=dev)
+    nbytes = lib.sbk_attn_rnn_decode_workspace_bytes(ctypes.byref(W), B, T)
+    ws = _Workspace(nbytes, dev)
+    _chk(lib.sbk_attn_rnn_decode_f32(ctypes.byref(W), _p(inp), _p(enc), _p(enc_len), ws.ptr, nbytes, _p(outputs), _p(attn), _p(hs),
+                                     _p(c), B, T, L, _stream(enc)), "sbk_attn_rnn_decode_f32")
+    return outputs, attn, hs, c
 
 
 # ------------------------------------------------------------------ CRDNN convolution blocks (csrc/crdnn.hip)
