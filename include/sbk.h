@@ -608,6 +608,29 @@ int sbk_ctc_beam_search_lm_f32(const float* x, const float* rel_len, const int32
                                size_t workspace_bytes, int32_t* out_tokens, float* out_score, float* out_lm_score,
                                int32_t* out_count, int B, int T, int V, sbk_stream_t stream);
 
+/* CTCPrefixBeamSearcher without a language model (decoders/ctc.py:382-509,1488-1905,868-934; csrc/ctc_prefix_search.hip;
+ * additive entries, ABI 11 unchanged): beams are prefix texts with blank / non-blank probabilities, merged by text.  One
+ * workgroup per utterance, every frame in one launch, the beam list in LDS; fp32 scores; bit-identical from run to run and
+ * stream to stream (every logaddexp into one beam is applied in a fixed order: tokens ascending, then the beams in list order).
+ *   x, rel_len, cfg, out_tokens, out_score, out_count as for sbk_ctc_beam_search_f32, with these differences:
+ *   token_table column 7 is 1 for a token that the reference looks up under a text no beam can have and that therefore
+ *     always starts a beam of its own (a SentencePiece piece that starts with the boundary mark), else 0; a token's text
+ *     holds no white space, and only the blank's may be empty;
+ *   out_tokens [B,topk,T]: the token that CREATED the hypothesis' prefix at each frame (-1 where the prefix was carried,
+ *     skipped or padded) -- the host rebuilds `text` and `text_frames` from it;
+ *   out_count[b] = -1 reports a length int(fp32(T * rel_len[b])) that is no number, negative or above T;
+ *   cfg->beam_prune_logp <= 0.
+ *   workspace: sbk_ctc_prefix_beam_search_workspace_bytes(B, T, V, Vl, beam_size, topk) bytes, 16-byte aligned: records
+ *     [B][T][beam_size] int32, expanded-frame flags [B][T] int32, counters [B][4] int32 {frames expanded, frames skipped by
+ *     the blank threshold, extensions generated, frames whose working set lived in the workspace}, then per utterance the
+ *     working set of a frame too large for LDS: beam_size * (min(V, Vl) + 1) items, the most a frame can have.
+ * beam_size 1..256; topk 1..beam_size; V <= 65535. */
+size_t sbk_ctc_prefix_beam_search_workspace_bytes(int B, int T, int V, int Vl, int beam, int topk);
+int sbk_ctc_prefix_beam_search_f32(const float* x, const float* rel_len, const int32_t* token_table, int Vl,
+                                   const sbk_ctc_beam_config* cfg, void* workspace, size_t workspace_bytes,
+                                   int32_t* out_tokens, float* out_score, int32_t* out_count, int B, int T, int V,
+                                   sbk_stream_t stream);
+
 /* ---- transducer greedy decoding (csrc/transducer.hip; additive entries, ABI 11 unchanged) -------------------------------
  * TransducerBeamSearcher.transducer_greedy_decode (decoders/transducer.py:156-291) for the prediction network (PN)
  * [Embedding, LSTM (1..SBK_TRANSDUCER_MAX_LAYERS unidirectional layers, torch gate order i, f, g, o), Linear proj_dec], the

@@ -6,6 +6,7 @@
 
 #include "argmax.h"
 #include "common.h"
+#include "ctc_text.h"
 #include "device.h"
 
 namespace sbk {
@@ -14,13 +15,6 @@ namespace {
 
 constexpr int kCtcThreads = 256;       // one thread per beam slot / candidate
 constexpr int kCtcBeamMax = kCtcThreads;
-constexpr uint32_t kHashMod = 2147483647u;  // 2^31 - 1: two polynomial hashes of a string's characters
-
-__device__ __forceinline__ uint32_t hmul(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * b) % kHashMod); }
-__device__ __forceinline__ uint32_t hadd(uint32_t a, uint32_t b) {
-  const uint32_t s = a + b;  // (a, b < 2^31: no wrap)
-  return s >= kHashMod ? s - kHashMod : s;
-}
 
 // ---------------------------------------------------------------------------------------------------------- greedy
 // x [B,T,V]; len_b = int(round(fp32(rel[b] * T))) (half to even, as torch.round); tokens [B,T] (compacted), count [B].
@@ -140,14 +134,6 @@ __device__ __forceinline__ bool beam_before(const Beam& a, const Beam& b) {
   const float sa = rank_score(a), sb = rank_score(b);
   const float ka = isnan(sa) ? -INFINITY : sa, kb = isnan(sb) ? -INFINITY : sb;
   return ka > kb || (ka == kb && a.order < b.order);
-}
-// numpy's npy_logaddexpf
-__device__ __forceinline__ float logaddexp_f32(float x, float y) {
-  if (x == y) return x + 0.693147180559945309f;
-  const float d = x - y;
-  if (d > 0.0f) return x + log1pf(expf(-d));
-  if (d <= 0.0f) return y + log1pf(expf(d));
-  return d;  // NaN
 }
 // merge_tokens(text, w) with w = the beam's partial word: text + " " + w (either side empty: the other)
 __device__ __forceinline__ void fold_partial(CtcBeam& c, uint32_t sp1, uint32_t sp2, uint32_t space_code) {

@@ -4,8 +4,9 @@
 The frame loop of the beam search runs on the MI355X in one launch per batch (include/sbk.h, sbk_ctc_beam_search_f32); the
 host only rebuilds each returned hypothesis' ``text`` and ``text_frames`` by replaying the token path the kernel reports
 through the reference's string rules (O(T) per hypothesis).  With ``kenlm_model_path`` an ARPA n-gram model (order 1..5,
-decoders/ngram.py) is fused into the same launch (sbk_ctc_beam_search_lm_f32).  CTCPrefixBeamSearcher and the streaming
-``partial_decode_beams`` are not implemented."""
+decoders/ngram.py) is fused into the same launch (sbk_ctc_beam_search_lm_f32).  CTCPrefixBeamSearcher runs on
+csrc/ctc_prefix_search.hip in the same way, without a language model.  The streaming ``partial_decode_beams`` is not
+implemented."""
 import dataclasses
 import math
 import warnings
@@ -196,10 +197,7 @@ class CTCBaseSearcher(torch.nn.Module):
         return self.decode_beams(log_probs, wav_lens, lm_start_state)
 
 
-class CTCBeamSearcher(CTCBaseSearcher):
-    """decoders/ctc.py:1156-1487: the whole search of a batch is one device launch (sbk_ctc_beam_search_f32; with an
-    n-gram model, sbk_ctc_beam_search_lm_f32).  Beam sizes up to 256 on both paths."""
-
+class _DeviceSearchConfig:
     def config(self):
         from speechbrain_amd import native
 
@@ -211,6 +209,11 @@ class CTCBeamSearcher(CTCBaseSearcher):
             token_prune_min_logp=float(np.float32(self.token_prune_min_logp)),
             log_blank_skip_threshold=float(np.float32(self.blank_skip_threshold)), char_base1=HASH_BASE1,
             char_base2=HASH_BASE2, space_code=ord(" ") + 1)
+
+
+class CTCBeamSearcher(_DeviceSearchConfig, CTCBaseSearcher):
+    """decoders/ctc.py:1156-1487: the whole search of a batch is one device launch (sbk_ctc_beam_search_f32; with an
+    n-gram model, sbk_ctc_beam_search_lm_f32).  Beam sizes up to 256 on both paths."""
 
     def decode_beams(self, log_probs, wav_lens=None, lm_start_state=None):
         from speechbrain_amd import native
@@ -237,8 +240,81 @@ class CTCBeamSearcher(CTCBaseSearcher):
         return [[self.replay(paths[b, k], scores[b, k]) for k in range(count[b])] for b in range(len(count))]
 
 
-class CTCPrefixBeamSearcher(CTCBaseSearcher):
-    """decoders/ctc.py:1490-: not implemented (the reference itself calls it unstable); use CTCBeamSearcher."""
+class CTCPrefixBeamSearcher(_DeviceSearchConfig, CTCBaseSearcher):
+    """decoders/ctc.py:1488-1905: prefix beam search -- beams are prefix texts with blank / non-blank probabilities, merged
+    by text -- as one device launch per batch (sbk_ctc_prefix_beam_search_f32, csrc/ctc_prefix_search.hip).  Beam sizes up
+    to 256, no language model: ``kenlm_model_path`` raises NotImplementedError."""
 
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError("CTCPrefixBeamSearcher is not implemented: use CTCBeamSearcher")
+    def __init__(self, blank_index, vocab_list, space_token=" ", kenlm_model_path=None, **kwargs):
+        if kenlm_model_path is not None:
+            raise NotImplementedError("kenlm_model_path: CTCPrefixBeamSearcher runs without a language model; n-gram "
+                                      "fusion is implemented for CTCBeamSearcher")
+        super().__init__(blank_index, vocab_list, space_token, None, **kwargs)
+        for v, tok in enumerate(self.vocab_list):  # the text keys of the kernel follow a token's text as one word piece
+            tok = str(tok)
+            text = tok[1:] if self.is_spm and tok[:1] == self.spm_token else tok
+            if v in (self.blank_index, self.space_index) or (tok != "" and (text == "" or text.split() == [text])):
+                continue
+            raise NotImplementedError(f"CTCPrefixBeamSearcher: vocabulary entry {v} ({tok!r}) is empty or holds white "
+                                      "space inside its text")
+        self._prefix_table = None
+
+    def partial_decode_beams(self, *args, **kwargs):
+        raise NotImplementedError("partial_decode_beams (streaming chunk decoding of CTC prefix beams) is not "
+                                  "implemented: decode whole utterances with decode_beams")
+
+    def prefix_table(self):
+        """token_table() with column 7 of include/sbk.h: 1 for the pieces that start with the boundary mark, which the
+        reference looks up as ``text + piece`` (mark included, a text no beam has) and so never merges when it extends."""
+        if self._prefix_table is None:
+            t = self.token_table().clone()
+            for v, tok in enumerate(self.vocab_list):
+                t[v, 7] = 1 if (self.is_spm and v != self.blank_index and str(tok)[:1] == self.spm_token) else 0
+            self._prefix_table = t
+        return self._prefix_table
+
+    def replay_prefix(self, path, score):
+        """The hypothesis whose prefix was created by token ``path[t]`` at frame t (-1 = none), through the rules of
+        _get_new_beam, finalize_decoding and decode_log_probs."""
+        vocab = self.vocab_list
+        text, partial, last, frames, pf = "", "", -1, [], (-1, -1)
+        for t, v in enumerate(path):
+            if v < 0:
+                continue
+            tok = str(vocab[v])
+            boundary = tok[:1] == self.spm_token if self.is_spm else v == self.space_index
+            if boundary:
+                if partial != "":
+                    frames = frames + [pf]
+                partial, pf = (tok[1:], (t, t + 1)) if self.is_spm else ("", (-1, -1))
+                text = text + " " + partial
+            elif v == last:
+                text, pf = text + tok, (pf[0], t + 1)
+            else:
+                text, partial, pf = text + tok, partial + tok, ((t, t + 1) if pf[0] < 0 else (pf[0], t + 1))
+            last = v
+        if partial != "":
+            frames = frames + [pf]
+        score = np.float32(score)
+        return CTCHypothesis(text=self.normalize_whitespace(text), last_lm_state=None, score=score, lm_score=score,
+                             text_frames=list(zip(text.split(), frames)))
+
+    def decode_beams(self, log_probs, wav_lens=None, lm_start_state=None):
+        from speechbrain_amd import native
+
+        if lm_start_state is not None:
+            raise NotImplementedError("lm_start_state: CTCPrefixBeamSearcher runs without a language model")
+        if log_probs.size(2) != len(self.vocab_list):
+            warnings.warn(f"Vocab size mismatch: log_probs vocab dim is {log_probs.size(2)} while vocab_list is "
+                          f"{len(self.vocab_list)}. During decoding, going to truncate the log_probs vocab dim to match "
+                          "vocab_list.")
+        if log_probs.size(2) < len(self.vocab_list):
+            raise NotImplementedError("CTC prefix beam search: a vocabulary longer than the posteriors' last dimension")
+        x = log_probs if log_probs.dtype == torch.float32 else log_probs.float()
+        paths, scores, count = native.ctc_prefix_beam_search(x, wav_lens, self.prefix_table(), len(self.vocab_list),
+                                                             self.config())
+        paths, scores, count = paths.cpu().numpy(), scores.cpu().numpy(), count.cpu().tolist()
+        if min(count) < 0:
+            raise ValueError(f"wav_lens: utterance {count.index(-1)} has a length that is no number, negative or longer "
+                             f"than the {log_probs.size(1)} frames")
+        return [[self.replay_prefix(paths[b, k], scores[b, k]) for k in range(count[b])] for b in range(len(count))]

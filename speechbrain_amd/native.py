@@ -226,6 +226,9 @@ def _declare(lib):
         "sbk_ctc_greedy_decode_f32": ([p, p, p, p, i, i, i, i, p], c_int),
         "sbk_ctc_beam_search_workspace_bytes": ([i, i, i, i, i], ctypes.c_size_t),
         "sbk_ctc_beam_search_f32": ([p, p, p, i, POINTER(CTCBeamConfig), p, ctypes.c_size_t, p, p, p, i, i, i, p], c_int),
+        "sbk_ctc_prefix_beam_search_workspace_bytes": ([i, i, i, i, i, i], ctypes.c_size_t),
+        "sbk_ctc_prefix_beam_search_f32": ([p, p, p, i, POINTER(CTCBeamConfig), p, ctypes.c_size_t, p, p, p, i, i, i, p],
+                                           c_int),
         "sbk_ctc_beam_search_lm_f32": ([p, p, p, i, POINTER(CTCBeamConfig), POINTER(CTCLMTables), p, ctypes.c_size_t, p, p, p,
                                         p, i, i, i, p], c_int),
         "sbk_transducer_greedy_f32": ([POINTER(TransducerWeights), POINTER(TransducerConfig), p, p, p, p, p, p, p, i, i, p],
@@ -2232,6 +2235,32 @@ def ctc_beam_search(x, rel_len, table, n_vocab, cfg, lm=None):
         return paths, scores, count, lm_scores
     _chk(lib.sbk_ctc_beam_search_f32(_p(x), _p(rel), _p(table), int(n_vocab), ctypes.byref(cfg), ws.ptr, nbytes, _p(paths),
                                      _p(scores), _p(count), B, T, V, _stream(x)), "sbk_ctc_beam_search_f32")
+    return paths, scores, count
+
+
+def ctc_prefix_beam_search(x, rel_len, table, n_vocab, cfg, with_stats=False):
+    """CTCPrefixBeamSearcher on the device (sbk_ctc_prefix_beam_search_f32).  x [B,T,V] fp32 log-probabilities, table
+    [n_vocab,8] int32 (the token table of include/sbk.h with its column 7), cfg a CTCBeamConfig -> (paths [B,topk,T] int32:
+    the token that created the prefix at each frame, scores [B,topk], count [B]; -1 = a bad length).  ``with_stats`` adds
+    the kernel's counters [B,4] int32: frames expanded, frames skipped, extensions, frames held in the workspace."""
+    lib = load()
+    _f32(x)
+    B, T, V = x.shape
+    x = x.contiguous()
+    rel = _rel_len(rel_len, x.device)
+    table = table.to(device=x.device, dtype=torch.int32).contiguous()
+    _dev_ok(x, rel, table)
+    nbytes = lib.sbk_ctc_prefix_beam_search_workspace_bytes(B, T, V, int(n_vocab), cfg.beam_size, cfg.topk)
+    ws = _Workspace(nbytes, x.device, align=16, floor=1)
+    paths = torch.empty(B, max(cfg.topk, 1), T, dtype=torch.int32, device=x.device)
+    scores = torch.empty(B, max(cfg.topk, 1), dtype=torch.float32, device=x.device)
+    count = torch.empty(B, dtype=torch.int32, device=x.device)
+    _chk(lib.sbk_ctc_prefix_beam_search_f32(_p(x), _p(rel), _p(table), int(n_vocab), ctypes.byref(cfg), ws.ptr, nbytes,
+                                            _p(paths), _p(scores), _p(count), B, T, V, _stream(x)),
+         "sbk_ctc_prefix_beam_search_f32")
+    if with_stats:
+        at = ws.off + (B * T * cfg.beam_size + B * T) * 4
+        return paths, scores, count, ws.buf[at:at + B * 16].view(torch.int32).reshape(B, 4)
     return paths, scores, count
 
 

@@ -2,12 +2,14 @@
 transcribe_batch of 32 x 10 s from 16-bit PCM with greedy decoding and with CTCBeamSearcher (beam 100, beam_prune_logp
 -12, token_prune_min_logp -1.2, prune_history False), plus the decode kernels' own times (HIP events).  One JSON line.
 
-    python tools/ctc_bench.py [--steps 10] [--warmup 3] [--arpa PATH | --lm-order N] [--compare-lib libsbk_hip.so]
+    python tools/ctc_bench.py [--steps 10] [--warmup 3] [--arpa PATH | --lm-order N] [--compare-lib libsbk_hip.so] [--prefix]
 
 With --arpa or --lm-order the same log-probabilities are also searched with an n-gram model fused in (--lm-order: a synthetic
 ARPA model of that order, whose size is recorded), and the plain and the fused beam-100 kernels are timed side by side in
 blocks of launches (HIP events around each block; the spread of the block means is reported).  --compare-lib times the plain
-kernel of another build of the library, such as the parent commit's, in the same blocks.
+kernel of another build of the library, such as the parent commit's, in the same blocks.  --prefix times
+CTCPrefixBeamSearcher's kernel beside the beam kernel in the same way, with the searchers' default thresholds and with the
+recipe's, each block of launches under a time limit of its own (--step-limit).
 """
 import argparse
 import functools
@@ -58,6 +60,9 @@ def main():
     ap.add_argument("--arpa", default=None, help="an ARPA n-gram model to fuse into the beam search")
     ap.add_argument("--lm-order", type=int, default=0, help="generate a synthetic ARPA model of this order instead")
     ap.add_argument("--compare-lib", default=None, help="another libsbk_hip.so whose plain beam kernel is timed alongside")
+    ap.add_argument("--prefix", action="store_true",
+                    help="time the prefix beam search kernel beside the beam kernel (beam 100; default and recipe thresholds)")
+    ap.add_argument("--step-limit", type=int, default=60, help="seconds a block of launches of --prefix may take")
     args = ap.parse_args()
     native.load()
     B, n = args.batch, int(args.seconds * 16000)
@@ -94,7 +99,55 @@ def main():
         res[f"{name}_frames"] = int(logp.shape[1])
     if args.arpa or args.lm_order:
         res.update(lm_kernels(args, asr, logp, lens.cuda()))
+    if args.prefix:
+        res.update(prefix_kernels(args, logp, lens.cuda()))
     print(json.dumps(res))
+
+
+def prefix_kernels(args, logp, lens):
+    """sbk_ctc_beam_search_f32 and sbk_ctc_prefix_beam_search_f32 on the same log-probabilities, with the searchers' default
+    thresholds and with the recipe's (BEAM), in alternating blocks of launches (HIP events around each block), and the
+    prefix kernel's own counters.  Every block runs under a time limit of its own (--step-limit seconds, SIGALRM): a kernel
+    that does not come back ends the tool there instead of holding the device."""
+    import signal
+
+    from speechbrain_amd import native
+    from speechbrain_amd.decoders.ctc import CTCBeamSearcher, CTCPrefixBeamSearcher
+
+    legs = []
+    for tag, kw in (("default", dict(blank_index=0, beam_size=100)), ("recipe", BEAM)):
+        beam, prefix = CTCBeamSearcher(vocab_list=CHARS, **kw), CTCPrefixBeamSearcher(vocab_list=CHARS, **kw)
+        tb, tp = beam.token_table().to(logp.device), prefix.prefix_table().to(logp.device)
+        legs.append((f"beam_{tag}", lambda s=beam, t=tb, **o: native.ctc_beam_search(logp, lens, t, len(CHARS), s.config())))
+        legs.append((f"prefix_{tag}", lambda s=prefix, t=tp, **o: native.ctc_prefix_beam_search(logp, lens, t, len(CHARS),
+                                                                                            s.config(), **o)))
+    blocks = {name: [] for name, _ in legs}
+    for rep in range(7):
+        for name, fn in legs:
+            signal.alarm(args.step_limit)  # (default action: the process ends)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            fn()
+            a.record()
+            for _ in range(args.steps):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            signal.alarm(0)
+            if rep > 0:
+                blocks[name].append(a.elapsed_time(b) / args.steps)
+    out = {"prefix_settings_default": "beam 100, beam_prune_logp -10, token_prune_min_logp -5, prune_history True",
+           "prefix_settings_recipe": "beam 100, beam_prune_logp -12, token_prune_min_logp -1.2, prune_history False"}
+    for name, v in blocks.items():
+        out[f"{name}_kernel_ms_blocks"] = [round(t, 4) for t in v]
+        out[f"{name}_kernel_ms_median"] = round(sorted(v)[len(v) // 2], 4)
+    for tag in ("default", "recipe"):
+        out[f"prefix_over_beam_{tag}"] = round(out[f"prefix_{tag}_kernel_ms_median"] / out[f"beam_{tag}_kernel_ms_median"], 3)
+        st = dict(legs)[f"prefix_{tag}"](with_stats=True)[3].cpu().double()
+        out[f"prefix_{tag}_frames_expanded_per_utt"] = round(float(st[:, 0].mean()), 1)
+        out[f"prefix_{tag}_frames_skipped_per_utt"] = round(float(st[:, 1].mean()), 1)
+        out[f"prefix_{tag}_extensions_per_expanded_frame"] = round(float(st[:, 2].sum() / st[:, 0].sum().clamp(min=1)), 1)
+        out[f"prefix_{tag}_frames_in_workspace"] = int(st[:, 3].sum())
+    return out
 
 
 def lm_kernels(args, asr, logp, lens):

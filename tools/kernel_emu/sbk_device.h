@@ -129,6 +129,11 @@ static inline int atomicMin(int* p, int v) {
   }
   return o;
 }
+static inline int atomicCAS(int* p, int expect, int v) {
+  __atomic_compare_exchange_n(p, &expect, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
+  return expect;
+}
+static inline int atomicExch(int* p, int v) { return __atomic_exchange_n(p, v, __ATOMIC_RELAXED); }
 static inline int atomicMaxUnused_(int* p, int v) { int o = *p; if (v > o) *p = v; return o; }
 
 namespace sbk {
