@@ -762,6 +762,23 @@ int sbk_transducer_beam_search_lm_f32(const sbk_transducer_weights* W, const sbk
                                       size_t workspace_bytes, int32_t* out_tokens, int32_t* out_len, float* out_score,
                                       int32_t* out_count, int32_t* out_status, int B, int T, sbk_stream_t stream);
 
+/* ---- one RNNLM step for the n hypothesis rows of a beam search (csrc/rnnlm_step.hip; additive entries, ABI 11 unchanged) --
+ * replaces: decoders/scorer.py RNNLMScorer.score + permute_mem -- logits, hs = lm(inp_tokens, hx = memory) with memory the
+ * previous hs after index_select(dim=1, predecessors), then log_softmax(logits / temperature).  The gather is part of the LSTM
+ * kernel: row r reads h and c of row parent[r] of state_in and writes row r of state_out; the caller swaps the two buffers.
+ *   tokens    [n] int32   the token fed at this step (indexes emb_ih)
+ *   parent    [n] int32   the row of state_in every row continues; NULL = identity
+ *   state_in  [n_layers][2][n][hidden]  h then c of every layer; NULL = zeros (the first step)
+ *   state_out the same layout; must not alias state_in
+ *   out       [n, vocab] = weight * log_softmax(logits / temperature)
+ * Limits: those of sbk_rnnlm_weights (1..4 LSTM layers, 1..2 DNN blocks, hidden <= 2048) and 1 <= n <= 65535.  tokens and
+ * parent are clamped where they index and checked on the device (one 4-byte read-back): a value outside [0, n_emb) / [0, n)
+ * is SBK_EINVAL with the argument's name.  Every sum has a fixed order: two runs give the same bits on any stream. */
+size_t sbk_rnnlm_step_workspace_bytes(const sbk_rnnlm_weights* LM, int n);
+int sbk_rnnlm_step_f32(const sbk_rnnlm_weights* LM, const int32_t* tokens, const int32_t* parent, const float* state_in,
+                       float* state_out, void* workspace, size_t workspace_bytes, float* out, float weight,
+                       float temperature, int n, sbk_stream_t stream);
+
 /* log_softmax(x / temperature) * weight over the last dimension, x [rows,V] (seq2seq.py:1933). */
 int sbk_log_softmax_f32(const float* x, float* out, int rows, int V, float temperature, float weight,
                         sbk_stream_t stream);
@@ -921,6 +938,12 @@ typedef struct {
   float* out_probe;
   const uint16_t* ctc_w3; /* optional (NULL = unused; ABI 6): ctc_w as sbk_split_bf16x3 writes it (the CTC head over
                              the B*T encoder frames, scorer.py:239-255, as sbk_gemm_nt_f32x3) */
+  /* optional RNNLM full scorer (RNNLMScorer, scorer.py), scored BEFORE the CTC scorer like full_scorers=[rnnlm, ctc]:
+   * log_probs += rnnlm_weight * log_softmax(RNNLM(token, state) / rnnlm_temperature), one sbk_rnnlm_step_f32 per step whose
+   * parent map is the beam update's predecessors.  rnnlm = NULL or rnnlm_weight = 0: off (appended fields: a zeroed tail is
+   * the search as it was; a caller built against the shorter struct must be recompiled, the library reads the tail).  Not together with `lm`, a token prompt or graph_mode 1. */
+  const sbk_rnnlm_weights* rnnlm;
+  float rnnlm_weight, rnnlm_temperature;
 } sbk_search_config;
 
 /* ---- the CTC prefix scorer as a per-step API (ABI 11) -----------------------------------------------------------------------

@@ -22,7 +22,8 @@ LIB = os.path.join(HERE, "libsbk_hip.so")
 # one workgroup per CU either way).  Sources from before keep their compile lines, so that their code and recorded
 # timings stay what they were.  (A cc1 option.  The host pass of hipcc answers it with "not a recognized feature for this
 # target (ignoring feature)", which is harmless; the device pass takes it silently.)
-EXTRA_FLAGS = {"ctc_prefix_search.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+_NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS = {"ctc_prefix_search.hip": _NO_PACKED_FP32, "rnnlm_step.hip": _NO_PACKED_FP32}
 
 
 def sources():

@@ -118,6 +118,13 @@ int gemm_ln_nt(const float* A, int lda, const float* Wf, int ldw, const float* b
                int ldc, int M, int N, int K, float eps, int act, float alpha, hipStream_t st);
 int layernorm(const float* x, const float* gamma, const float* beta, float* y, int rows, int d, float eps, int act,
               hipStream_t st);
+// One RNNLM step for n hypothesis rows (csrc/rnnlm_step.hip) as the beam search calls it: no argument checks and no read-back
+// (the kernels clamp tokens and parent).  ws: rnnlm_step_workspace_floats; rnnlm_state_zero clears one state buffer.
+int rnnlm_check(const sbk_rnnlm_weights* M, const char* who);
+size_t rnnlm_step_workspace_floats(const sbk_rnnlm_weights* M, int n);
+int rnnlm_state_zero(float* state, const sbk_rnnlm_weights* M, int n, hipStream_t st);
+int rnnlm_step(const sbk_rnnlm_weights* M, const int32_t* tokens, const int32_t* parent, const float* state_in, float* state_out,
+               float* ws, float* out, float weight, float temperature, int n, hipStream_t st);
 int relpos_attention(const float* qkv, const float* pos, const float* bias_u, const float* bias_v,
                      const int32_t* key_len, float* out, float* attn, int B, int T, int H, int Dh, float scale,
                      hipStream_t st, int chunk = 0, int left = -1);

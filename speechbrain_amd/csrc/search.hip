@@ -1316,16 +1316,43 @@ size_t carve_layout(Layout& lay, void* workspace, Args... args) {
 int beam_pos_off(const sbk_search_config* cfg) { return cfg->prompt && cfg->prompt_len > 1 ? cfg->prompt_len - 1 : 0; }
 int beam_lmax(const sbk_search_config* cfg) { return (cfg->max_steps > 0 ? cfg->max_steps : 1) + beam_pos_off(cfg); }
 const sbk_lm_weights* beam_lm(const sbk_search_config* cfg) { return (cfg->lm && cfg->lm_weight != 0.0f) ? cfg->lm : nullptr; }
+const sbk_rnnlm_weights* beam_rnnlm(const sbk_search_config* cfg) {
+  return (cfg->rnnlm && cfg->rnnlm_weight != 0.0f) ? cfg->rnnlm : nullptr;
+}
+
+// the RNNLM scorer's buffers: the LM state of every hypothesis row twice (a step reads one through the predecessors and writes the
+// other), the step's scratch and its weighted log-probabilities
+struct RnnLmBufs {
+  float* state[2];  // [layers][2][n][H] each
+  float* ws;
+  float* logits;    // [n, V]
+  void carve(Carver& c, const sbk_rnnlm_weights* M, int n) {
+    const size_t st = (size_t)M->n_layers * 2 * n * M->hidden;
+    state[0] = c.take<float>(st);
+    state[1] = c.take<float>(st);
+    ws = c.take<float>(sbk::rnnlm_step_workspace_floats(M, n));
+    logits = c.take<float>((size_t)n * M->vocab);
+  }
+};
+
+// (the sizes the carve multiplies are in range: what the workspace query may see before the entry's own checks)
+bool valid_rnnlm(const sbk_search_config* cfg) {
+  const sbk_rnnlm_weights* M = beam_rnnlm(cfg);
+  return M && M->n_layers >= 1 && M->n_layers <= SBK_TRANSDUCER_MAX_LAYERS && M->hidden >= 1 && M->n_dnn >= 1 &&
+         M->n_dnn <= SBK_RNNLM_MAX_DNN && M->dnn >= 1 && M->vocab >= 1;
+}
 
 struct BeamLayout {  // sbk_beam_search_f32
   DecoderBufs d;
   BeamBufs bb;
   LmBufs lb;  // only with an LM scorer
+  RnnLmBufs rb;  // only with an RNNLM scorer
   void carve(Carver& c, const sbk_decoder_weights* W, const sbk_search_config* cfg, int B, int T) {
     const int n = B * cfg->beam, Lmax = beam_lmax(cfg);
     carve_decoder(c, d, W, n, B, T, Lmax);
     carve_beam(c, bb, B, cfg->beam, T, W->vocab, Lmax, cfg->ctc_weight > 0.0f, cfg->ctc_window_size);
     if (beam_lm(cfg)) carve_lm(c, lb, beam_lm(cfg), n, Lmax);
+    if (valid_rnnlm(cfg)) rb.carve(c, beam_rnnlm(cfg), n);
   }
 };
 
@@ -1394,6 +1421,17 @@ extern "C" int sbk_beam_search_f32(const sbk_decoder_weights* W, const sbk_searc
   SBK_REQUIRE(!ctc || (ctc_w && ctc_b), "beam_search: ctc_weight > 0 needs the ctc_lin weights");
   SBK_REQUIRE(!ctc || (cfg->bos != cfg->eos && cfg->bos != cfg->blank && cfg->eos != cfg->blank),
               "Set blank, eos and bos to different indexes for joint ATT/CTC or CTC decoding");
+  const sbk_rnnlm_weights* RLM = beam_rnnlm(cfg);
+  if (RLM) {  // (before the carve, which multiplies its sizes)
+    SBK_TRY(sbk::rnnlm_check(RLM, "beam_search: rnnlm"));
+    SBK_REQUIRE(!beam_lm(cfg), "beam_search: the TransformerLM scorer and the RNNLM scorer together are not implemented (one LM)");
+    SBK_REQUIRE(!cfg->prompt, "beam_search: the RNNLM scorer with a token prompt is not implemented");
+    SBK_REQUIRE(cfg->graph_mode != 1, "beam_search: the RNNLM scorer with graph_mode 1 is not implemented (graph_mode 0 or 2)");
+    SBK_REQUIRE(RLM->vocab == W->vocab, "beam_search: the RNNLM scores %d tokens, the decoder %d", RLM->vocab, W->vocab);
+    SBK_REQUIRE(RLM->n_emb >= W->vocab, "beam_search: the RNNLM embeds %d tokens, the decoder emits %d", RLM->n_emb, W->vocab);
+    SBK_REQUIRE(cfg->rnnlm_temperature > 0.0f, "beam_search: rnnlm_temperature must be positive");
+    SBK_REQUIRE(B * cfg->beam <= 65535, "beam_search: %d hypothesis rows exceed the RNNLM step's 65535", B * cfg->beam);
+  }
   BeamLayout lay;
   SBK_REQUIRE(workspace_bytes >= carve_layout(lay, workspace, W, cfg, B, T), "beam_search: workspace too small");
   SBK_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "beam_search: workspace must be 256-byte aligned");
@@ -1411,7 +1449,10 @@ extern "C" int sbk_beam_search_f32(const sbk_decoder_weights* W, const sbk_searc
   const DecoderBufs& d = lay.d;
   BeamBufs& bb = lay.bb;
   const LmBufs& lb = lay.lb;
-  const float* extra = LM ? lb.logits : nullptr;  // weighted LM log-probs of the step
+  const RnnLmBufs& rb = lay.rb;
+  const float* extra = LM ? lb.logits : RLM ? rb.logits : nullptr;  // weighted LM log-probs of the step
+  // the RNNLM's first step starts from a zero state whatever the predecessors hold (the step number may live on the device)
+  if (RLM) SBK_TRY(sbk::rnnlm_state_zero(rb.state[0], RLM, n, st));
 
   const int Vp = ctc_pitch(V);  // row pitch of the CTC posteriors
   SBK_TRY(project_memory(W, d, enc, B, T, st));
@@ -1486,6 +1527,9 @@ extern "C" int sbk_beam_search_f32(const sbk_decoder_weights* W, const sbk_searc
       SBK_TRY(lm_step(LM, lb, bb.s.tokens[cur], bb.s.kv_slot[cur], bb.s.seq[cur], Lmax, 1, cfg->bos, step, n, Lmax, st));
       SBK_TRY(sbk::log_softmax_rows(lb.logits, lb.logits, n, V, cfg->lm_temperature, cfg->lm_weight, st));
     }
+    if (RLM)  // RNNLMScorer.score + permute_mem: the state rows follow the predecessors the previous beam update chose
+      SBK_TRY(sbk::rnnlm_step(RLM, bb.s.tokens[cur], bb.s.parent, rb.state[cur], rb.state[cur ^ 1], rb.ws, rb.logits,
+                              cfg->rnnlm_weight, cfg->rnnlm_temperature, n, st));
     const int32_t* win = nullptr;
     if (window > 0) {  // attention peaks of this step (the last decoder layer's head-averaged cross-attention)
       SBK_TRY(sbk::cross_attn_avg_probs(d.q, d.ckv[W->n_layers - 1], enc_len, bb.attn_avg, n, T, dm, W->nhead, beam, st));

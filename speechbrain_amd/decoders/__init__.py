@@ -1,5 +1,5 @@
 """speechbrain.decoders mirror (ASR searchers + CTC / TransformerLM scorers)."""
-from speechbrain_amd.decoders.scorer import CTCScorer, ScorerBuilder, TransformerLMScorer  # noqa: F401
+from speechbrain_amd.decoders.scorer import CTCScorer, RNNLMScorer, ScorerBuilder, TransformerLMScorer  # noqa: F401
 from speechbrain_amd.decoders.seq2seq import (S2SRNNBeamSearcher, S2SRNNGreedySearcher,  # noqa: F401
                                                 S2STransformerBeamSearcher, S2STransformerGreedySearcher,
                                                 S2SWhisperBeamSearcher, S2SWhisperGreedySearcher)

@@ -1,11 +1,11 @@
-"""speechbrain.decoders.scorer mirror for the ASR recipe: ScorerBuilder + CTCScorer + TransformerLMScorer.
+"""speechbrain.decoders.scorer mirror for the ASR recipe: ScorerBuilder + CTCScorer + TransformerLMScorer + RNNLMScorer.
 
 Two ways to use them.  ``S2STransformerBeamSearcher(scorer=ScorerBuilder(...))`` reads them as configuration: the CTC prefix
 scoring and the LM steps are fused into the device-side search (csrc/ctc_prefix.hip, csrc/search.hip).  A searcher written
 against the reference's own step protocol (scorer.py:1221-1315: ``reset_scorer_mem`` once per batch, then ``score`` and
 ``permute_scorer_mem`` once per decoding step) calls the same methods here: ``CTCScorer`` runs the library's prefix scorer
 through its per-step entry points (``sbk_ctc_scorer_*``), ``TransformerLMScorer`` re-runs the LM over the prefix like the
-reference does (``sbk_lm_prefix_f32``).
+reference does (``sbk_lm_prefix_f32``), ``RNNLMScorer`` steps the LM on the state it carries (``sbk_rnnlm_step_f32``).
 """
 import torch
 
@@ -112,12 +112,51 @@ class TransformerLMScorer(BaseScorerInterface):
         return None
 
 
+class RNNLMScorer(BaseScorerInterface):
+    """scorer.py RNNLMScorer: language_model = a lobes.models.RNNLM.RNNLM; temperature divides its logits before the log-softmax.
+    ``memory`` is the LM's state [layers, 2 (h, c), n_bh, H] of the previous step with the row map ``permute_mem`` recorded:
+    the reference's index_select of the state is not run here, the next step's LSTM kernel reads through the map
+    (csrc/rnnlm_step.hip).  The device search steps the same entry itself (sbk_search_config.rnnlm)."""
+
+    _WHAT = "the RNNLM scorer"
+
+    def __init__(self, language_model, temperature=1.0):
+        from speechbrain_amd import native
+        from speechbrain_amd.lobes.models import RNNLM
+
+        RNNLM.fused_parts(language_model, self._WHAT)  # (refuses what is not built before anything runs)
+        self.lm = language_model
+        self.lm.eval()
+        self.temperature = temperature
+        self._prepared = native.Derived()
+
+    def prepared(self, device):
+        """The LM's weight table on ``device`` (a native.RNNLMPrepared), rebuilt when a parameter changes."""
+        from speechbrain_amd.lobes.models import RNNLM
+
+        return RNNLM.prepared(self.lm, self._prepared, device, self._WHAT)
+
+    def score(self, inp_tokens, memory, candidates, attn):
+        from speechbrain_amd import native
+
+        state, parent = (None, None) if memory is None else memory  # (always the pair: score hands on (state, None))
+        out, state = native.rnnlm_step(self.prepared(inp_tokens.device), inp_tokens, parent, state, temperature=self.temperature)
+        return out, (state, None)
+
+    def permute_mem(self, memory, index):
+        """index [n_bh]: the row of the previous beam every new hypothesis extends; kept as the next step's parent map."""
+        return memory[0], index.reshape(-1).to(torch.int32)
+
+    def reset_mem(self, x, enc_lens):
+        return None
+
+
 _KNOWN = ("ctc", "rnnlm", "transformerlm", "kenlm", "coverage", "length", "huggingfacelm", "basescorerinterface")
 
 
 class ScorerBuilder:
-    """scorer.py:1075-1315.  Supported compositions: full_scorers drawn from {CTCScorer,
-    TransformerLMScorer} -- the recipe's ``valid_search`` ([ctc]) and ``test_search``
+    """scorer.py:1075-1315.  Supported compositions: full_scorers drawn from {CTCScorer, one of
+    TransformerLMScorer / RNNLMScorer} -- the recipe's ``valid_search`` ([ctc]) and ``test_search``
     ([transformerlm, ctc]) (conformer_large.yaml:215-239) -- and CTCScorer as the one partial scorer
     (``partial_scorers=[ctc]``: only the best int(beam_size * scorer_beam_scale) tokens of every hypothesis get a
     CTC score, :1287-1300)."""
@@ -129,12 +168,14 @@ class ScorerBuilder:
         self.weights = {**dict.fromkeys(_KNOWN, 0.0), **weights}
         self.full_scorers = {name(s): s for s in full_scorers}
         self.partial_scorers = {name(s): s for s in partial_scorers}
-        unsupported = [k for k in self.full_scorers if k not in ("ctc", "transformerlm")]
+        unsupported = [k for k in self.full_scorers if k not in ("ctc", "transformerlm", "rnnlm")]
         unsupported += [k for k in self.partial_scorers if k != "ctc"]
         if unsupported or ("ctc" in self.full_scorers and "ctc" in self.partial_scorers):
             raise NotImplementedError(
-                f"scorers {unsupported}: the device search fuses the CTC scorer (full or partial) and the full "
-                "TransformerLM scorer; RNNLM / KenLM / coverage / length scorers are not implemented")
+                f"scorers {unsupported}: the device search fuses the CTC scorer (full or partial) and one full LM scorer "
+                "(TransformerLM or RNNLM); KenLM / coverage / length scorers are not implemented")
+        if "transformerlm" in self.full_scorers and "rnnlm" in self.full_scorers:
+            raise NotImplementedError("scorers ['transformerlm', 'rnnlm']: the device search fuses one LM scorer, not both")
         if not 0.0 <= self.weights["ctc"] <= 1.0:
             raise ValueError("ctc_weight should not > 1.0 and < 0.0")
 

@@ -277,10 +277,16 @@ class S2STransformerBeamSearcher(S2SBaseSearcher):
         self.ctc_candidates = 0  # > 0: CTC is a partial scorer over that many candidates per hypothesis
         self.ctc_window_size = 0
         self.lm, self.lm_weight, self.lm_temperature = None, 0.0, 1.0
+        self.rnnlm, self.rnnlm_weight = None, 0.0  # (an RNNLMScorer: its temperature and weight table are read per search)
         if scorer is not None:
             if scorer.weights["transformerlm"] != 0.0 and "transformerlm" in scorer.full_scorers:
                 lms = scorer.full_scorers["transformerlm"]
                 self.lm, self.lm_weight, self.lm_temperature = lms.lm, scorer.weights["transformerlm"], lms.temperature
+            if scorer.weights["rnnlm"] != 0.0 and "rnnlm" in scorer.full_scorers:
+                self.rnnlm, self.rnnlm_weight = scorer.full_scorers["rnnlm"], scorer.weights["rnnlm"]
+                if self.lm is not None:
+                    raise NotImplementedError("the device search fuses one LM scorer: TransformerLM and RNNLM together are "
+                                              "not implemented")
             if length_normalization and scorer.weights["length"] > 0.0:
                 raise ValueError("Length normalization is not compatible with length rewarding.")
             if scorer.weights["ctc"] > 0.0:
@@ -316,6 +322,12 @@ class S2STransformerBeamSearcher(S2SBaseSearcher):
             self._lm_handle.ready.wait(self._lm_handle.device)  # (built on another worker's stream a moment ago?)
             lm = dict(lm=ctypes.pointer(self._lm_handle.W), lm_weight=self.lm_weight,
                       lm_temperature=self.lm_temperature)
+        if self.rnnlm is not None:
+            if int(self.graph_mode) == 1 and not self.ctc_window_size:  # (the window turns graph_mode off below)
+                raise NotImplementedError("the RNNLM scorer with graph_mode 1 is not implemented (graph_mode 0 or 2)")
+            self._rnnlm_prepared = self.rnnlm.prepared(self.fc.w.weight.device)  # (kept alive during the call)
+            lm = dict(rnnlm=ctypes.addressof(self._rnnlm_prepared.M), rnnlm_weight=self.rnnlm_weight,
+                      rnnlm_temperature=self.rnnlm.temperature)
         return native.SearchConfig(**lm, topk=self.topk if self.return_topk else 1,
                                    graph_mode=0 if self.ctc_window_size else int(self.graph_mode),
                                    bos=self.bos_index, eos=self.eos_index, blank=self.blank_index, beam=self.beam_size,

@@ -66,7 +66,9 @@ class TransducerBeamSearcher(torch.nn.Module):
         hypothesis is truncated: the kernel is given room for T * max_expansions tokens, which none can exceed.)"""
         fuse = self.lm is not None and self.lm_weight > 0  # (with lm_weight <= 0 the reference never touches the LM)
         if fuse:
-            self._lm_networks()  # (refuses what is not built before anything runs)
+            from speechbrain_amd.lobes.models import RNNLM
+
+            RNNLM.fused_parts(self.lm, "transducer beam search with LM fusion")  # (refuses before anything runs)
         if self.beam_size > native.TRANSDUCER_MAX_BEAM:
             raise NotImplementedError(f"transducer beam search with beam_size={self.beam_size} is not implemented "
                                       f"(at most {native.TRANSDUCER_MAX_BEAM})")
@@ -124,45 +126,11 @@ class TransducerBeamSearcher(torch.nn.Module):
                                       f"(got {[type(x).__name__ for x in cls]})")
         return layers[0], layers[1], layers[2], cls[0]
 
-    _LM_ACTS = {"LeakyReLU": native.ACT_LEAKY_RELU, "ReLU": native.ACT_RELU, "GELU": native.ACT_GELU, "Tanh": native.ACT_TANH}
-
-    def _lm_networks(self):
-        """(embedding, LSTM, [(Linear, LayerNorm)] per DNN block, out Linear, activation code) of an LM the kernel fuses."""
-        from speechbrain_amd.lobes.models.RNNLM import RNNLM
-
-        lm = self.lm
-        refuse = lambda why: NotImplementedError(  # noqa: E731
-            f"transducer beam search with LM fusion is not implemented for {type(lm).__name__}{why} (an RNNLM with a 1..4 layer "
-            "unidirectional LSTM, 1..2 DNN blocks and LeakyReLU, ReLU, GELU or Tanh)")
-        if not isinstance(lm, RNNLM):
-            raise refuse("")
-        rnn = lm.rnn.rnn
-        if rnn.bidirectional or not 1 <= rnn.num_layers <= native.TRANSDUCER_MAX_LAYERS:
-            raise refuse(f" with {rnn.num_layers} {'bidirectional ' if rnn.bidirectional else ''}LSTM layers")
-        blocks = lm.blocks()
-        if not 1 <= len(blocks) <= native.RNNLM_MAX_DNN:
-            raise refuse(f" with {len(blocks)} DNN blocks")
-        acts = {type(b[2]) for b in blocks}
-        act = next(iter(acts))
-        if len(acts) != 1 or act not in (torch.nn.LeakyReLU, torch.nn.ReLU, torch.nn.GELU, torch.nn.Tanh):
-            raise refuse(f" with activation {sorted(a.__name__ for a in acts)}")
-        mod = blocks[0][2]
-        if (act is torch.nn.LeakyReLU and mod.negative_slope != 0.01) or (act is torch.nn.GELU and mod.approximate != "none"):
-            raise refuse(f" with {mod}")
-        return lm.embedding, lm.rnn, [(b[0], b[1]) for b in blocks], lm.out, self._LM_ACTS[act.__name__]
-
     def _prepare_lm(self, device):
         """The LM's weight layouts on ``device``, by the key rule of _prepare."""
-        emb, lstm, blocks, out, act = self._lm_networks()
-        d = lambda t: None if t is None else t.detach().to(device)  # noqa: E731
+        from speechbrain_amd.lobes.models import RNNLM
 
-        def build():
-            layers = [tuple(d(t) for t in layer) for layer in lstm.layer_weights()]
-            dnn = [(d(lin.w.weight), d(lin.w.bias), d(ln.norm.weight), d(ln.norm.bias), ln.eps) for lin, ln in blocks]
-            return native.RNNLMPrepared(d(emb.Embedding.weight), layers, dnn, d(out.w.weight), d(out.w.bias), act)
-
-        return self._lm_prepared.get(list(self.lm.parameters()), build, device=device,
-                                     extra=(device, act) + tuple(ln.eps for _, ln in blocks))
+        return RNNLM.prepared(self.lm, self._lm_prepared, device, "transducer beam search with LM fusion")
 
     def _prepare(self, device, beam=False):
         """The kernel's weight layouts on ``device``, rebuilt when a parameter changes (the PN and classifier modules are

@@ -58,3 +58,47 @@ class RNNLM(torch.nn.Module):
         """[(Linear, LayerNorm, activation module)] per DNN block, in order."""
         layers = [m for m in self.dnn.values() if not isinstance(m, torch.nn.Dropout)]
         return [tuple(layers[i:i + 3]) for i in range(0, len(layers), 3)]
+
+
+def fused_parts(lm, what):
+    """(embedding, LSTM, [(Linear, LayerNorm)] per DNN block, out Linear, activation code) of an LM that the kernels behind
+    sbk_rnnlm_weights run -- the transducer beam search and the RNNLM scorer -- or NotImplementedError naming ``what``."""
+    from speechbrain_amd import native
+
+    refuse = lambda why: NotImplementedError(  # noqa: E731
+        f"{what} is not implemented for {type(lm).__name__}{why} (an RNNLM with a 1..4 layer "
+        "unidirectional LSTM, 1..2 DNN blocks and LeakyReLU, ReLU, GELU or Tanh)")
+    if not isinstance(lm, RNNLM):
+        raise refuse("")
+    rnn = lm.rnn.rnn
+    if rnn.bidirectional or not 1 <= rnn.num_layers <= native.TRANSDUCER_MAX_LAYERS:
+        raise refuse(f" with {rnn.num_layers} {'bidirectional ' if rnn.bidirectional else ''}LSTM layers")
+    blocks = lm.blocks()
+    if not 1 <= len(blocks) <= native.RNNLM_MAX_DNN:
+        raise refuse(f" with {len(blocks)} DNN blocks")
+    acts = {type(b[2]) for b in blocks}
+    act = next(iter(acts))
+    codes = {torch.nn.LeakyReLU: native.ACT_LEAKY_RELU, torch.nn.ReLU: native.ACT_RELU, torch.nn.GELU: native.ACT_GELU,
+             torch.nn.Tanh: native.ACT_TANH}
+    if len(acts) != 1 or act not in codes:
+        raise refuse(f" with activation {sorted(a.__name__ for a in acts)}")
+    mod = blocks[0][2]
+    if (act is torch.nn.LeakyReLU and mod.negative_slope != 0.01) or (act is torch.nn.GELU and mod.approximate != "none"):
+        raise refuse(f" with {mod}")
+    return lm.embedding, lm.rnn, [(b[0], b[1]) for b in blocks], lm.out, codes[act]
+
+
+def prepared(lm, derived, device, what):
+    """The native.RNNLMPrepared of ``lm`` on ``device``, kept in ``derived`` (a native.Derived) and rebuilt when a parameter
+    changes."""
+    from speechbrain_amd import native
+
+    emb, lstm, blocks, out, act = fused_parts(lm, what)
+    d = lambda t: None if t is None else t.detach().to(device)  # noqa: E731
+
+    def build():
+        layers = [tuple(d(t) for t in layer) for layer in lstm.layer_weights()]
+        dnn = [(d(lin.w.weight), d(lin.w.bias), d(ln.norm.weight), d(ln.norm.bias), ln.eps) for lin, ln in blocks]
+        return native.RNNLMPrepared(d(emb.Embedding.weight), layers, dnn, d(out.w.weight), d(out.w.bias), act)
+
+    return derived.get(list(lm.parameters()), build, device=device, extra=(device, act) + tuple(ln.eps for _, ln in blocks))

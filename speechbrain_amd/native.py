@@ -69,7 +69,7 @@ class SearchConfig(ctypes.Structure):  # sbk_search_config
                 ("utt_max_steps", c_void_p), ("graph_mode", c_int32), ("ctc_candidates", c_int32),
                 ("ctc_window_size", c_int32), ("prompt", c_void_p), ("prompt_len", c_int32), ("temperature_post", c_int32), ("logit_bias", c_void_p),
                 ("first_bias", c_void_p), ("probe_pos", c_int32), ("probe_token", c_int32), ("out_probe", c_void_p),
-                ("ctc_w3", c_void_p)]
+                ("ctc_w3", c_void_p), ("rnnlm", c_void_p), ("rnnlm_weight", c_float), ("rnnlm_temperature", c_float)]
 
 
 class CTCBeamConfig(ctypes.Structure):  # sbk_ctc_beam_config
@@ -243,6 +243,8 @@ def _declare(lib):
         "sbk_transducer_beam_search_lm_f32": ([POINTER(TransducerWeights), POINTER(RNNLMWeights), f,
                                                POINTER(TransducerBeamConfig), p, p, ctypes.c_size_t, p, p, p, p, p, i, i, p],
                                               c_int),
+        "sbk_rnnlm_step_workspace_bytes": ([POINTER(RNNLMWeights), i], ctypes.c_size_t),
+        "sbk_rnnlm_step_f32": ([POINTER(RNNLMWeights), p, p, p, p, p, ctypes.c_size_t, p, f, f, i, p], c_int),
         "sbk_beam_search_workspace_bytes": ([POINTER(DecoderWeights), POINTER(SearchConfig), i, i], ctypes.c_size_t),
         "sbk_beam_search_f32": ([POINTER(DecoderWeights), POINTER(SearchConfig), p, p, p, p, p, ctypes.c_size_t, p, p,
                                  p, p, p, p, p, POINTER(c_int32), i, i, p], c_int),
@@ -2319,6 +2321,33 @@ class RNNLMPrepared:
         self.device = self.emb_ih.device
         # (what one LM step reads: every matrix once, and one row of emb_ih)
         self.weight_bytes = 4 * sum(int(x.numel()) for x in keep) - 4 * int(self.emb_ih.numel()) + 4 * 4 * M.hidden
+
+
+def rnnlm_state(lm: RNNLMPrepared, n):
+    """An uninitialised state buffer of rnnlm_step: [layers, 2 (h, c), n, H] fp32 on the LM's device."""
+    return torch.empty(lm.M.n_layers, 2, int(n), lm.M.hidden, dtype=torch.float32, device=lm.device)
+
+
+def rnnlm_step(lm: RNNLMPrepared, tokens, parent=None, state_in=None, state_out=None, weight=1.0, temperature=1.0):
+    """sbk_rnnlm_step_f32: one RNNLM step for n hypothesis rows.  tokens [n] int32; parent [n] int32 (the row of ``state_in``
+    every row continues) or None (identity); state_in [layers, 2, n, H] or None (zeros: the first step); state_out the same
+    layout (allocated when None; never ``state_in``) -> (weight * log_softmax(logits / temperature) [n, V], state_out)."""
+    lib = load()
+    n = tokens.shape[0]
+    i32 = lambda t: None if t is None else t.to(device=lm.device, dtype=torch.int32).contiguous()  # noqa: E731
+    tokens, parent = i32(tokens), i32(parent)
+    if state_out is None:
+        state_out = rnnlm_state(lm, n)
+    for name, t in (("state_in", state_in), ("state_out", state_out)):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (lm.M.n_layers, 2, n, lm.M.hidden)):
+            raise SbkError(f"rnnlm_step: {name} must be fp32 [{lm.M.n_layers}, 2, {n}, {lm.M.hidden}], got {tuple(t.shape)}")
+    out = torch.empty(n, lm.M.vocab, dtype=torch.float32, device=lm.device)
+    _dev_ok(tokens, parent, state_in, state_out)
+    nbytes = lib.sbk_rnnlm_step_workspace_bytes(ctypes.byref(lm.M), n)
+    ws = _Workspace(nbytes, lm.device, align=16, floor=16)
+    _chk(lib.sbk_rnnlm_step_f32(ctypes.byref(lm.M), _p(tokens), _p(parent), _p(state_in), _p(state_out), ws.ptr, nbytes, _p(out),
+                                float(weight), float(temperature), n, _stream(out)), "sbk_rnnlm_step_f32")
+    return out, state_out
 
 
 def lstm(x, layers, hx=None):
