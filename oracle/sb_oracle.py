@@ -551,10 +551,14 @@ class SearchTrace:
 
 def beam_search(enc: Tensor, wav_len: Tensor, sd: SD, cfg: ModelCfg, sc: SearchCfg, pfx: str = "Transformer.",
                 seq_lin: str = "seq_lin.w.", ctc_lin: str = "ctc_lin.w.", trace: Optional[SearchTrace] = None,
-                lm_cfg: Optional[LMCfg] = None, lm_pfx: str = "LM."):
+                lm_cfg: Optional[LMCfg] = None, lm_pfx: str = "LM.", full_scorer=None):
     """S2SBeamSearcher.forward (decoders/seq2seq.py:1632-1723) specialised to
     S2STransformerBeamSearcher (:1853-1934) with an optional full CTC scorer
     (scorer.py:1221-1268).  Returns (hyps, best_lens, best_scores, best_log_probs).
+
+    ``full_scorer`` (default None: nothing changes): a stateful full scorer in front of the CTC scorer, as RNNLMScorer is
+    (scorer.py:258-411).  ``score(tokens [n_bh], memory or None) -> (weighted log-probs [n_bh,V], new memory)`` is added where
+    the TransformerLM term is; ``permute(memory, preds [n_bh]) -> memory`` follows the beam update (permute_mem).
     """
     B, T, _ = enc.shape
     beam, V = sc.beam, cfg.vocab
@@ -566,6 +570,7 @@ def beam_search(enc: Tensor, wav_len: Tensor, sd: SD, cfg: ModelCfg, sc: SearchC
         logp = F.log_softmax(F.linear(enc, sd[ctc_lin + "weight"], sd[ctc_lin + "bias"]), dim=-1)
         ctc = CTCPrefixScorer(logp, enc_lens, sc.blank, sc.eos)
     ctc_state = None
+    fs_memory = None
     enc_i = enc.repeat_interleave(beam, dim=0)
     enc_lens_i = enc_lens.repeat_interleave(beam, dim=0)
     tok = torch.full((n_bh,), sc.bos, dtype=torch.long)
@@ -607,6 +612,9 @@ def beam_search(enc: Tensor, wav_len: Tensor, sd: SD, cfg: ModelCfg, sc: SearchC
             lp = lp + lm_lp * sc.lm_weight
             if trace is not None:
                 trace.lm_log_probs.append(lm_lp.clone())
+        if full_scorer is not None:
+            fs_lp, fs_memory = full_scorer.score(tok, fs_memory)
+            lp = lp + fs_lp
         if ctc is not None:
             lp[:, sc.blank] = CTCPrefixScorer.NEG  # scorer.py:1248-1253
             ctc_sc, ctc_full = ctc.step(tok, ctc_state, beam)
@@ -624,6 +632,8 @@ def beam_search(enc: Tensor, wav_len: Tensor, sd: SD, cfg: ModelCfg, sc: SearchC
         memory = memory[preds]
         if ctc is not None:
             ctc_state = ctc.permute(ctc_full, cand, beam)
+        if full_scorer is not None:
+            fs_memory = full_scorer.permute(fs_memory, preds)
         tok_lp = lp_keep.view(B, -1).gather(1, cand).view(n_bh)
         alive_seq = torch.cat([alive_seq[preds], tok.unsqueeze(1)], dim=-1)
         alive_lp = torch.cat([alive_lp[preds], tok_lp.unsqueeze(1)], dim=-1)
