@@ -461,6 +461,12 @@ int sbk_w2v_conv0_f32(const float* wav, const float* wstat, const float* w, cons
  * any T; x and w 16-byte aligned; y may be a view but not x. */
 int sbk_w2v_posconv_f32(const float* x, const int32_t* key_len, const float* w, const float* bias, const float* gamma,
                         const float* beta, float eps, float* y, int B, int T, int d, int G, int k, sbk_stream_t stream);
+/* The same with the per-group product on the bf16 matrix cores (precision "bf16"; additive entry): w_bf16 [d, Kp] holds the bf16
+ * bit patterns of w, every row zero-padded from k * d/G to Kp = the next multiple of 32.  xm and w enter the product rounded to
+ * bf16 (nearest even); accumulation, bias, GELU, the residual (from the unrounded xm), the LayerNorm and y are fp32. */
+int sbk_w2v_posconv_bf16(const float* x, const int32_t* key_len, const void* w_bf16, int Kp, const float* bias,
+                         const float* gamma, const float* beta, float eps, float* y, int B, int T, int d, int G, int k,
+                         sbk_stream_t stream);
 
 /* The wrapper's output_norm: y[r] = (x[r] - mean_r) / sqrt(var_r + eps) over the n values of each of `rows` rows (an utterance's
  * whole [T', d] block; biased variance, no affine).  y may be x. */
@@ -481,6 +487,12 @@ int sbk_wavlm_attention_max_frames(void);
 int sbk_wavlm_attention_f32(const float* qkv, const float* x, const float* gate_w, const float* gate_b, const float* gate_const,
                             const float* tab, const int32_t* key_len, float* out, int B, int T, int H, int Dh, float scale,
                             sbk_stream_t stream);
+/* The same arguments, Dh = 64 only, both products on the bf16 matrix cores (precision "bf16"; additive entry): q * scale, k, v
+ * and the unnormalised probabilities are rounded to bf16 (nearest even) as matrix operands; the gate, the bias (added to the
+ * fp32 score tile, never rounded), the softmax statistics, the context accumulation and out are fp32. */
+int sbk_wavlm_attention_bf16(const float* qkv, const float* x, const float* gate_w, const float* gate_b, const float* gate_const,
+                             const float* tab, const int32_t* key_len, float* out, int B, int T, int H, int Dh, float scale,
+                             sbk_stream_t stream);
 
 /* ---- HyperMixing (csrc/hypermix.hip; additive entries, ABI 11 unchanged) -------------------------------------------------
  * The token mixer of the HyperConformer recipes (nnet/hypermixing.py: HyperMixing, untied, multi-head) with the LayerNorm

@@ -33,6 +33,11 @@ using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 __device__ __forceinline__ f32x16 mfma_32x32x16_bf16(bf16x8 a, bf16x8 b, f32x16 acc) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
 }
+// D(16x16) += A(16x32) * B(32x16), fp32 accumulate; lane l supplies row / column l&15 and the k block l>>4 (8 consecutive
+// k each); acc layout as for mfma_16x16x4.  For tiles whose width is a multiple of 16 but not of 32.
+__device__ __forceinline__ f32x4 mfma_16x16x32_bf16(bf16x8 a, bf16x8 b, f32x4 acc) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+}
 // fp32 -> bf16, round to nearest even: gfx950 converts in hardware (v_cvt_pk_bf16_f32, two values per instruction)
 __device__ __forceinline__ unsigned short f32_to_bf16(float f) { return __builtin_bit_cast(unsigned short, (__bf16)f); }
 __device__ __forceinline__ bf16x8 cvt_bf16x8(const float (&x)[8]) {

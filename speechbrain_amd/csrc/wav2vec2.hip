@@ -32,6 +32,7 @@
 // With (gamma, beta) the LayerNorm over d follows as a second launch, in place (a row needs all G groups).
 #include "act.h"
 #include "common.h"
+#include "kernel_util.h"
 
 namespace {
 
@@ -401,6 +402,112 @@ __global__ void __launch_bounds__(256) w2v_posconv_kernel(const float* __restric
   }
 }
 
+// The same convolution with the per-group product on v_mfma_f32_16x16x32_bf16 (the opt-in precision "bf16"; 16-wide tiles
+// because cg = 48 is a multiple of 16 and not of 32).  The masked halo is staged as bf16 (nearest even), [frames][CG] with a
+// pitch of CG + 8: for output frame t the contraction index kk = tap * CG + channel is the run of the halo that starts at
+// row t -- element kk sits at row t + kk / CG, column kk % CG -- and as CG is a multiple of 8, a lane's 8 consecutive kk
+// are ONE 16-byte LDS read at every accepted CG.  (Without the 8 columns of pitch the run would be contiguous, t * CG + kk,
+// but the 16 frames of an A operand would then lie 32 .. 128 bytes apart and share 16-byte bank groups; with it the rows
+// lie (CG + 8) / 8 = 3, 5, 7 or 9 groups apart, all odd: 16 frames, 16 different groups.)  wb is the bf16 image of the
+// tap-major filter, [d][Kp] with the contraction length k * CG zero-padded to Kp, a multiple of the instruction's K step 32;
+// the steps of the padded tail read A from the zeroed row behind the halo.  A wave = (frame half, half of the K steps that
+// touch any frame of [0, klen)), 2 x CT accumulator tiles; the B operand is one 16-byte load per lane and tile from global
+// memory / L2, requested one step ahead.  fp32 accumulation (one chain per K half: its rounding is 2^-15 of the operand
+// rounding); bias, GELU and the residual in fp32, the residual from the UNROUNDED masked x.
+template <int CT>
+__global__ void __launch_bounds__(256) w2v_posconv_bf16_kernel(const float* __restrict__ x, const int32_t* __restrict__ key_len,
+                                                               const unsigned short* __restrict__ wb,
+                                                               const float* __restrict__ bias, float* __restrict__ y, int T,
+                                                               int d, int k, int Kp) {
+  using sbk::bf16x8;
+  constexpr int CG = 16 * CT, P = CG + 8;
+  __shared__ __attribute__((aligned(16))) unsigned short halo[(kPRows + 1) * (kPMaxCg + 8)];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = sbk::uniform(tid >> 6);
+  const int fh = wave & 1, kh = wave >> 1;  // frame half, K half
+  const int tile = blockIdx.x, g = blockIdx.y, b = blockIdx.z;
+  const int t0 = tile * kPT, pad = k / 2;
+  int klen = T;
+  if (key_len) klen = min(max(key_len[b], 0), T);
+  const float* xb = x + (size_t)b * T * d + g * CG;
+  // ---- stage the masked halo: row r holds frame t0 - pad + r of THIS utterance, zeros outside [0, klen) and in row `rows`
+  const int rows = kPT + k - 1;
+  for (int e = tid; e < (rows + 1) * (CG / 8); e += 256) {
+    const int rr = e / (CG / 8), q = e - rr * (CG / 8);
+    const int f = t0 - pad + rr;
+    float v[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (rr < rows && f >= 0 && f < klen) sbk::load_run<8>(v, xb + (size_t)f * d + 8 * q);
+    *reinterpret_cast<bf16x8*>(halo + rr * P + 8 * q) = sbk::cvt_bf16x8(v);
+  }
+  __syncthreads();
+  const int vlo = max(pad - t0, 0), vhi = min(klen - t0 + pad, rows);  // halo rows that hold frames of [0, klen)
+  const int row = lane & 15, ks = lane >> 4;
+  const int rb = fh * 32;  // this wave's first output frame inside the tile
+  const bool live = t0 + rb < T;  // (wave-uniform) a ragged last tile: no output frame of this wave exists
+  // K step q contracts kk = 32q .. 32q + 31: taps 32q / CG .. (32q + 31) / CG, halo rows rb + tap .. rb + tap + 31 of this
+  // wave.  The steps that touch a row of [vlo, vhi) are a contiguous range [qb, qe); this wave takes its half kh of it.
+  const int nq = Kp / 32;
+  int qb = 0, qe = nq;
+  while (qb < qe && rb + (32 * qb + 31) / CG + 32 <= vlo) ++qb;
+  while (qe > qb && rb + (32 * (qe - 1)) / CG >= vhi) --qe;
+  const int qm = qb + (qe - qb + 1) / 2;
+  const int q0 = live ? (kh ? qm : qb) : 0, q1 = live ? (kh ? qe : qm) : 0;
+  sbk::f32x4 acc[2][CT];
+#pragma unroll
+  for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) acc[rt][ct] = sbk::f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  const unsigned short* wl = wb + ((size_t)g * CG + row) * Kp + 8 * ks;
+  auto load_b = [&](int q, bf16x8 (&b8)[CT]) {
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) b8[ct] = *reinterpret_cast<const bf16x8*>(wl + (size_t)ct * 16 * Kp + 32 * q);
+  };
+  bf16x8 bn[CT];
+  if (q0 < q1) load_b(q0, bn);
+  for (int q = q0; q < q1; ++q) {
+    bf16x8 b8[CT], a8[2];
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) b8[ct] = bn[ct];
+    if (q + 1 < q1) load_b(q + 1, bn);
+    const int kk = 32 * q + 8 * ks, j = kk / CG, c = kk - j * CG;  // (j <= k: row rb + 31 + k is the zeroed row at most)
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt) a8[rt] = *reinterpret_cast<const bf16x8*>(halo + (rb + 16 * rt + row + j) * P + c);
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) acc[rt][ct] = sbk::mfma_16x16x32_bf16(a8[rt], b8[ct], acc[rt][ct]);
+  }
+  // ---- the sum of the two K halves goes through the halo's memory: [2 CT 4 values][frame half][64 lanes]
+  // acc[rt][ct][r] is frame rb + 16 rt + 4 ks + r, channel 16 ct + row
+  __syncthreads();
+  float* part = reinterpret_cast<float*>(halo);
+  if (kh == 1) {
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) part[((rt * CT + ct) * 4 + r) * 128 + fh * 64 + lane] = acc[rt][ct][r];
+  }
+  __syncthreads();
+  if (kh == 0 && live) {
+    float* yb = y + (size_t)b * T * d + g * CG;
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) {
+        const int c = 16 * ct + row;
+        const float bv = bias[g * CG + c];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int t = t0 + rb + 16 * rt + 4 * ks + r;
+          const float v = acc[rt][ct][r] + part[((rt * CT + ct) * 4 + r) * 128 + fh * 64 + lane] + bv;
+          if (t < T) yb[(size_t)t * d + c] = (t < klen ? xb[(size_t)t * d + c] : 0.0f) + sbk::gelu_erf(v);
+        }
+      }
+  }
+}
+
 // LayerNorm over the d channels of every row, IN PLACE (one wave per row; a lane re-writes only what it read itself)
 __global__ void __launch_bounds__(256) w2v_row_ln_kernel(float* y, const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, int rows, int d, float eps) {
@@ -527,9 +634,9 @@ extern "C" int sbk_w2v_conv0_f32(const float* wav, const float* wstat, const flo
   return sbk::launch_status("sbk_w2v_conv0_f32");
 }
 
-extern "C" int sbk_w2v_posconv_f32(const float* x, const int32_t* key_len, const float* w, const float* bias, const float* gamma,
-                                   const float* beta, float eps, float* y, int B, int T, int d, int G, int k,
-                                   sbk_stream_t stream) {
+// w: the fp32 filter [d][k*cg] (Kp = 0), or its bf16 image [d][Kp] for the bf16 kernel
+static int w2v_posconv(const float* x, const int32_t* key_len, const void* w, int Kp, const float* bias, const float* gamma,
+                       const float* beta, float eps, float* y, int B, int T, int d, int G, int k, sbk_stream_t stream) {
   SBK_REQUIRE(B >= 0 && B <= 65535 && T >= 0 && d > 0 && G > 0 && G <= 65535 && d % G == 0, "w2v_posconv: bad shape B=%d T=%d d=%d G=%d",
               B, T, d, G);
   const int cg = d / G;
@@ -541,22 +648,46 @@ extern "C" int sbk_w2v_posconv_f32(const float* x, const int32_t* key_len, const
   SBK_REQUIRE(sbk::aligned16(x) && sbk::aligned16(w), "w2v_posconv: x and w must be 16-byte aligned");
   SBK_REQUIRE(x != y, "w2v_posconv: in place (a workgroup reads frames its neighbours write)");
   hipStream_t st = sbk::as_stream(stream);
-  {
-    const double n = (double)B * T * d;
-    sbk::ProfScope prof("w2v_posconv", 2.0 * n * cg * k, 8.0 * n + 4.0 * (double)d * cg * k, st);
-    dim3 grid(sbk::cdiv(T, kPT), G, B), block(256);
+  const double n = (double)B * T * d;
+  dim3 grid(sbk::cdiv(T, kPT), G, B), block(256);
+  if (Kp) {
+    SBK_REQUIRE(Kp == (k * cg + 31) / 32 * 32, "w2v_posconv_bf16: image pitch %d, not %d taps x %d channels padded to 32", Kp, k, cg);
+    const unsigned short* wb = static_cast<const unsigned short*>(w);
+    sbk::ProfScope prof("w2v_posconv_bf16", 2.0 * n * cg * k, 8.0 * n + 2.0 * (double)d * Kp, st);
     switch (cg) {
-      case 16: SBK_LAUNCH((w2v_posconv_kernel<1>), grid, block, 0, st, x, key_len, w, bias, y, T, d, k); break;
-      case 32: SBK_LAUNCH((w2v_posconv_kernel<2>), grid, block, 0, st, x, key_len, w, bias, y, T, d, k); break;
-      case 48: SBK_LAUNCH((w2v_posconv_kernel<3>), grid, block, 0, st, x, key_len, w, bias, y, T, d, k); break;
-      default: SBK_LAUNCH((w2v_posconv_kernel<4>), grid, block, 0, st, x, key_len, w, bias, y, T, d, k); break;
+      case 16: SBK_LAUNCH((w2v_posconv_bf16_kernel<1>), grid, block, 0, st, x, key_len, wb, bias, y, T, d, k, Kp); break;
+      case 32: SBK_LAUNCH((w2v_posconv_bf16_kernel<2>), grid, block, 0, st, x, key_len, wb, bias, y, T, d, k, Kp); break;
+      case 48: SBK_LAUNCH((w2v_posconv_bf16_kernel<3>), grid, block, 0, st, x, key_len, wb, bias, y, T, d, k, Kp); break;
+      default: SBK_LAUNCH((w2v_posconv_bf16_kernel<4>), grid, block, 0, st, x, key_len, wb, bias, y, T, d, k, Kp); break;
+    }
+  } else {
+    const float* wf = static_cast<const float*>(w);
+    sbk::ProfScope prof("w2v_posconv", 2.0 * n * cg * k, 8.0 * n + 4.0 * (double)d * cg * k, st);
+    switch (cg) {
+      case 16: SBK_LAUNCH((w2v_posconv_kernel<1>), grid, block, 0, st, x, key_len, wf, bias, y, T, d, k); break;
+      case 32: SBK_LAUNCH((w2v_posconv_kernel<2>), grid, block, 0, st, x, key_len, wf, bias, y, T, d, k); break;
+      case 48: SBK_LAUNCH((w2v_posconv_kernel<3>), grid, block, 0, st, x, key_len, wf, bias, y, T, d, k); break;
+      default: SBK_LAUNCH((w2v_posconv_kernel<4>), grid, block, 0, st, x, key_len, wf, bias, y, T, d, k); break;
     }
   }
   if (gamma) {
     sbk::ProfScope prof("w2v_posconv_ln", 8.0 * B * T * d, 8.0 * B * T * d, st);
     SBK_LAUNCH(w2v_row_ln_kernel, dim3(sbk::cdiv(B * T, 4)), dim3(256), 0, st, y, gamma, beta, B * T, d, eps);
   }
-  return sbk::launch_status("sbk_w2v_posconv_f32");
+  return sbk::launch_status(Kp ? "sbk_w2v_posconv_bf16" : "sbk_w2v_posconv_f32");
+}
+
+extern "C" int sbk_w2v_posconv_f32(const float* x, const int32_t* key_len, const float* w, const float* bias, const float* gamma,
+                                   const float* beta, float eps, float* y, int B, int T, int d, int G, int k,
+                                   sbk_stream_t stream) {
+  return w2v_posconv(x, key_len, w, 0, bias, gamma, beta, eps, y, B, T, d, G, k, stream);
+}
+
+extern "C" int sbk_w2v_posconv_bf16(const float* x, const int32_t* key_len, const void* w_bf16, int Kp, const float* bias,
+                                    const float* gamma, const float* beta, float eps, float* y, int B, int T, int d, int G,
+                                    int k, sbk_stream_t stream) {
+  SBK_REQUIRE(Kp > 0, "w2v_posconv_bf16: image pitch %d", Kp);
+  return w2v_posconv(x, key_len, w_bf16, Kp, bias, gamma, beta, eps, y, B, T, d, G, k, stream);
 }
 
 extern "C" int sbk_w2v_utt_norm_f32(const float* x, float* y, int rows, long n, float eps, sbk_stream_t stream) {

@@ -1,5 +1,5 @@
 // WavLM self-attention: scaled-dot-product attention with the GATED RELATIVE-POSITION BIAS fused in
-//                                                      (sbk_wavlm_attention_f32)
+//                                                      (sbk_wavlm_attention_f32, sbk_wavlm_attention_bf16)
 //   p      = gate_w x[b,i,h*Dh:(h+1)*Dh] + gate_b                      (8 values, gru_rel_pos_linear, shared by the heads)
 //   ga, gb = sigmoid(p0+p1+p2+p3), sigmoid(p4+p5+p6+p7)
 //   gate   = ga * (gb * gate_const[h] - 1) + 2
@@ -167,13 +167,186 @@ __global__ void __launch_bounds__(256, 2) wavlm_flash_t_kernel(WavlmArgs a) {
   }
 }
 
+// The same walk with both products on v_mfma_f32_32x32x16_bf16 (head_dim 64; the opt-in precision "bf16"): the walk of
+// rope_flash_t_bf16_kernel (csrc/relpos_attn.hip) with the gate, the staged table row and the bias of the kernel above.
+// q * scale, k, v and the unnormalised probabilities are rounded to bf16 (nearest even) on their way into the matrix
+// operands; the score tile, the bias added to it, the softmax statistics (the normaliser sums the UNROUNDED probabilities)
+// and the context stay fp32.  The bias never passes through bf16: it is one fp32 fused multiply-add per score either way,
+// and it is the term that makes this WavLM.  K and V go from global memory / L2 straight into registers, as in the fp32
+// kernel: MFMA step t contracts channels 16t + 8*half .. + 7 of a q / k row (two float4 loads), step s of the context
+// product the 8 keys of the accumulator registers 8s .. 8s + 7.  Four instructions per score tile and four per context
+// update instead of 32 + 32.
+__global__ void __launch_bounds__(256, 2) wavlm_flash_t_bf16_kernel(WavlmArgs a) {
+  constexpr int DH = 64, DH2 = 32;
+  using sbk::bf16x8;
+  SBK_DYN_LDS(float, tab_s);  // [2T - 1 + kTabPad]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int jl = lane & 31, half = lane >> 5;
+  const int i0 = (blockIdx.x * 4 + wave) * 32, h = blockIdx.y, b = blockIdx.z;
+  const int T = a.T, d = a.H * DH;
+  {
+    const int n = 2 * T - 1;
+    const float* row = a.tab + (size_t)h * n;
+    for (int e = tid; e < n + kTabPad; e += 256) tab_s[e] = e < n ? row[e] : 0.0f;
+  }
+  __syncthreads();
+  if (i0 >= T) return;  // (a wave without queries: after the workgroup's only barrier)
+  const size_t row3 = (size_t)3 * d;
+  const float* qkv_b = a.qkv + (size_t)b * T * row3 + (size_t)h * 3 * DH;
+  const int qrow = min(i0 + jl, T - 1);
+
+  float gate;
+  {
+    float xr[DH2];
+    load_run<DH2>(xr, a.x + ((size_t)b * T + qrow) * d + h * DH + half * DH2);
+    float p[8];
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+      float w[DH2];
+      load_run<DH2>(w, a.gate_w + g * DH + half * DH2);
+      float s = 0.0f;
+#pragma unroll
+      for (int c = 0; c < DH2; ++c) s = fmaf(w[c], xr[c], s);
+      p[g] = s + sbk::shfl_xor(s, 32) + a.gate_b[g];
+    }
+    const float ga = sbk::sigmoid((p[0] + p[1]) + (p[2] + p[3])), gb = sbk::sigmoid((p[4] + p[5]) + (p[6] + p[7]));
+    gate = ga * (gb * a.gate_const[h] - 1.0f) + 2.0f;
+  }
+
+  auto load_chunks = [&](const float* row, float scale, bf16x8 (&dst)[4]) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      float x[8];
+      load_run<8>(x, row + 16 * t + 8 * half);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) x[e] *= scale;
+      dst[t] = sbk::cvt_bf16x8(x);
+    }
+  };
+  bf16x8 qb[4];
+  load_chunks(qkv_b + (size_t)qrow * row3, a.scale, qb);
+
+  int klen = T;
+  if (a.key_len) klen = min(max(a.key_len[b], 1), T);
+  const int nkt = (klen + 31) / 32;
+  const float* tq = tab_s + (T - 1 - qrow) + 4 * half;  // (as above)
+  float m_run = -INFINITY, l_run = 0.0f;
+  f32x16 o[2];
+#pragma unroll
+  for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[ct][r] = 0.0f;
+
+  for (int kt = 0; kt < nkt; ++kt) {
+    const int j0 = kt * 32;
+    bf16x8 kb[4];
+    load_chunks(qkv_b + (size_t)min(j0 + jl, T - 1) * row3 + DH, 1.0f, kb);
+    f32x16 acc;  // S^T: row = key (r&3) + 8(r>>2) + 4*half of the tile, column = query jl
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc = sbk::mfma_32x32x16_bf16(kb[t], qb[t], acc);
+    // V^T operands, requested before the softmax: step s contracts the keys of the accumulator registers 8s .. 8s + 7
+    bf16x8 vb[2][2];
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) {
+      const float* vbase = qkv_b + 2 * DH + ct * 32 + jl;
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        float x[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const int r = 8 * s + e;
+          x[e] = vbase[(size_t)min(j0 + (r & 3) + 8 * (r >> 2) + 4 * half, T - 1) * row3];
+        }
+        vb[ct][s] = sbk::cvt_bf16x8(x);
+      }
+    }
+    float mx = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int ko = (r & 3) + 8 * (r >> 2);  // (j0 + ko + 4*half <= nkt*32 - 1 <= T + 30: inside the padded row)
+      acc[r] = fmaf(gate, tq[j0 + ko], acc[r]);
+      if (j0 + ko + 4 * half >= klen) acc[r] = -INFINITY;
+      mx = fmaxf(mx, acc[r]);
+    }
+    mx = fmaxf(mx, sbk::shfl_xor(mx, 32));
+    const float m_new = fmaxf(m_run, mx);
+    const float alpha = m_new == -INFINITY ? 1.0f : expf(m_run - m_new);
+    float sum = 0.0f;
+    bf16x8 pb[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      float x[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int r = 8 * s + e;
+        x[e] = acc[r] == -INFINITY ? 0.0f : expf(acc[r] - m_new);
+        sum += x[e];
+      }
+      pb[s] = sbk::cvt_bf16x8(x);
+    }
+    sum += sbk::shfl_xor(sum, 32);
+    l_run = l_run * alpha + sum;
+    m_run = m_new;
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) o[ct][r] *= alpha;
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct) o[ct] = sbk::mfma_32x32x16_bf16(vb[ct][s], pb[s], o[ct]);
+  }
+  // O^T: column = this lane's query, row = channel (r&3) + 8(r>>2) + 4*half + 32*ct
+  if (i0 + jl < T) {
+    const float inv = l_run > 0.0f ? 1.0f / l_run : 0.0f;
+    float* orow = a.out + ((size_t)b * T + i0 + jl) * d + h * DH;
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) orow[ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * half] = o[ct][r] * inv;
+  }
+}
+
+// DH = 0: the bf16 kernel (head_dim 64)
 template <int DH>
 int launch_wavlm(const WavlmArgs& a, hipStream_t st) {
+  constexpr int Dh = DH ? DH : 64;
   const size_t lds = (size_t)(2 * a.T - 1 + kTabPad) * sizeof(float);
-  sbk::ProfScope prof("wavlm_attention", 4.0 * a.B * a.H * (double)a.T * a.T * DH + 2.0 * a.B * a.H * (double)a.T * a.T,
-                      4.0 * a.B * a.T * (5.0 * a.H * DH) + 4.0 * (2.0 * a.T - 1) * a.H, st);
-  SBK_LAUNCH((wavlm_flash_t_kernel<DH>), dim3((a.T + 127) / 128, a.H, a.B), dim3(256), lds, st, a);
-  return sbk::launch_status("sbk_wavlm_attention_f32");
+  sbk::ProfScope prof(DH ? "wavlm_attention" : "wavlm_attention_bf16",
+                      4.0 * a.B * a.H * (double)a.T * a.T * Dh + 2.0 * a.B * a.H * (double)a.T * a.T,
+                      4.0 * a.B * a.T * (5.0 * a.H * Dh) + 4.0 * (2.0 * a.T - 1) * a.H, st);
+  const dim3 grid((a.T + 127) / 128, a.H, a.B);
+  if constexpr (DH == 0) {
+    SBK_LAUNCH(wavlm_flash_t_bf16_kernel, grid, dim3(256), lds, st, a);
+    return sbk::launch_status("sbk_wavlm_attention_bf16");
+  } else {
+    SBK_LAUNCH((wavlm_flash_t_kernel<DH>), grid, dim3(256), lds, st, a);
+    return sbk::launch_status("sbk_wavlm_attention_f32");
+  }
+}
+
+int wavlm_attention(const float* qkv, const float* x, const float* gate_w, const float* gate_b, const float* gate_const,
+                    const float* tab, const int32_t* key_len, float* out, int B, int T, int H, int Dh, float scale,
+                    sbk_stream_t stream, bool bf16) {
+  SBK_REQUIRE(B >= 0 && T >= 0 && H > 0 && Dh > 0, "wavlm_attention: bad shape");
+  if (B == 0 || T == 0) return 0;  // empty batch: nothing to launch, the data pointers may be NULL
+  SBK_REQUIRE(qkv && x && gate_w && gate_b && gate_const && tab && out, "wavlm_attention: null operand");
+  if (bf16) SBK_REQUIRE(Dh == 64, "wavlm_attention_bf16: head_dim %d not instantiated (64)", Dh);
+  SBK_REQUIRE(Dh == 64 || Dh == 32 || Dh == 16, "wavlm_attention: head_dim %d not instantiated (16,32,64)", Dh);
+  SBK_REQUIRE(T <= kMaxT, "wavlm_attention: T=%d frames: the head's bias table (2T-1 floats) is staged in 64 KiB of LDS, T <= %d",
+              T, kMaxT);
+  SBK_REQUIRE(sbk::aligned16(qkv) && sbk::aligned16(x) && sbk::aligned16(gate_w),
+              "wavlm_attention: qkv, x and gate_w must be 16-byte aligned");
+  const WavlmArgs a{qkv, x, gate_w, gate_b, gate_const, tab, key_len, out, B, T, H, scale};
+  const hipStream_t st = sbk::as_stream(stream);
+  if (bf16) return launch_wavlm<0>(a, st);
+  switch (Dh) {
+    case 64: return launch_wavlm<64>(a, st);
+    case 32: return launch_wavlm<32>(a, st);
+    default: return launch_wavlm<16>(a, st);
+  }
 }
 
 }  // namespace
@@ -183,19 +356,11 @@ extern "C" int sbk_wavlm_attention_max_frames(void) { return kMaxT; }
 extern "C" int sbk_wavlm_attention_f32(const float* qkv, const float* x, const float* gate_w, const float* gate_b,
                                        const float* gate_const, const float* tab, const int32_t* key_len, float* out, int B,
                                        int T, int H, int Dh, float scale, sbk_stream_t stream) {
-  SBK_REQUIRE(B >= 0 && T >= 0 && H > 0 && Dh > 0, "wavlm_attention: bad shape");
-  if (B == 0 || T == 0) return 0;  // empty batch: nothing to launch, the data pointers may be NULL
-  SBK_REQUIRE(qkv && x && gate_w && gate_b && gate_const && tab && out, "wavlm_attention: null operand");
-  SBK_REQUIRE(Dh == 64 || Dh == 32 || Dh == 16, "wavlm_attention: head_dim %d not instantiated (16,32,64)", Dh);
-  SBK_REQUIRE(T <= kMaxT, "wavlm_attention: T=%d frames: the head's bias table (2T-1 floats) is staged in 64 KiB of LDS, T <= %d",
-              T, kMaxT);
-  SBK_REQUIRE(sbk::aligned16(qkv) && sbk::aligned16(x) && sbk::aligned16(gate_w),
-              "wavlm_attention: qkv, x and gate_w must be 16-byte aligned");
-  const WavlmArgs a{qkv, x, gate_w, gate_b, gate_const, tab, key_len, out, B, T, H, scale};
-  const hipStream_t st = sbk::as_stream(stream);
-  switch (Dh) {
-    case 64: return launch_wavlm<64>(a, st);
-    case 32: return launch_wavlm<32>(a, st);
-    default: return launch_wavlm<16>(a, st);
-  }
+  return wavlm_attention(qkv, x, gate_w, gate_b, gate_const, tab, key_len, out, B, T, H, Dh, scale, stream, false);
+}
+
+extern "C" int sbk_wavlm_attention_bf16(const float* qkv, const float* x, const float* gate_w, const float* gate_b,
+                                        const float* gate_const, const float* tab, const int32_t* key_len, float* out, int B,
+                                        int T, int H, int Dh, float scale, sbk_stream_t stream) {
+  return wavlm_attention(qkv, x, gate_w, gate_b, gate_const, tab, key_len, out, B, T, H, Dh, scale, stream, true);
 }

@@ -125,9 +125,12 @@ class EncoderASR(Pretrained):
     def encode_batch(self, wavs, wav_lens):
         """The log-probabilities of the CTC head [B,T,V].  As in EncoderDecoderASR.encode_batch, only the Transformer
         encoder runs under the interface's precision (fp32 = the parity path): the children of the encoder container
-        that are an ``EncoderWrapper`` / ``TransformerASR``; the feature front-end, the CNN and the CTC head stay fp32.
+        that are an ``EncoderWrapper`` / ``TransformerASR`` and, under "bf16", a ``Wav2Vec2`` / ``HuBERT`` / ``WavLM`` wrapper
+        (its contractions, attention and positional convolution; its waveform convolution, statistics and LayerNorms have
+        no reduced form); the feature front-end, the CNN and the CTC head stay fp32.
         (An encoder that is not a container runs under the precision as a whole.)"""
         from speechbrain_amd import native
+        from speechbrain_amd.integrations.huggingface.wav2vec2 import Wav2Vec2
         from speechbrain_amd.lobes.models.transformer.TransformerASR import EncoderWrapper, TransformerASR
         from speechbrain_amd.nnet.containers import LengthsCapableSequential, Sequential
 
@@ -137,9 +140,12 @@ class EncoderASR(Pretrained):
         if self.eval_precision == "fp32" or not isinstance(enc, Sequential):
             with native.precision_scope(self.eval_precision):
                 return enc(wavs, wav_lens)
+        scoped = (EncoderWrapper, TransformerASR)
+        if self.eval_precision == "bf16":  # the self-supervised encoders (Wav2Vec2 and its subclasses HuBERT, WavLM): bf16 only
+            scoped += (Wav2Vec2,)
         x = wavs
         for name, layer in enc.items():  # LengthsCapableSequential.forward / Sequential.forward, child by child
-            p = self.eval_precision if isinstance(layer, (EncoderWrapper, TransformerASR)) else "fp32"
+            p = self.eval_precision if isinstance(layer, scoped) else "fp32"
             with native.precision_scope(p):
                 if isinstance(enc, LengthsCapableSequential) and name in enc.length_layers:
                     x = layer(x, lengths=wav_lens)

@@ -210,9 +210,11 @@ def _declare(lib):
         "sbk_w2v_conv0_stats_f32": ([p, p, p, i, f, f, p, p, p, ctypes.c_size_t, i, i, i, i, i, p], c_int),
         "sbk_w2v_conv0_f32": ([p, p, p, p, i, p, p, p, f, p, i, i, i, i, i, p], c_int),
         "sbk_w2v_posconv_f32": ([p, p, p, p, p, p, f, p, i, i, i, i, i, p], c_int),
+        "sbk_w2v_posconv_bf16": ([p, p, p, i, p, p, p, f, p, i, i, i, i, i, p], c_int),
         "sbk_w2v_utt_norm_f32": ([p, p, i, ctypes.c_long, f, p], c_int),
         "sbk_wavlm_attention_max_frames": ([], c_int),
         "sbk_wavlm_attention_f32": ([p, p, p, p, p, p, p, p, i, i, i, i, f, p], c_int),
+        "sbk_wavlm_attention_bf16": ([p, p, p, p, p, p, p, p, i, i, i, i, f, p], c_int),
         "sbk_hypermix_split_frames": ([], c_int),
         "sbk_hypermix_workspace_bytes": ([i, i, i, i], ctypes.c_size_t),
         "sbk_hypermix_f32": ([p] * 13 + [f, p, p, p, ctypes.c_size_t, i, i, i, i, i, p], c_int),
@@ -460,7 +462,8 @@ _tls = threading.local()
 
 def precision() -> str:
     """"fp32" (parity path, default) or an opt-in reduced-precision operand type for the large GEMMs, all with fp32
-    accumulation: "bf16" (also the bf16 attention kernel), "fp16", "fp8" (e4m3, per-tensor scales)."""
+    accumulation: "bf16" (also the bf16 attention kernels -- rope_attention and wavlm_attention at head dim 64 -- and the
+    positional convolution w2v_posconv), "fp16", "fp8" (e4m3, per-tensor scales)."""
     return getattr(_tls, "precision", "fp32")
 
 
@@ -815,6 +818,10 @@ def _make_image(w: torch.Tensor, kind: str):
         N, K = w2.shape
         out = torch.empty(((N + 63) // 64) * 64 * K * 3, dtype=torch.int16, device=w.device)
         _chk(lib.sbk_split_x3p(_p(w2), K, _p(out), N, K, _stream(w2)), "sbk_split_x3p")
+    elif kind == "bf16k32":  # bf16 with every row zero-padded to a multiple of 32 (sbk_w2v_posconv_bf16's K step)
+        w2 = torch.nn.functional.pad(w2, (0, -w2.shape[1] % 32))
+        out = torch.empty(w2.shape, dtype=torch.int16, device=w.device)
+        _chk(lib.sbk_f32_to_bf16(_p(w2), _p(out), w2.numel(), _stream(w2)), "sbk_f32_to_bf16")
     else:
         out = torch.empty(w2.shape, dtype=torch.int16, device=w.device)
         fn = lib.sbk_f32_to_bf16 if kind == "bf16" else lib.sbk_f32_to_f16
@@ -824,6 +831,7 @@ def _make_image(w: torch.Tensor, kind: str):
 
 def lp_weight(w: torch.Tensor, kind: str = "bf16"):
     """The reduced-precision image of a weight matrix ("bf16" / "fp16": int16 bits; "fp8": (uint8 e4m3 bits, w_scale);
+    "bf16k32": bf16 bits with every row zero-padded to a multiple of 32, the filter image of sbk_w2v_posconv_bf16;
     "x3": the exact three-piece bf16 split [N, K/32, 3, 32] of sbk_split_bf16x3 -- not reduced: the pieces sum to w),
     cached for the lifetime of THAT tensor object: the entry holds a weak reference to its source and is used only while
     ``ref() is w`` and the version counter is unchanged (a freed model's addresses are commonly handed to the next
@@ -1379,6 +1387,11 @@ def w2v_posconv(x, key_len, w, bias, groups, ksize, ln=None, out=None):
     if not (1 <= ksize <= W2V_POSCONV_MAX_KERNEL) or tuple(w.shape) != (d, ksize * (d // groups)):
         raise SbkError(f"w2v_posconv: {ksize} taps (1..{W2V_POSCONV_MAX_KERNEL}) with a weight {tuple(w.shape)}")
     y = out if out is not None else torch.empty(B, T, d, dtype=torch.float32, device=x.device)
+    if precision() == "bf16":  # opt-in: the per-group product on the bf16 matrix cores, the filter's image made once
+        wb = lp_weight(w, "bf16k32")
+        _chk(lib.sbk_w2v_posconv_bf16(_p(x), _p(key_len), _p(wb), wb.shape[1], _p(bias), _p(gamma), _p(beta), float(eps), _p(y),
+                                      B, T, d, groups, ksize, _stream(x)), "sbk_w2v_posconv_bf16")
+        return y
     _chk(lib.sbk_w2v_posconv_f32(_p(x), _p(key_len), _p(w), _p(bias), _p(gamma), _p(beta), float(eps), _p(y), B, T, d, groups,
                                  ksize, _stream(x)), "sbk_w2v_posconv_f32")
     return y
@@ -1422,8 +1435,10 @@ def wavlm_attention(qkv, x, gate_w, gate_b, gate_const, tab, key_len, H, scale, 
     _f32(gate_b), _f32(gate_const)
     if out is None:
         out = torch.empty(B, T, d, dtype=torch.float32, device=qkv.device)
-    _chk(lib.sbk_wavlm_attention_f32(_p(qkv), _p(x), _p(gate_w), _p(gate_b), _p(gate_const), _p(tab), _p(key_len), _p(out),
-                                     B, T, H, Dh, float(scale), _stream(qkv)), "sbk_wavlm_attention_f32")
+    # opt-in: both products on the bf16 matrix cores at head dim 64 (16 / 32 keep the fp32 kernel, as rope_attention does)
+    name = "sbk_wavlm_attention_bf16" if precision() == "bf16" and Dh == 64 else "sbk_wavlm_attention_f32"
+    _chk(getattr(lib, name)(_p(qkv), _p(x), _p(gate_w), _p(gate_b), _p(gate_const), _p(tab), _p(key_len), _p(out),
+                            B, T, H, Dh, float(scale), _stream(qkv)), name)
     return out
 
 

@@ -360,6 +360,25 @@ static inline f32x4 mfma_16x16x4(float a, float b, f32x4 acc) {
   sbk_emu::wave_barrier();
   return acc;
 }
+static inline f32x4 mfma_16x16x32_bf16(bf16x8 a, bf16x8 b, f32x4 acc) {
+  const int l = sbk_emu::cur().lane;
+  float* A = sbk_emu::wave_buf(0);  // [lane][8]
+  float* B = sbk_emu::wave_buf(1);
+  for (int e = 0; e < 8; ++e) {
+    A[l * 8 + e] = bf16_to_f32_(a.v[e]);
+    B[l * 8 + e] = bf16_to_f32_(b.v[e]);
+  }
+  sbk_emu::wave_barrier();
+  for (int r = 0; r < 4; ++r) {
+    const int row = (l >> 4) * 4 + r, col = l & 15;
+    float c = acc[r];
+    for (int kb = 0; kb < 4; ++kb)
+      for (int e = 0; e < 8; ++e) c = fmaf(A[(row + 16 * kb) * 8 + e], B[(col + 16 * kb) * 8 + e], c);
+    acc[r] = c;
+  }
+  sbk_emu::wave_barrier();
+  return acc;
+}
 template <typename T>
 static inline T shfl_idx_(T v, int src) {
   const int l = sbk_emu::cur().lane;

@@ -8,9 +8,14 @@ profiler (HIP events), and in the same run the yardsticks the two new kernels ar
     device copy of the activation's size;
   * sbk_w2v_posconv_f32 should reach >= 0.25 of native.gemm_nt's rate on the plain [B*T' x cg*k] x [cg*k x cg] product.
 
+``--precision bf16`` runs the reduced-precision leg instead and records it under "bf16" of the same file: per shape
+sbk_w2v_posconv_bf16 next to sbk_w2v_posconv_f32 on the same input (alternating, each one's best of three), and the encoder
+under "fp32" and under "bf16".  Expectations recorded as met or missed (nothing is gated on them): the bf16 kernel is faster than
+the fp32 kernel in the same run; the encoder under bf16 is faster than under fp32.
+
 One JSON line per run, also written to profiles/wav2vec2_bench.json.  A job for a GPU visit.
 
-    python tools/wav2vec2_bench.py [--steps 5] [--warmup 2] [--shapes base,large]
+    python tools/wav2vec2_bench.py [--steps 5] [--warmup 2] [--shapes base,large] [--precision bf16]
 """
 import argparse
 import json
@@ -121,6 +126,50 @@ def run_shape(native, name, args):
     return res
 
 
+def met(ok):
+    return "met" if ok else "missed"
+
+
+def run_shape_bf16(native, name, args):
+    from speechbrain_amd.integrations.huggingface.wav2vec2 import Wav2Vec2
+
+    B, N = args.batch, int(args.seconds * 16000)
+    w = Wav2Vec2.from_config(SHAPES[name], normalize_wav=(name == "large"), output_norm=True, seed=3).to("cuda:0")
+    cfg, pc = w.model.config, w.model.encoder.pos_conv_embed.conv
+    wav = (0.3 * torch.randn(B, N, generator=torch.Generator().manual_seed(5))).cuda()
+    lens = torch.linspace(0.6, 1.0, B).cuda()
+    T, d = int(w.model.feat_lengths(N)), cfg["hidden_size"]
+    x = torch.randn(B, T, d, generator=torch.Generator().manual_seed(7)).cuda()
+    key_len = (torch.linspace(0.6, 1.0, B) * T).round().to(torch.int32).cuda()
+    y = torch.empty_like(x)
+    res = {"shape": name, "batch": B, "seconds": args.seconds, "frames": T, "d": d, "groups": pc.groups, "taps": pc.kernel_size}
+
+    def scoped(prec, fn):
+        def call():
+            with native.precision_scope(prec):
+                return fn()
+        return call
+
+    with torch.no_grad():
+        conv = lambda: native.w2v_posconv(x, key_len, pc.effective(), pc.bias, pc.groups, pc.kernel_size, out=y)  # noqa: E731
+        ms = {"fp32": [], "bf16": []}
+        for _ in range(3):  # alternate the two, keep each one's best of three: clock and cache state are shared
+            for prec in ms:
+                ms[prec].append(event_ms(scoped(prec, conv), 10 * args.steps, args.warmup))
+        res["posconv_f32_ms"], res["posconv_bf16_ms"] = round(min(ms["fp32"]), 4), round(min(ms["bf16"]), 4)
+        res["posconv_speedup"] = round(min(ms["fp32"]) / min(ms["bf16"]), 2)
+        for prec in ("fp32", "bf16"):
+            run = scoped(prec, lambda: w(wav, lens))
+            res[f"encoder_{prec}_p50_ms"] = round(p50_ms(run, args.steps, args.warmup), 3)
+            rep = profiled(native, run, args.steps)
+            res[f"encoder_{prec}_kernels_ms"] = {k_: round(v, 4) for k_, v in sorted(rep.items(), key=lambda kv: -kv[1])}
+        res["encoder_speedup"] = round(res["encoder_fp32_p50_ms"] / res["encoder_bf16_p50_ms"], 2)
+        res["audio_sec_per_sec_bf16"] = round(B * args.seconds / (res["encoder_bf16_p50_ms"] / 1e3), 1)
+    res["expectations"] = {"posconv bf16 faster than fp32 in the same run": met(res["posconv_speedup"] > 1.0),
+                           "encoder under bf16 faster than under fp32": met(res["encoder_speedup"] > 1.0)}
+    return res
+
+
 def main():
     from speechbrain_amd import native
 
@@ -130,8 +179,21 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--shapes", default="base,large")
+    ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"])
     args = ap.parse_args()
     native.load()
+    path = os.path.join(ROOT, "profiles", "wav2vec2_bench.json")
+    if args.precision == "bf16":  # the reduced-precision leg: merged into the recorded result, shape by shape
+        with open(path) as f:
+            res = json.loads(f.read())
+        leg = {r["shape"]: r for r in res.get("bf16", [])}
+        leg.update({name: run_shape_bf16(native, name, args) for name in args.shapes.split(",")})
+        res["bf16"] = list(leg.values())
+        line = json.dumps(res)
+        print(json.dumps(res["bf16"]))
+        with open(path, "w") as f:
+            f.write(line + "\n")
+        return
     res = {"workload": f"wav2vec 2.0 encoder, {args.batch} x {args.seconds:g} s, fp32, random weights", "steps": args.steps,
            "shapes": [run_shape(native, name, args) for name in args.shapes.split(",")]}
     line = json.dumps(res)

@@ -6,12 +6,17 @@ run, the price of the fused gated relative-position bias: ``native.wavlm_attenti
 The expectation that is RECORDED as met or missed (nothing is gated on it): wavlm_attention / rope_attention <= 1.3 -- one LDS
 read and one fused multiply-add per score against 128 MFMA flops and an ``exp``, at the same occupancy.
 
+``--precision bf16`` adds the reduced-precision leg: sbk_wavlm_attention_bf16 next to the fp32 kernel in the attention step
+(alternating in the same run), and every encoder shape under "fp32" and under "bf16".  Expectations recorded as met or missed:
+the bf16 kernel is faster than the fp32 kernel in the same run; the encoder under bf16 is faster than under fp32.
+
 Every GPU step (one encoder shape, the attention pair) runs in a fresh child process under its own time limit; the first step
 that fails or runs out of time ends the run (nothing more is started on the GPU) and is recorded.  ``--headline NAME=FILE``
 copies the JSON result line of a ``bench.py`` run (e.g. this tree's and the parent commit's, from the same visit) into the result.
 One JSON line per run, also written to profiles/wavlm_bench.json.  A job for a GPU visit.
 
     python tools/wavlm_bench.py [--steps 5] [--warmup 2] [--shapes base_plus,large] [--headline this=a.json --headline parent=b.json]
+                                 [--precision bf16]
 """
 import argparse
 import json
@@ -57,7 +62,7 @@ def event_us(torch, fn, steps, warmup):
     return a.elapsed_time(b) / steps * 1e3
 
 
-def encoder_step(name, args):
+def encoder_step(name, args, precision="fp32"):
     import torch
 
     from speechbrain_amd import native
@@ -70,9 +75,9 @@ def encoder_step(name, args):
     cfg = w.model.config
     wav = (0.3 * torch.randn(B, N, generator=torch.Generator().manual_seed(5))).cuda()
     lens = torch.linspace(0.6, 1.0, B).cuda()
-    res = {"shape": name, "batch": B, "seconds": args.seconds, "frames": int(w.model.feat_lengths(N)),
+    res = {"shape": name, "precision": precision, "batch": B, "seconds": args.seconds, "frames": int(w.model.feat_lengths(N)),
            "layers": cfg["num_hidden_layers"], "d": cfg["hidden_size"]}
-    with torch.no_grad():
+    with torch.no_grad(), native.precision_scope(precision):
         run = lambda: w(wav, lens)  # noqa: E731
         ms = p50_ms(torch, run, args.steps, args.warmup)
         res["encoder_p50_ms"] = round(ms, 3)
@@ -85,7 +90,8 @@ def encoder_step(name, args):
         native.prof_enable(False)
         rep = {k: v["ms"] / args.steps for k, v in native.prof_report().items()}
         res["encoder_kernel_ms"] = round(sum(rep.values()), 3)
-        res["wavlm_attention_share_of_kernel_time"] = round(rep["wavlm_attention"] / sum(rep.values()), 4)
+        res["wavlm_attention_share_of_kernel_time"] = round(
+            rep["wavlm_attention_bf16" if precision == "bf16" else "wavlm_attention"] / sum(rep.values()), 4)
         res["kernels_ms"] = {k: round(v, 4) for k, v in sorted(rep.items(), key=lambda kv: -kv[1])}
     return res
 
@@ -111,18 +117,29 @@ def attention_step(args):
         key_len = (torch.linspace(0.6, 1.0, B) * T).round().to(torch.int32).cuda()
         o1, o2 = torch.empty(B, T, d, device="cuda:0"), torch.empty(B, T, d, device="cuda:0")
         gated = lambda: native.wavlm_attention(qkv, x, gate_w, gate_b, gate_const, tab, key_len, H, Dh ** -0.5, out=o1)  # noqa: E731
+
+        def gated_bf16():
+            with native.precision_scope("bf16"):
+                gated()
+
         with native.precision_scope("fp32"):
             plain = lambda: native.rope_attention(qkv, None, None, key_len, H, Dh ** -0.5, out=o2)  # noqa: E731
-            us_g, us_p = [], []
-            for _ in range(3):  # alternate the two, keep each one's best of three: clock and cache state are shared
+            us_g, us_p, us_b = [], [], []
+            for _ in range(3):  # alternate them, keep each one's best of three: clock and cache state are shared
                 us_g.append(event_us(torch, gated, 10 * args.steps, args.warmup))
                 us_p.append(event_us(torch, plain, 10 * args.steps, args.warmup))
+                if args.precision == "bf16":
+                    us_b.append(event_us(torch, gated_bf16, 10 * args.steps, args.warmup))
         flops = 4.0 * B * H * float(T) * T * Dh
         r = {"shape": name, "B": B, "T": T, "H": H, "Dh": Dh, "wavlm_attention_us": round(min(us_g), 1),
              "rope_attention_us": round(min(us_p), 1), "ratio": round(min(us_g) / min(us_p), 3),
              "wavlm_attention_tflops": round(flops / min(us_g) / 1e6, 1), "rope_attention_tflops": round(flops / min(us_p) / 1e6, 1),
              "bias_tensor_avoided_mbytes_per_layer": round(4.0 * B * H * T * T / 1e6, 1)}
         r["expectation ratio <= 1.3"] = "met" if r["ratio"] <= 1.3 else "missed"
+        if us_b:
+            r["wavlm_attention_bf16_us"] = round(min(us_b), 1)
+            r["bf16_speedup"] = round(min(us_g) / min(us_b), 2)
+            r["expectation bf16 kernel faster than fp32 in the same run"] = "met" if min(us_b) < min(us_g) else "missed"
         out.append(r)
     return out
 
@@ -130,7 +147,7 @@ def attention_step(args):
 def child(step, args):
     """A fresh process for one GPU step, under its own time limit -> (result or None, error text or None)."""
     cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--batch", str(args.batch), "--seconds", str(args.seconds)]
+           "--batch", str(args.batch), "--seconds", str(args.seconds), "--precision", args.precision]
     try:
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=STEP_TIMEOUT_S)
     except subprocess.TimeoutExpired:
@@ -147,16 +164,22 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--shapes", default="base_plus,large")
-    ap.add_argument("--step", default=None, help="(internal) run one GPU step in this process: attention | encoder:<shape>")
+    ap.add_argument("--step", default=None, help="(internal) run one GPU step in this process: attention | encoder:<shape>[:<precision>]")
+    ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"])
     ap.add_argument("--headline", action="append", default=[], metavar="NAME=FILE",
                     help="a file whose last line is a bench.py JSON result, recorded under bench_py[NAME]")
     args = ap.parse_args()
     if args.step:
-        print(json.dumps(attention_step(args) if args.step == "attention" else encoder_step(args.step.split(":", 1)[1], args)))
+        if args.step == "attention":
+            print(json.dumps(attention_step(args)))
+        else:
+            _, name, precision = args.step.split(":")
+            print(json.dumps(encoder_step(name, args, precision)))
         return
-    res = {"workload": f"WavLM encoder, {args.batch} x {args.seconds:g} s, fp32, random weights", "steps": args.steps,
+    res = {"workload": f"WavLM encoder, {args.batch} x {args.seconds:g} s, {'fp32 and bf16' if args.precision == 'bf16' else 'fp32'}, random weights", "steps": args.steps,
            "shapes": [], "attention": None, "failed": None}
-    for step in ["attention"] + [f"encoder:{s}" for s in args.shapes.split(",") if s]:
+    precs = ("fp32", "bf16") if args.precision == "bf16" else ("fp32",)
+    for step in ["attention"] + [f"encoder:{s}:{p}" for s in args.shapes.split(",") if s for p in precs]:
         out, err = child(step, args)
         if err:  # (nothing more is started on the GPU after a step that failed or hung)
             res["failed"] = err
@@ -165,6 +188,10 @@ def main():
             res["attention"] = out
         else:
             res["shapes"].append(out)
+    by = {(r["shape"], r["precision"]): r["encoder_p50_ms"] for r in res["shapes"]}
+    for name in {n for n, p in by if p == "bf16"}:  # the expectation of the reduced-precision leg, per shape
+        res.setdefault("expectation encoder under bf16 faster than under fp32", {})[name] = (
+            "met" if by[name, "bf16"] < by[name, "fp32"] else "missed")
     bench = {}
     for item in args.headline:
         name, path = item.split("=", 1)
