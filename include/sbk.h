@@ -533,6 +533,26 @@ enum { SBK_RNN_LSTM = 0 }; /* (room for GRU / LiGRU cells) */
 int sbk_rnn_layer_route(int B, int T, int H, int D);
 int sbk_rnn_layer_f32(const float* xp, const float* w_hh, const float* b_ih, const float* b_hh, const float* h0, const float* c0,
                       float* out, float* hn, float* cn, int B, int T, int H, int D, int cell, int route, sbk_stream_t stream);
+/* The same layer with the product h_{t-1} . W_hh^T on v_mfma_f32_32x32x16_bf16 (csrc/rnn_bf16.hip; the opt-in precision "bf16";
+ * additive entries, ABI 11 unchanged).  Rounded to bf16 (nearest even): W_hh and h_{t-1}, and only as operands of that product.
+ * fp32: the accumulators, xp, both biases, the gate non-linearities, c, and the h written to out and hn.  Operands, semantics and
+ * limits as sbk_rnn_layer_f32, except:
+ *   whh_image   sbk_rnn_whh_bf16_image_bytes(H, D) bytes, 16-byte aligned, written by sbk_rnn_whh_bf16_image from w_hh [D,4H,H]
+ *               (once per weight): bf16 [D][ceil(H/8) slices of 8 units][ceil(H/16) chunks of 16 k][64 lanes][8], lane l of a
+ *               chunk holding the 8 k of MFMA column l & 31 = gate * 8 + unit, k block l >> 5; zeros past H (units and k).
+ *   workspace   sbk_rnn_layer_bf16_workspace_bytes(B, H, D) bytes, 16-byte aligned, the caller's, contents undefined before and
+ *               after: two bf16 copies of the state in the operand order of the product
+ *               [2][D][ceil(B/32) tiles][ceil(H/16) chunks][64 lanes][8], written by the cell update beside the fp32 h and read
+ *               by the next step (ping-pong); the entry fills them from h0 (or zeros) first.
+ * A wave's quarter of K runs over two independent accumulators (16-wide chunks round-robin, added once at the end); no atomics,
+ * fixed summation order: two runs, and two streams, give the same bits.  SBK_EINVAL names a bad shape, an image whose size is not
+ * that of (H, D), and a short workspace.  The size queries return 0 for a shape outside the limits. */
+size_t sbk_rnn_whh_bf16_image_bytes(int H, int D);
+int sbk_rnn_whh_bf16_image(const float* w_hh, void* image, size_t image_bytes, int H, int D, sbk_stream_t stream);
+size_t sbk_rnn_layer_bf16_workspace_bytes(int B, int H, int D);
+int sbk_rnn_layer_bf16(const float* xp, const void* whh_image, size_t image_bytes, const float* b_ih, const float* b_hh,
+                       const float* h0, const float* c0, float* out, float* hn, float* cn, void* workspace, size_t workspace_bytes,
+                       int B, int T, int H, int D, int cell, sbk_stream_t stream);
 
 /* ---- The convolution blocks of a CRDNN encoder (csrc/crdnn.hip; additive entries, ABI 11 unchanged)
  * lobes/models/CRDNN.py:199-278: [reflect-pad(1) + Conv2d(3x3, stride 1, bias) (nnet/CNN.py:654-751) -> LayerNorm over (F,C)

@@ -7,6 +7,23 @@ import torch
 from speechbrain_amd.inference.interfaces import Pretrained
 
 
+def _run_children(enc, x, wav_lens, precision, scoped):
+    """LengthsCapableSequential.forward / Sequential.forward of the container ``enc``, child by child: the children that are
+    instances of ``scoped`` run under ``precision``, every other child under "fp32"."""
+    from speechbrain_amd import native
+    from speechbrain_amd.nnet.containers import LengthsCapableSequential
+
+    for name, layer in enc.items():
+        with native.precision_scope(precision if isinstance(layer, scoped) else "fp32"):
+            if isinstance(enc, LengthsCapableSequential) and name in enc.length_layers:
+                x = layer(x, lengths=wav_lens)
+            else:
+                x = layer(x)
+        if isinstance(x, tuple):
+            x = x[0]
+    return x
+
+
 class EncoderDecoderASR(Pretrained):
     """Same surface as the reference: transcribe_file / transcribe_batch / encode_batch / forward.
 
@@ -33,12 +50,18 @@ class EncoderDecoderASR(Pretrained):
 
     def encode_batch(self, wavs, wav_lens):
         from speechbrain_amd import native
+        from speechbrain_amd.lobes.models.CRDNN import CRDNN
+        from speechbrain_amd.nnet.containers import Sequential
 
         if self.transducer_beam_search and not self.transformer_beam_search:
             return EncoderASR.encode_batch(self, wavs, wav_lens)
         wavs = wavs.float()
         wavs, wav_lens = wavs.to(self.device), wav_lens.to(self.device)
-        encoder_out = self.mods.encoder(wavs, wav_lens)  # Fbank / normalisation / CNN: always fp32
+        enc = self.mods.encoder
+        if self.eval_precision == "bf16" and isinstance(enc, Sequential) and any(isinstance(m, CRDNN) for m in enc.values()):
+            encoder_out = _run_children(enc, wavs, wav_lens, "bf16", (CRDNN,))  # a CRDNN child: its contractions and recurrence
+        else:
+            encoder_out = enc(wavs, wav_lens)  # Fbank / normalisation / CNN: always fp32
         if self.transformer_beam_search:
             with native.precision_scope(self.eval_precision):
                 encoder_out = self.mods.transformer.encode(encoder_out, wav_lens)
@@ -127,12 +150,14 @@ class EncoderASR(Pretrained):
         encoder runs under the interface's precision (fp32 = the parity path): the children of the encoder container
         that are an ``EncoderWrapper`` / ``TransformerASR`` and, under "bf16", a ``Wav2Vec2`` / ``HuBERT`` / ``WavLM`` wrapper
         (its contractions, attention and positional convolution; its waveform convolution, statistics and LayerNorms have
-        no reduced form); the feature front-end, the CNN and the CTC head stay fp32.
+        no reduced form) or a ``CRDNN`` (its contractions and its LSTM recurrence, lobes/models/CRDNN.py); the feature
+        front-end, a stand-alone CNN and the CTC head stay fp32.
         (An encoder that is not a container runs under the precision as a whole.)"""
         from speechbrain_amd import native
         from speechbrain_amd.integrations.huggingface.wav2vec2 import Wav2Vec2
+        from speechbrain_amd.lobes.models.CRDNN import CRDNN
         from speechbrain_amd.lobes.models.transformer.TransformerASR import EncoderWrapper, TransformerASR
-        from speechbrain_amd.nnet.containers import LengthsCapableSequential, Sequential
+        from speechbrain_amd.nnet.containers import Sequential
 
         wavs = wavs.float()
         wavs, wav_lens = wavs.to(self.device), wav_lens.to(self.device)
@@ -141,19 +166,9 @@ class EncoderASR(Pretrained):
             with native.precision_scope(self.eval_precision):
                 return enc(wavs, wav_lens)
         scoped = (EncoderWrapper, TransformerASR)
-        if self.eval_precision == "bf16":  # the self-supervised encoders (Wav2Vec2 and its subclasses HuBERT, WavLM): bf16 only
-            scoped += (Wav2Vec2,)
-        x = wavs
-        for name, layer in enc.items():  # LengthsCapableSequential.forward / Sequential.forward, child by child
-            p = self.eval_precision if isinstance(layer, scoped) else "fp32"
-            with native.precision_scope(p):
-                if isinstance(enc, LengthsCapableSequential) and name in enc.length_layers:
-                    x = layer(x, lengths=wav_lens)
-                else:
-                    x = layer(x)
-            if isinstance(x, tuple):
-                x = x[0]
-        return x
+        if self.eval_precision == "bf16":  # the self-supervised encoders (Wav2Vec2 and its subclasses HuBERT, WavLM), CRDNN: bf16 only
+            scoped += (Wav2Vec2, CRDNN)
+        return _run_children(enc, wavs, wav_lens, self.eval_precision, scoped)
 
     def transcribe_batch(self, wavs, wav_lens):
         import functools

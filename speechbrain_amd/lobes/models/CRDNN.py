@@ -13,6 +13,9 @@ On the device (csrc/crdnn.hip, csrc/rnn.hip):
               in ONE pass that writes only the pooled tensor (native.crdnn_norm_pool)
   RNN         per layer ONE contraction x . [W_ih | W_ih_reverse]^T for both directions, then native.rnn_layer
   DNN_Block   Linear with the BatchNorm1d running statistics folded in and LeakyReLU in the GEMM epilogue
+Under the ambient precision "bf16" (native.crdnn_precision) the patch-matrix contractions, the LSTM input projections and the
+DNN blocks take gemm_nt's bf16 route (fp32 activations rounded on load) and the recurrence runs sbk_rnn_layer_bf16; the first
+convolution, the patches, every LayerNorm and pooling pass and the BatchNorm fold stay fp32.  Every other precision is fp32.
 
 Not implemented (NotImplementedError when the model is constructed): rnn_class GRU / LiGRU / RNN, use_rnnp, projection_dim,
 using_2d_pooling, activations other than LeakyReLU, kernels other than 3 x 3."""
@@ -106,7 +109,7 @@ class DNN_Block(Sequential):
         lin, norm = self["linear"].w, self["norm"]
         wf, bf = self._folded.get([lin.weight, lin.bias] + norm.sources(), lambda: norm.fold(lin.weight, lin.bias),
                                   extra=(norm.norm.eps,))
-        with native.precision_scope("fp32"):  # (as the convolutions and the input projections: CRDNN is an fp32 model here)
+        with native.precision_scope(native.crdnn_precision()):  # (as the convolutions and the input projections)
             return native.gemm_nt(x.contiguous(), wf, bf, act=native.ACT_LEAKY_RELU)
 
 
@@ -202,9 +205,9 @@ class CRDNN(Sequential):
         for w_ih, w_hh, b_ih, b_hh in self._rnn_weights():
             B, T, _ = x.shape
             D, H = w_hh.shape[0], w_hh.shape[2]
-            with native.precision_scope("fp32"):
+            with native.precision_scope(native.crdnn_precision()):
                 xp = native.gemm_nt(x.contiguous(), w_ih)  # [B,T,D*4H]: both directions in one contraction
-            x, _, _ = native.rnn_layer(xp.view(B, T, D, 4 * H), w_hh, b_ih, b_hh)
+                x, _, _ = native.rnn_layer(xp.view(B, T, D, 4 * H), w_hh, b_ih, b_hh)
             outs.append(x)
         return (x, outs) if return_layers else x
 

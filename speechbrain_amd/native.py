@@ -220,6 +220,10 @@ def _declare(lib):
         "sbk_hypermix_f32": ([p] * 13 + [f, p, p, p, ctypes.c_size_t, i, i, i, i, i, p], c_int),
         "sbk_rnn_layer_route": ([i, i, i, i], c_int),
         "sbk_rnn_layer_f32": ([p] * 9 + [i] * 6 + [p], c_int),
+        "sbk_rnn_whh_bf16_image_bytes": ([i, i], ctypes.c_size_t),
+        "sbk_rnn_whh_bf16_image": ([p, p, ctypes.c_size_t, i, i, p], c_int),
+        "sbk_rnn_layer_bf16_workspace_bytes": ([i, i, i], ctypes.c_size_t),
+        "sbk_rnn_layer_bf16": ([p, p, ctypes.c_size_t] + [p] * 8 + [ctypes.c_size_t] + [i] * 5 + [p], c_int),
         "sbk_crdnn_conv1_f32": ([p] * 6 + [i, i, i, i, f, f, p], c_int),
         "sbk_crdnn_im2col_f32": ([p, p, i, i, i, i, i, i, p], c_int),
         "sbk_crdnn_norm_pool_f32": ([p] * 4 + [i] * 6 + [f, f, p], c_int),
@@ -818,6 +822,11 @@ def _make_image(w: torch.Tensor, kind: str):
         N, K = w2.shape
         out = torch.empty(((N + 63) // 64) * 64 * K * 3, dtype=torch.int16, device=w.device)
         _chk(lib.sbk_split_x3p(_p(w2), K, _p(out), N, K, _stream(w2)), "sbk_split_x3p")
+    elif kind == "rnn_whh":  # w_hh [D,4H,H] in the operand order of sbk_rnn_layer_bf16
+        D, _, H = w2.shape
+        nbytes = lib.sbk_rnn_whh_bf16_image_bytes(H, D)  # (0 for a shape outside the limits: the entry below names it)
+        out = torch.empty(nbytes // 2, dtype=torch.int16, device=w.device)
+        _chk(lib.sbk_rnn_whh_bf16_image(_p(w2), _p(out), nbytes, H, D, _stream(w2)), "sbk_rnn_whh_bf16_image")
     elif kind == "bf16k32":  # bf16 with every row zero-padded to a multiple of 32 (sbk_w2v_posconv_bf16's K step)
         w2 = torch.nn.functional.pad(w2, (0, -w2.shape[1] % 32))
         out = torch.empty(w2.shape, dtype=torch.int16, device=w.device)
@@ -832,6 +841,7 @@ def _make_image(w: torch.Tensor, kind: str):
 def lp_weight(w: torch.Tensor, kind: str = "bf16"):
     """The reduced-precision image of a weight matrix ("bf16" / "fp16": int16 bits; "fp8": (uint8 e4m3 bits, w_scale);
     "bf16k32": bf16 bits with every row zero-padded to a multiple of 32, the filter image of sbk_w2v_posconv_bf16;
+    "rnn_whh": w_hh [D,4H,H] as bf16 bits in the operand order of sbk_rnn_layer_bf16 (sbk_rnn_whh_bf16_image);
     "x3": the exact three-piece bf16 split [N, K/32, 3, 32] of sbk_split_bf16x3 -- not reduced: the pieces sum to w),
     cached for the lifetime of THAT tensor object: the entry holds a weak reference to its source and is used only while
     ``ref() is w`` and the version counter is unchanged (a freed model's addresses are commonly handed to the next
@@ -1519,10 +1529,19 @@ def rnn_layer_route(B, T, H, D) -> int:
     return int(load().sbk_rnn_layer_route(int(B), int(T), int(H), int(D)))
 
 
+def rnn_whh_bf16_image(w_hh):
+    """The bf16 operand image of w_hh [D,4H,H] for sbk_rnn_layer_bf16 (int16 bits, [D][ceil(H/8)][ceil(H/16)][64][8], zeros past
+    H): made once per weight tensor through the weight cache, as the positional convolution's filter image is."""
+    return lp_weight(w_hh, "rnn_whh")
+
+
 def rnn_layer(xp, w_hh, b_ih=None, b_hh=None, h0=None, c0=None, route=0):
     """One LSTM layer for every utterance and direction (sbk_rnn_layer_f32): xp [B,T,D,4H] = x . W_ih^T per direction without
     bias, w_hh [D,4H,H], b_ih / b_hh [D,4H] or None, h0 / c0 [D,B,H] or None (zeros)
-    -> (out [B,T,D*H], hn [D,B,H], cn [D,B,H]); direction 1 runs backwards in time and writes at its own t."""
+    -> (out [B,T,D*H], hn [D,B,H], cn [D,B,H]); direction 1 runs backwards in time and writes at its own t.
+    Under ``precision() == "bf16"`` the product h . W_hh^T runs on the bf16 matrix cores (sbk_rnn_layer_bf16): W_hh and h_{t-1}
+    are rounded to bf16 as its operands only; xp, the biases, the gates, c and the h that is returned stay fp32.  Every other
+    precision takes the fp32 entry."""
     lib = load()
     if xp.ndim != 4 or w_hh.ndim != 3:
         raise SbkError(f"rnn_layer: xp {tuple(xp.shape)} is not [B,T,D,4H] or w_hh {tuple(w_hh.shape)} is not [D,4H,H]")
@@ -1540,6 +1559,14 @@ def rnn_layer(xp, w_hh, b_ih=None, b_hh=None, h0=None, c0=None, route=0):
     out = torch.empty(B, T, D * H, dtype=torch.float32, device=xp.device)
     hn = torch.empty(D, B, H, dtype=torch.float32, device=xp.device)
     cn = torch.empty(D, B, H, dtype=torch.float32, device=xp.device)
+    if precision() == "bf16":  # opt-in: the product on the bf16 matrix cores, W_hh's image made once per weight
+        img = rnn_whh_bf16_image(w_hh)
+        nbytes = lib.sbk_rnn_layer_bf16_workspace_bytes(B, H, D)
+        st = _stream(xp)
+        with _Workspace(nbytes, xp.device, per_stream=True) as ws:  # (the bf16 shadows of the state)
+            _chk(lib.sbk_rnn_layer_bf16(_p(xp), _p(img), img.numel() * 2, _p(b_ih), _p(b_hh), _p(h0), _p(c0), _p(out), _p(hn),
+                                        _p(cn), ws.ptr, nbytes, B, T, H, D, RNN_LSTM, st), "sbk_rnn_layer_bf16")
+        return out, hn, cn
     _chk(lib.sbk_rnn_layer_f32(_p(xp), _p(w_hh), _p(b_ih), _p(b_hh), _p(h0), _p(c0), _p(out), _p(hn), _p(cn), B, T, H, D,
                                RNN_LSTM, int(route), _stream(xp)), "sbk_rnn_layer_f32")
     return out, hn, cn
@@ -1691,6 +1718,12 @@ CRDNN_MAX_FRAME = 16384  # csrc/crdnn.hip kMaxFrame: F * C floats of a frame hel
 CRDNN_COL_BYTES = 256 << 20  # budget of the patch matrix of one chunk of frames
 
 
+def crdnn_precision() -> str:
+    """The precision of a CRDNN's contractions (patch-matrix products, LSTM input projections, DNN blocks) and of its recurrence:
+    the ambient "bf16", or "fp32" -- "fp16" / "fp8" have no recurrent kernel, and CRDNN stays an fp32 model under them."""
+    return "bf16" if precision() == "bf16" else "fp32"
+
+
 def _crdnn_time_check(T, F):
     if T < 2 or F < 2:  # (F.pad(mode="reflect") of the reference refuses a padding that is not smaller than the dimension)
         raise ValueError(f"CRDNN convolution: reflect padding of 1 needs at least 2 frames and 2 bins, got T={T} F={F}")
@@ -1733,7 +1766,7 @@ def crdnn_conv(x, wk, bias, col_bytes=None):
             n = min(per, B * T - f0)
             col = ws.buf[ws.off:ws.off + n * F * K * 4].view(torch.float32).view(n * F, K)
             _chk(lib.sbk_crdnn_im2col_f32(_p(x), _p(col), B, T, F, Cin, f0, n, st), "sbk_crdnn_im2col_f32")
-            with precision_scope("fp32"):
+            with precision_scope(crdnn_precision()):
                 gemm_nt(col, wk, bias, out=y2[f0 * F:(f0 + n) * F])
     return y
 

@@ -21,6 +21,8 @@ time ends the run (nothing more is started on the GPU) and is recorded.  ``--hea
 a ``bench.py`` run into the result.  One JSON line per run, also written to profiles/crdnn_bench.json.  A job for a GPU visit.
 
     python tools/crdnn_bench.py [--steps 3] [--warmup 1] [--headline this=a.json ...]
+    python tools/crdnn_bench.py --precision bf16     # the fp32 and bf16 forms alternating: us per recurrent step at B 32 and B 1,
+                                                     # ms per batch, the recurrence's share; joins the file as "precision_bf16"
 """
 import argparse
 import json
@@ -222,6 +224,70 @@ def torch_step(args):
     return out
 
 
+def bf16_step(args):
+    """``--precision bf16``: the fp32 and the bf16 form alternating in ONE process -- the recurrence of layers 1-3 at B 32 and B 1
+    (us per step), then the encoder from PCM (ms per batch) and the recurrence's share of its kernel time."""
+    import torch
+
+    from speechbrain_amd import native
+    from speechbrain_amd.lobes.features import Fbank
+
+    native.load()
+    gen = torch.Generator().manual_seed(9)
+    precisions = ("fp32", "bf16")
+    res = {"lstm": []}
+
+    def scoped(prec, fn):
+        def run(*a):
+            with native.precision_scope(prec):
+                return fn(*a)
+        return run
+
+    w_hh = (torch.randn(2, 4 * H, H, generator=gen) / H ** 0.5).cuda()
+    b_ih, b_hh = torch.randn(2, 4 * H, generator=gen).cuda(), torch.randn(2, 4 * H, generator=gen).cuda()
+    for B in (32, 1):
+        xp = torch.randn(B, T_RNN, 2, 4 * H, generator=gen).cuda()
+        rec = {p: scoped(p, lambda: native.rnn_layer(xp, w_hh, b_ih, b_hh)) for p in precisions}
+        runs = {p: [] for p in precisions}
+        for _ in range(3):  # alternate
+            for p in precisions:
+                runs[p].append(med(event_ms(torch, rec[p], args.steps, args.warmup)))
+        us = {p: round(med(sorted(runs[p])) * 1e3 / T_RNN, 2) for p in precisions}
+        diff = float((rec["bf16"]()[0] - rec["fp32"]()[0]).abs().max())
+        res["lstm"].append({"B": B, "T": T_RNN, "H": H, "D": 2, "fp32_us_per_step": us["fp32"], "bf16_us_per_step": us["bf16"],
+                            "ms_repeated": {p: [round(v, 3) for v in runs[p]] for p in precisions}, "max_abs_diff_out": diff,
+                            "expectation the bf16 step is faster": "met" if us["bf16"] < us["fp32"] else "missed"})
+    B = args.batch
+    m = build_model(torch)
+    fbank = Fbank(sample_rate=16000, n_fft=400, n_mels=N_MELS).to("cuda:0")
+    wav = (0.1 * torch.randn(B, 160000, generator=torch.Generator().manual_seed(5))).cuda()
+    enc = {"batch": B, "seconds": 10.0}
+    with torch.no_grad():
+        run = {p: (lambda f=scoped(p, m): f(fbank(wav))) for p in precisions}  # (the front-end is fp32 in every mode)
+        ms = {p: [] for p in precisions}
+        for _ in range(2):  # alternate
+            for p in precisions:
+                ms[p] += event_ms(torch, run[p], args.steps, args.warmup)
+        for p in precisions:
+            enc[p + "_p50_ms"] = round(med(sorted(ms[p])), 2)
+            native.prof_reset()
+            native.prof_enable(True)
+            run[p]()
+            torch.cuda.synchronize()
+            native.prof_enable(False)
+            rep = native.prof_report()
+            total = sum(v["ms"] for v in rep.values())
+            enc[p + "_kernel_ms"] = round(total, 2)
+            enc[p + "_share_recurrence"] = round(sum(v["ms"] for k, v in rep.items() if k.startswith("rnn_")) / total, 4)
+            enc[p + "_kernels_ms"] = {k: [v["count"], round(v["ms"], 3)] for k, v in sorted(rep.items(), key=lambda kv: -kv[1]["ms"])}
+        ref = run["fp32"]()
+        enc["rel_rms_bf16_vs_fp32"] = float(((run["bf16"]() - ref).pow(2).mean() / ref.pow(2).mean()).sqrt())
+    enc["expectation bf16 ms per batch is lower"] = "met" if enc["bf16_p50_ms"] < enc["fp32_p50_ms"] else "missed"
+    enc["expectation the bf16 recurrence share is lower"] = "met" if enc["bf16_share_recurrence"] < enc["fp32_share_recurrence"] else "missed"
+    res["encoder"] = enc
+    return res
+
+
 STEPS = {"encoder": encoder_step, "convs": convs_step, "lstm": lstm_step, "torch": torch_step}
 
 
@@ -243,13 +309,25 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--precision", default="fp32", choices=("fp32", "bf16"),
+                    help="bf16: only the fp32 / bf16 comparison (recurrent step, encoder), recorded under the key precision_bf16")
     ap.add_argument("--step", default=None, help="(internal) run one GPU step in this process: " + " | ".join(STEPS))
     ap.add_argument("--headline", action="append", default=[], metavar="NAME=FILE",
                     help="a file whose last line is a bench.py JSON result, recorded under bench_py[NAME]")
     args = ap.parse_args()
     if args.step:
-        print(json.dumps(STEPS[args.step](args)))
+        print(json.dumps(dict(STEPS, bf16=bf16_step)[args.step](args)))
         return
+    path = os.path.join(ROOT, "profiles", "crdnn_bench.json")
+    if args.precision == "bf16":  # one step; its result joins the recorded fp32 run under a key of its own
+        out, err = child("bf16", args)
+        with open(path) as f:
+            res = json.loads(f.read().strip().splitlines()[-1])
+        res["precision_bf16"] = out if err is None else {"failed": err}
+        print(json.dumps(res["precision_bf16"]))
+        with open(path, "w") as f:
+            f.write(json.dumps(res) + "\n")
+        sys.exit(1 if err else 0)
     res = {"workload": f"CRDNN encoder (train_BPE_1000.yaml shape), {args.batch} x 10 s from PCM, fp32, random weights",
            "steps": args.steps, "rnn_routes_in_tree": [1], "failed": None}
     for step in STEPS:
