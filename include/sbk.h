@@ -397,6 +397,19 @@ int sbk_relpos_attention_f32(const float* qkv, const float* pos, const float* bi
                              const int32_t* key_len, float* out, float* attn, int B, int T, int H, int Dh,
                              float scale, int chunk_size, int left_chunks, sbk_stream_t stream);
 
+/* The same attention (context only: no attn output; head_dim 64) on the bf16 matrix cores, for the opt-in reduced-precision
+ * path (run_opts precision="bf16": the Conformer / Branchformer encoders with RelPosMHAXL).  All three products -- K (q+u)^T,
+ * P (q+v)^T and V^T P^T -- run on v_mfma_f32_32x32x16_bf16.  Rounded to bf16 (nearest even), and nothing else:
+ *   (q + u) * scale and (q + v) * scale, each formed in fp32 first; k, the position rows and v as matrix operands; the
+ *   unnormalised probabilities as the operand of the context product.
+ * Kept in fp32: the position term (added to the fp32 score unrounded), the scores, the softmax statistics, the normaliser
+ * (the sum of the UNROUNDED probabilities), the context accumulators; inputs and output stay fp32 in HBM.
+ * key_len, chunk_size / left_chunks and the zero context of a query without an allowed key as for sbk_relpos_attention_f32;
+ * qkv and pos 16-byte aligned.  Additive entry, ABI 11 unchanged. */
+int sbk_relpos_attention_bf16(const float* qkv, const float* pos, const float* bias_u, const float* bias_v,
+                              const int32_t* key_len, float* out, int B, int T, int H, int Dh, float scale,
+                              int chunk_size, int left_chunks, sbk_stream_t stream);
+
 /* ---- RoPEMHA core (nnet/attention.py:1167-1392): what sits between in_proj and out_proj.
  *   out = softmax( rot(q) rot(k)^T scale , keys < key_len ) v,  scale = 1/sqrt(embed_dim) (:1272)
  *   qkv as for sbk_relpos_attention_f32; cosines / sines [table_rows >= T, Dh] = the buffers of

@@ -1,5 +1,5 @@
 // Fused relative-position self-attention (RelPosMHAXL, Transformer-XL style)
-//                                                      (sbk_relpos_attention_f32)
+//                                                      (sbk_relpos_attention_f32, sbk_relpos_attention_bf16)
 //   out = softmax( (q+u)K^T s + shift((q+v)P^T s) , keys < key_len ) V
 //
 // Roofline: MFMA fp32 (three 32x32 contractions per key tile: AC, BD x2, then
@@ -830,6 +830,173 @@ __global__ void __launch_bounds__(256, 2) rope_flash_t_bf16_kernel(AttnArgs a) {
   }
 }
 
+// RelPosMHAXL on the bf16 matrix cores (precision "bf16", head_dim 64): the walk of relpos_flash_t_kernel -- a wave owns 32
+// queries, scores transposed, online softmax over 32-key tiles, the position term through the wave's 64-row LDS ring -- with
+// all three products on v_mfma_f32_32x32x16_bf16: 4 issues for S^T = K ((q+u) s)^T, 4 for the ring block G^T = P ((q+v) s)^T
+// of 32 position rows, 4 for O^T += V^T P^T; 12 per key tile where the fp32 kernel makes 96.  The accumulator layout of the
+// instruction is the 32x32x2 one's (register r = row (r&3) + 8(r>>2) + 4*half), so the ring indexing carries over unchanged.
+// Rounded to bf16: (q+u) s and (q+v) s (each formed in fp32 first), k, the position rows, v, and the unnormalised
+// probabilities as the operand of the context product.  Everything else is fp32: the ring (the position term is added to the
+// fp32 score and never rounded, like the bias of wavlm_flash_t_bf16_kernel), the scores, the softmax statistics, the
+// normaliser (the sum of the UNROUNDED probabilities), the context accumulators, the output.
+// Operands come per wave as fp32 rows from global, converted in registers (load_chunks of rope_flash_t_bf16_kernel: MFMA step
+// t reads channels 16t + 8*half .. +7).  LDS: 4 x 8 KiB of ring per workgroup.
+__global__ void __launch_bounds__(256, 2) relpos_flash_t_bf16_kernel(AttnArgs a) {
+  constexpr int DH = 64;
+  using sbk::bf16x8;
+  __shared__ float Gs[4][64][32];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int jl = lane & 31, half = lane >> 5;
+  const int i0 = (blockIdx.x * 4 + wave) * 32, h = blockIdx.y, b = blockIdx.z;
+  const int T = a.T, d = a.H * DH;
+  if (i0 >= T) return;
+  const size_t row3 = (size_t)3 * d;
+  const float* qkv_b = a.qkv + (size_t)b * T * row3 + (size_t)h * 3 * DH;
+  const int qrow = min(i0 + jl, T - 1);
+  float (*G)[32] = Gs[wave];
+
+  // the four operand chunks of one fp32 row: channels 16t + 8*half .. +7, rounded on the way into the matrix cores
+  auto load_chunks = [&](const float* row, bf16x8 (&dst)[4]) SBK_INLINE_LAMBDA {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      float x[8];
+      load_run<8>(x, row + 16 * t + 8 * half);
+      dst[t] = sbk::cvt_bf16x8(x);
+    }
+  };
+  bf16x8 qu[4], qv[4];  // (q + u) * scale and (q + v) * scale: formed in fp32, then rounded
+  {
+    const float* qr = qkv_b + (size_t)qrow * row3;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int c0 = 16 * t + 8 * half;
+      float x[8], xu[8], xv[8];
+      load_run<8>(x, qr + c0);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {  // (the bias vectors carry no alignment requirement: scalar loads, once per wave)
+        xu[e] = (x[e] + a.bias_u[h * DH + c0 + e]) * a.scale;
+        xv[e] = (x[e] + a.bias_v[h * DH + c0 + e]) * a.scale;
+      }
+      qu[t] = sbk::cvt_bf16x8(xu);
+      qv[t] = sbk::cvt_bf16x8(xv);
+    }
+  }
+  int klen = T;
+  if (a.key_len) klen = min(max(a.key_len[b], 1), T);
+  const int nkt = (klen + 31) / 32;
+  int lo, hi;
+  key_range(a, qrow, klen, lo, hi);
+  int kt_begin = 0, kt_end = nkt;
+  if (a.chunk > 0) {
+    kt_end = min(nkt, ((min(i0 + 31, T - 1) / a.chunk + 1) * a.chunk + 31) / 32);
+    if (a.left >= 0) kt_begin = max(0, (i0 / a.chunk - a.left) * a.chunk) / 32;
+  }
+  float m_run = -INFINITY, l_run = 0.0f;
+  f32x16 o[2];
+#pragma unroll
+  for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[ct][r] = 0.0f;
+
+  // G^T of the 32 position rows from `first_row` (clamped to the table) against the wave's queries -> ring rows of `slot`, fp32
+  auto g_block = [&](int first_row, int slot) SBK_INLINE_LAMBDA {
+    bf16x8 pb[4];
+    const int prow = min(max(first_row + jl, 0), 2 * T - 2);
+    load_chunks(a.pos + (size_t)prow * d + h * DH, pb);
+    f32x16 g;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) g[r] = 0.0f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) g = sbk::mfma_32x32x16_bf16(pb[t], qv[t], g);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) G[slot * 32 + (r & 3) + 8 * (r >> 2) + 4 * half][jl] = g[r];
+  };
+  // key tile kt reads the rows rbase .. rbase+62, rbase = T-1-i0-31+32*kt; the block starting at rbase + 32*m lives in slot (kt + m) & 1
+  g_block((T - 1) - i0 - 31 + 32 * kt_begin, kt_begin & 1);
+  for (int kt = kt_begin; kt < kt_end; ++kt) {
+    const int j0 = kt * 32;
+    const int rbase = (T - 1) - i0 - 31 + j0;
+    bf16x8 kb[4];
+    load_chunks(qkv_b + (size_t)min(j0 + jl, T - 1) * row3 + DH, kb);
+    f32x16 acc;  // S^T: row = key (r&3) + 8(r>>2) + 4*half of the tile, column = query jl
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc = sbk::mfma_32x32x16_bf16(kb[t], qu[t], acc);
+    g_block(rbase + 32, (kt + 1) & 1);  // the upper block of this tile = the lower one of the next (the slot last read two tiles ago)
+    // V^T operands: step s contracts the 8 keys the accumulator registers 8s .. 8s+7 of this half-wave belong to
+    bf16x8 vb[2][2];
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) {
+      const float* vbase = qkv_b + 2 * DH + ct * 32 + jl;
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        float x[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const int r = 8 * s + e;
+          x[e] = vbase[(size_t)min(j0 + (r & 3) + 8 * (r >> 2) + 4 * half, T - 1) * row3];
+        }
+        vb[ct][s] = sbk::cvt_bf16x8(x);
+      }
+    }
+    sbk::wave_sync();  // the ring holds both blocks of this tile
+    float mx = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int jc = (r & 3) + 8 * (r >> 2) + 4 * half;
+      const int rr = 31 - jl + jc;  // 0 .. 62: row of this tile's window for (query jl, key jc)
+      acc[r] += G[(((kt & 1) + (rr >> 5)) & 1) * 32 + (rr & 31)][jl];
+      const int key = j0 + jc;
+      if (!(key >= lo && key < hi)) acc[r] = -INFINITY;
+      mx = fmaxf(mx, acc[r]);
+    }
+    sbk::wave_sync();  // everybody has read the lower block before the next tile overwrites its slot
+    mx = fmaxf(mx, sbk::shfl_xor(mx, 32));
+    const float m_new = fmaxf(m_run, mx);
+    // base-2 softmax on one v_exp_f32 per score, as relpos_flash_t_kernel: a masked score gives exactly 0; a query whose keys are
+    // all masked so far keeps m = -inf: guarded
+    constexpr float kL2E = 1.44269504088896340736f;
+    const bool none = m_new == -INFINITY;
+    const float nm = none ? 0.0f : -m_new * kL2E;
+    const float alpha = none ? 1.0f : sbk::exp2_raw(fmaf(m_run, kL2E, nm));
+    float sum = 0.0f;
+    bf16x8 pb[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      float x[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        x[e] = none ? 0.0f : sbk::exp2_raw(fmaf(acc[8 * s + e], kL2E, nm));
+        sum += x[e];  // the normaliser sums the unrounded probabilities
+      }
+      pb[s] = sbk::cvt_bf16x8(x);
+    }
+    sum += sbk::shfl_xor(sum, 32);
+    l_run = l_run * alpha + sum;
+    m_run = m_new;
+    if (sbk::wave_any(alpha != 1.0f)) {  // (a new maximum is rare after the first tiles)
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[ct][r] *= alpha;
+    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct) o[ct] = sbk::mfma_32x32x16_bf16(vb[ct][s], pb[s], o[ct]);
+  }
+  // O^T: column = this lane's query, row = channel (r&3) + 8(r>>2) + 4*half + 32*ct; registers 4q .. 4q+3 are four consecutive channels
+  if (i0 + jl < T) {
+    const float inv = l_run > 0.0f ? 1.0f / l_run : 0.0f;  // no allowed key at all: zero context
+    float* orow = a.out + ((size_t)b * T + i0 + jl) * d + h * DH;
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) orow[ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * half] = o[ct][r] * inv;
+  }
+}
+
 // ---- plain attention on bf16 q / k / v rows shared through LDS (the Whisper encoder under precision "bf16") ------------
 // qkv [B,T,H,3,64] bf16 as written by the bf16-activation QKV contraction; vT [B,H,64,Tp] bf16 = the values transposed
 // (v_transpose_bf16_kernel, Tp = T rounded up to 64, zero padded).  A workgroup = one (utterance, head) and 128 queries
@@ -1185,4 +1352,20 @@ extern "C" int sbk_relpos_attention_f32(const float* qkv, const float* pos, cons
   SBK_REQUIRE(chunk_size >= 0, "relpos_attention: negative chunk size");
   return sbk::relpos_attention(qkv, pos, bias_u, bias_v, key_len, out, attn, B, T, H, Dh, scale,
                                sbk::as_stream(stream), chunk_size, left_chunks);
+}
+
+extern "C" int sbk_relpos_attention_bf16(const float* qkv, const float* pos, const float* bias_u, const float* bias_v,
+                                         const int32_t* key_len, float* out, int B, int T, int H, int Dh, float scale,
+                                         int chunk_size, int left_chunks, sbk_stream_t stream) {
+  if (B == 0 || T == 0) return 0;  // empty batch: nothing to launch, the data pointers may be NULL
+  SBK_REQUIRE(qkv && pos && bias_u && bias_v && out, "relpos_attention_bf16: null operand");
+  SBK_REQUIRE(B >= 0 && T >= 0 && H > 0 && Dh == 64, "relpos_attention_bf16: head_dim 64 only (got %d)", Dh);
+  SBK_REQUIRE(sbk::aligned16(qkv) && sbk::aligned16(pos), "relpos_attention_bf16: operands must be 16-byte aligned");
+  SBK_REQUIRE(chunk_size >= 0, "relpos_attention_bf16: negative chunk size");
+  hipStream_t st = sbk::as_stream(stream);
+  AttnArgs a{qkv, pos, bias_u, bias_v, key_len, out, nullptr, B, T, H, 0, scale, chunk_size, left_chunks, 0};
+  sbk::ProfScope prof("relpos_attention_bf16", 6.0 * B * H * (double)T * T * Dh,
+                      4.0 * B * T * (4.0 * H * Dh) + 4.0 * (2.0 * T - 1) * H * Dh, st);
+  SBK_LAUNCH(relpos_flash_t_bf16_kernel, dim3((T + 127) / 128, H, B), dim3(256), 0, st, a);
+  return sbk::launch_status("sbk_relpos_attention_bf16");
 }

@@ -202,6 +202,7 @@ def _declare(lib):
         "sbk_conv_block_k_f32": ([p, p, p, p, p, p, i, i, i, i, i, i, i, f, f, p], c_int),
         "sbk_conv_block_res1x1_f32": ([p, p, p, p, p, f, p, p, p, p, f, p, i, i, i, i, i, f, p], c_int),
         "sbk_relpos_attention_f32": ([p, p, p, p, p, p, p, i, i, i, i, f, i, i, p], c_int),
+        "sbk_relpos_attention_bf16": ([p, p, p, p, p, p, i, i, i, i, f, i, i, p], c_int),
         "sbk_rope_attention_f32": ([p, p, p, p, p, p, i, i, i, i, i, f, i, i, p], c_int),
         "sbk_rope_attention_bf16": ([p, p, p, p, p, i, i, i, i, i, f, i, i, p], c_int),
         "sbk_glu_dwconv_f32": ([p, p, p, p, i, i, i, i, i, p], c_int),
@@ -1243,7 +1244,8 @@ def relpos_attention(qkv, pos, bias_u, bias_v, key_len, H, scale, want_attn=Fals
                      out=None):
     """qkv [B,T,3*d] (per-head interleaved), pos [2T-1,d] -> context [B,T,d] (+ weights [B,H,T,T]).
     ``chunk_size`` > 0: Dynamic Chunk mask (``left_chunks`` < 0 = unlimited left context).  ``out``: optional
-    contiguous [B,T,d] destination."""
+    contiguous [B,T,d] destination.  Under precision "bf16" the context-only call at head_dim 64 runs its three products on
+    the bf16 matrix cores (sbk_relpos_attention_bf16); the weights output and other head dims keep the fp32 kernels."""
     lib = load()
     _dev_ok(qkv, pos, bias_u, bias_v, key_len, out)
     _f32(qkv)
@@ -1251,6 +1253,11 @@ def relpos_attention(qkv, pos, bias_u, bias_v, key_len, H, scale, want_attn=Fals
     d = d3 // 3
     if out is None:
         out = torch.empty(B, T, d, dtype=torch.float32, device=qkv.device)
+    if precision() == "bf16" and not want_attn and d // H == 64:  # opt-in: bf16 operands on the matrix cores
+        _chk(lib.sbk_relpos_attention_bf16(_p(qkv), _p(pos), _p(bias_u), _p(bias_v), _p(key_len), _p(out), B, T, H, d // H,
+                                           float(scale), int(chunk_size), int(left_chunks), _stream(qkv)),
+             "sbk_relpos_attention_bf16")
+        return out, None
     attn = torch.empty(B, H, T, T, dtype=torch.float32, device=qkv.device) if want_attn else None
     _chk(lib.sbk_relpos_attention_f32(_p(qkv), _p(pos), _p(bias_u), _p(bias_v), _p(key_len), _p(out), _p(attn), B, T,
                                       H, d // H, float(scale), int(chunk_size), int(left_chunks), _stream(qkv)),

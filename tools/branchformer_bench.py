@@ -4,8 +4,12 @@ the encoder's ms per batch, the CSGU launches' own time (HIP events) and bytes/s
 launch reads 2C and writes C floats per frame, the statistics pass reads C more and writes two), and -- for context, in the
 same run -- the Conformer-L encoder (12 layers, d_ffn 2048) on the same features.  One JSON line, also written to
 profiles/branchformer_bench.json.  A job for a GPU visit.
+``--precision bf16`` adds the reduced-precision leg under the key precision_bf16: both encoders under precision "bf16" with
+sbk_relpos_attention_bf16 and, alternating, with the attention alone held to fp32 (the encoder before that kernel existed);
+the attention's share of kernel time in both; and three attention launches at the encoder's shape by HIP events (relpos fp32,
+relpos bf16, rope bf16 -- the last shows what the position ring costs).
 
-    python tools/branchformer_bench.py [--steps 10] [--warmup 3]
+    python tools/branchformer_bench.py [--steps 10] [--warmup 3] [--precision bf16]
 """
 import argparse
 import json
@@ -49,6 +53,87 @@ def p50_ms(fn, steps, warmup):
     return round(times[len(times) // 2] * 1e3, 3)
 
 
+def event_us(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(steps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / steps * 1e3
+
+
+def attention_launches(native, B, T, steps, warmup, H=8, Dh=64):
+    """relpos_attention fp32 / bf16 and rope_attention bf16 on the same qkv and key lengths, alternating; each one's best of three."""
+    d, gen = H * Dh, torch.Generator().manual_seed(11)
+    qkv = torch.randn(B, T, 3 * d, generator=gen).cuda()
+    pos = torch.randn(2 * T - 1, d, generator=gen).cuda()
+    u, v = (0.3 * torch.randn(d, generator=gen)).cuda(), (0.3 * torch.randn(d, generator=gen)).cuda()
+    key_len = (torch.linspace(0.6, 1.0, B) * T).round().to(torch.int32).cuda()
+    out = torch.empty(B, T, d, device="cuda:0")
+
+    def scoped(precision, fn):
+        def run():
+            with native.precision_scope(precision):
+                fn()
+        return run
+
+    relpos = lambda: native.relpos_attention(qkv, pos, u, v, key_len, H, Dh ** -0.5, out=out)  # noqa: E731
+    runs = {"relpos_attention_fp32": scoped("fp32", relpos), "relpos_attention_bf16": scoped("bf16", relpos),
+            "rope_attention_bf16": scoped("bf16", lambda: native.rope_attention(qkv, None, None, key_len, H, Dh ** -0.5, out=out))}
+    us = {k: [] for k in runs}
+    for _ in range(3):
+        for k, fn in runs.items():
+            us[k].append(event_us(fn, 10 * steps, warmup))
+    best = {k: min(t) for k, t in us.items()}
+    res = {"B": B, "T": T, "H": H, "Dh": Dh}
+    for k, t in best.items():  # (6 flops per score and channel with the position term, 4 without)
+        res[k + "_us"] = round(t, 1)
+        res[k + "_tflops"] = round((4.0 if k.startswith("rope") else 6.0) * B * H * float(T) * T * Dh / t / 1e6, 1)
+    res["bf16_speedup_over_fp32"] = round(best["relpos_attention_fp32"] / best["relpos_attention_bf16"], 2)
+    res["ratio_to_rope_attention_bf16"] = round(best["relpos_attention_bf16"] / best["rope_attention_bf16"], 2)
+    res["expectation bf16 relpos launch faster than fp32 in the same run"] = "met" if res["bf16_speedup_over_fp32"] > 1.0 else "missed"
+    return res
+
+
+def bf16_leg(native, models, feats, lens, steps, warmup):
+    """Both encoders under precision "bf16", and -- the encoder as it ran before relpos_attention had a bf16 form -- the same with
+    the attention call alone put back under "fp32" (bf16 GEMMs, fp32 attention), alternating in this run."""
+    real = native.relpos_attention
+
+    def fp32_attention(*a, **k):
+        with native.precision_scope("fp32"):
+            return real(*a, **k)
+
+    res = {}
+    for name, tr in models.items():
+        ms, share = {"attention_fp32": [], "attention_bf16": []}, {}
+        for _ in range(2):
+            for mode in ms:
+                native.relpos_attention = fp32_attention if mode == "attention_fp32" else real
+                try:
+                    with native.precision_scope("bf16"):
+                        ms[mode].append(p50_ms(lambda: tr.encode(feats, lens), steps, warmup))
+                        native.prof_reset()
+                        native.prof_enable(True)
+                        tr.encode(feats, lens)
+                        torch.cuda.synchronize()
+                        native.prof_enable(False)
+                finally:
+                    native.relpos_attention = real
+                rep = native.prof_report()
+                key = "relpos_attention" if mode == "attention_fp32" else "relpos_attention_bf16"
+                share[mode] = round(rep[key]["ms"] / sum(v["ms"] for v in rep.values()), 4)
+        res[name] = {"encoder_p50_ms_attention_fp32": min(ms["attention_fp32"]), "encoder_p50_ms": min(ms["attention_bf16"]),
+                     "attention_share_of_kernel_time_before": share["attention_fp32"],
+                     "attention_share_of_kernel_time_after": share["attention_bf16"],
+                     "expectation encoder faster than with the fp32 attention":
+                         "met" if min(ms["attention_bf16"]) < min(ms["attention_fp32"]) else "missed"}
+    return res
+
+
 def main():
     from speechbrain_amd import native
 
@@ -57,6 +142,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--seconds", type=float, default=10.0)
+    ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"],
+                    help="bf16: adds the reduced-precision leg (both encoders, the three attention launches) under precision_bf16")
     args = ap.parse_args()
     native.load()
     B = args.batch
@@ -88,9 +175,11 @@ def main():
         res["copy_kernel_TBps"] = COPY_TBPS
         res["branchformer_kernel_ms_by_name"] = {k: round(v["ms"] / args.steps, 3) for k, v in
                                                  sorted(rep.items(), key=lambda kv: -kv[1]["ms"])}
-        del bf
         cf = build("conformer", 12)
         res["conformer_l_encoder_p50_ms"] = p50_ms(lambda: cf.encode(feats, lens), args.steps, args.warmup)
+        if args.precision == "bf16":
+            res["precision_bf16"] = {"attention": attention_launches(native, B, T, args.steps, args.warmup),
+                                     **bf16_leg(native, {"branchformer": bf, "conformer_l": cf}, feats, lens, args.steps, args.warmup)}
     line = json.dumps(res)
     print(line)
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
