@@ -420,10 +420,12 @@ int sbk_rope_attention_f32(const float* qkv, const float* cosines, const float* 
                            float* out, float* attn, int B, int T, int H, int Dh, int table_rows, float scale,
                            int chunk_size, int left_chunks, sbk_stream_t stream);
 
-/* The same attention (no attention-weights output, head_dim 64) on the bf16 matrix cores, for the opt-in reduced-
+/* The same attention (no attention-weights output, head_dim 64 or 128) on the bf16 matrix cores, for the opt-in reduced-
  * precision path (run_opts precision="bf16"; the Whisper encoder's MHA at d = 1280 / 20 heads is its main user): q, k,
  * v and the probabilities are rounded to bf16 into v_mfma_f32_32x32x16_bf16, the scores, the softmax statistics and
- * the context accumulate in fp32; inputs and output stay fp32 in HBM. */
+ * the context accumulate in fp32; inputs and output stay fp32 in HBM.  head_dim 128 (the transformer.yaml recipe: d 512,
+ * 4 heads) stages K and V once per workgroup in LDS; it needs a 16-byte aligned out and T * 3 * H * 128 < 2^30, as
+ * sbk_rope_attention_f32 does at 128.  sbk_rope_attention_bf16o (bf16 context) is head_dim 64 only. */
 int sbk_rope_attention_bf16(const float* qkv, const float* cosines, const float* sines, const int32_t* key_len,
                             float* out, int B, int T, int H, int Dh, int table_rows, float scale, int chunk_size,
                             int left_chunks, sbk_stream_t stream);

@@ -830,6 +830,220 @@ __global__ void __launch_bounds__(256, 2) rope_flash_t_bf16_kernel(AttnArgs a) {
   }
 }
 
+// Head dim 128 on the bf16 matrix cores (precision "bf16"; the transformer.yaml recipe: d 512, 4 heads): plain and RoPE attention
+// with the semantics of rope_flash_t_bf16_kernel, but the K / V work done once per WORKGROUP.  At 128 channels the per-wave form
+// would fetch, rotate and convert 16 KiB of K, 16 KiB of V (as strided 4-byte loads) and 32 KiB of tables per wave and tile, four
+// times over.  Here the 256 threads load a stage of 32 keys as 16-byte global loads (4 K pieces, 4 V pieces and, with tables,
+// 4 + 4 table pieces per thread), rotate K in fp32 with the key frame's own table rows, round K and V to bf16 and write them to
+// LDS, where all four waves read their MFMA operands:
+//   Ks[buf][key][17 x 16 B]     a K row of 128 bf16 + 16 B of padding: the pitch is 272 B = 17 x 16, so the 16-byte reads of a
+//                               half-wave (32 keys, the same 8 channels) fall on 16-byte bank groups 17 j mod 16 = j: conflict-free;
+//   Vs[buf][channel][5 x 16 B]  V transposed, 32 keys per channel row + 16 B of padding (pitch 80 B = 5 x 16, 5 odd: the reads
+//                               of a half-wave -- 32 channels, the same slot -- are conflict-free too).  The keys of a row are
+//                               permuted: position p holds key p with bits 2 and 3 swapped, so the 16-byte slot 2s + half is
+//                               the 8 keys (r&3) + 8(r>>2) + 4*half of the accumulator registers r = 8s .. 8s+7 of that half-wave:
+//                               the V^T operand of context step s is one read.
+// The stage kt + 1 travels in registers (64 per lane with tables, 32 without) while the MFMAs consume stage kt from one LDS
+// buffer, then is converted into the other: one barrier per stage.  2 x (8 704 + 10 240) B = 37 888 B of static LDS.
+// Dynamic Chunk masks give the waves of a workgroup different key-tile ranges: the workgroup walks the UNION of them, every
+// thread takes part in every stage's loads and barriers -- also the waves past the end of the utterance (i0 >= T) and those
+// for which the tile lies outside their own range, which skip the arithmetic only.  Nobody returns before the last barrier.
+// Per 32-key tile and wave: 8 MFMAs for S^T = K (rot(q) s)^T (step t = channels 16t + 8*half .. +7), base-2 online softmax in
+// fp32 as in relpos_flash_t_bf16_kernel, 8 MFMAs for O^T += V^T P^T (4 channel groups x 2 key steps): 16 issues where
+// rope_flash_t128_kernel makes 128.  Rounded to bf16: the rotated, scaled q; the rotated k; v; the unnormalised probabilities
+// as the operand of the context product.  fp32: scores, softmax statistics, the normaliser (the sum of the UNROUNDED
+// probabilities), the context accumulators, the output.  Offsets inside an utterance are 32-bit (the entry checks T * 3d < 2^30).
+__device__ __forceinline__ float4 rotate4(float4 x, float4 c, float4 g) {
+  return make_float4(x.x * c.x + x.y * g.x, x.y * c.y + x.x * g.y, x.z * c.z + x.w * g.z, x.w * c.w + x.z * g.w);
+}
+
+__global__ void __launch_bounds__(256, 2) rope_flash_t128_bf16_kernel(AttnArgs a) {
+  constexpr int DH = 128, NC = 4, NT = 8;
+  using sbk::bf16x8;
+  __shared__ uint4 Ks[2][32][17];
+  __shared__ uint4 Vs[2][DH][5];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int jl = lane & 31, half = lane >> 5;
+  const int i0 = (blockIdx.x * 4 + wave) * 32, h = blockIdx.y, b = blockIdx.z;
+  const int T = a.T, d = a.H * DH;
+  const bool live = i0 < T;  // (a wave past the utterance still loads and meets the barriers)
+  const unsigned row3u = 3u * d;
+  const float* qkv_b = a.qkv + (size_t)b * T * row3u + (size_t)h * 3 * DH;
+  const int qrow = min(i0 + jl, T - 1);
+  const bool rot = a.pos != nullptr;  // no tables: plain scaled-dot-product attention (uniform for the launch)
+
+  bf16x8 qb[NT];  // MFMA step t: channels 16t + 8*half .. +7 of this lane's query, rotated and scaled in fp32, then rounded
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int c0 = 16 * t + 8 * half;
+    float x[8];
+    load_run<8>(x, qkv_b + ((unsigned)qrow * row3u + c0));
+    if (rot) rotate_chunks<8>(x, a.pos + (size_t)qrow * DH + c0, a.bias_u + (size_t)qrow * DH + c0);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[e] *= a.scale;
+    qb[t] = sbk::cvt_bf16x8(x);
+  }
+
+  int klen = T;
+  if (a.key_len) klen = min(max(a.key_len[b], 1), T);
+  const int nkt = (klen + 31) / 32;
+  int lo, hi;  // allowed keys of this lane's query
+  key_range(a, qrow, klen, lo, hi);
+  // key tiles of the 32 queries from `first`; the wave's own range and the union over the workgroup's live waves
+  auto tile_range = [&](int first, int& begin, int& end) SBK_INLINE_LAMBDA {
+    begin = 0;
+    end = nkt;
+    if (a.chunk > 0) {
+      end = min(nkt, ((min(first + 31, T - 1) / a.chunk + 1) * a.chunk + 31) / 32);
+      if (a.left >= 0) begin = max(0, (first / a.chunk - a.left) * a.chunk) / 32;
+    }
+  };
+  int kt_begin = 0, kt_end = 0, u_begin = nkt, u_end = 0;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const int first = (blockIdx.x * 4 + w) * 32;
+    int wb = 0, we = 0;
+    if (first < T) tile_range(first, wb, we);
+    if (wb < we) {
+      u_begin = min(u_begin, wb);
+      u_end = max(u_end, we);
+    }
+    if (w == wave) {
+      kt_begin = wb;
+      kt_end = we;
+    }
+  }
+
+  // loader roles.  K: row tid>>3 of the stage, the 8-channel pieces ksub and ksub + 8 of it (two adjacent 16-byte loads each; one
+  // 16-byte LDS write each).  V: channels 4vf .. 4vf+3 of the keys 4vm .. 4vm+3 (four 16-byte loads; per channel the four keys
+  // are four adjacent positions of the permuted row: one 8-byte LDS write each, slot = vm with bits 0 and 1 swapped).
+  const int krow = tid >> 3, ksub = tid & 7;
+  const int vf = (lane & 7) + 8 * wave, vm = lane >> 3;
+  const int vslot = (vm & 4) | ((vm & 1) << 1) | ((vm >> 1) & 1);
+  float4 kx[4], kc[4], ks[4], vx[4];
+  auto issue = [&](int kt) SBK_INLINE_LAMBDA {  // global -> registers; rows past the utterance re-read its last row (masked below)
+    const unsigned key = min(kt * 32 + krow, T - 1);
+    const float4* kp = reinterpret_cast<const float4*>(qkv_b + (key * row3u + DH + 8 * ksub));
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      kx[2 * i] = kp[16 * i];
+      kx[2 * i + 1] = kp[16 * i + 1];
+    }
+    if (rot) {
+      const float4* cp = reinterpret_cast<const float4*>(a.pos + (size_t)key * DH + 8 * ksub);
+      const float4* sp = reinterpret_cast<const float4*>(a.bias_u + (size_t)key * DH + 8 * ksub);
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        kc[2 * i] = cp[16 * i];
+        kc[2 * i + 1] = cp[16 * i + 1];
+        ks[2 * i] = sp[16 * i];
+        ks[2 * i + 1] = sp[16 * i + 1];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const unsigned vkey = min(kt * 32 + 4 * vm + i, T - 1);
+      vx[i] = *reinterpret_cast<const float4*>(qkv_b + (vkey * row3u + 2 * DH + 4 * vf));
+    }
+  };
+  auto commit = [&](int buf) SBK_INLINE_LAMBDA {  // registers -> rotate (fp32) -> bf16 -> LDS
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      float4 x0 = kx[2 * i], x1 = kx[2 * i + 1];
+      if (rot) {
+        x0 = rotate4(x0, kc[2 * i], ks[2 * i]);
+        x1 = rotate4(x1, kc[2 * i + 1], ks[2 * i + 1]);
+      }
+      Ks[buf][krow][ksub + 8 * i] =
+          make_uint4(sbk::bf16_pair(x0.x, x0.y), sbk::bf16_pair(x0.z, x0.w), sbk::bf16_pair(x1.x, x1.y), sbk::bf16_pair(x1.z, x1.w));
+    }
+    reinterpret_cast<uint2*>(Vs[buf][4 * vf])[vslot] = make_uint2(sbk::bf16_pair(vx[0].x, vx[1].x), sbk::bf16_pair(vx[2].x, vx[3].x));
+    reinterpret_cast<uint2*>(Vs[buf][4 * vf + 1])[vslot] = make_uint2(sbk::bf16_pair(vx[0].y, vx[1].y), sbk::bf16_pair(vx[2].y, vx[3].y));
+    reinterpret_cast<uint2*>(Vs[buf][4 * vf + 2])[vslot] = make_uint2(sbk::bf16_pair(vx[0].z, vx[1].z), sbk::bf16_pair(vx[2].z, vx[3].z));
+    reinterpret_cast<uint2*>(Vs[buf][4 * vf + 3])[vslot] = make_uint2(sbk::bf16_pair(vx[0].w, vx[1].w), sbk::bf16_pair(vx[2].w, vx[3].w));
+  };
+  auto operand = [](const uint4& u) SBK_INLINE_LAMBDA { return sbk::bf16x8_from_words(u.x, u.y, u.z, u.w); };
+
+  float m_run = -INFINITY, l_run = 0.0f;
+  f32x16 o[NC];
+#pragma unroll
+  for (int ct = 0; ct < NC; ++ct)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[ct][r] = 0.0f;
+
+  if (u_begin < u_end) {  // (uniform for the workgroup, like everything that decides a barrier below)
+    issue(u_begin);
+    commit(0);
+    __syncthreads();
+  }
+  for (int kt = u_begin; kt < u_end; ++kt) {
+    const int buf = (kt - u_begin) & 1;
+    const bool more = kt + 1 < u_end;
+    if (more) issue(kt + 1);  // in flight behind this stage's arithmetic
+    if (live && kt >= kt_begin && kt < kt_end) {  // (uniform for the wave)
+      const int j0 = kt * 32;
+      f32x16 acc;  // S^T: row = key (r&3) + 8(r>>2) + 4*half of the tile, column = query jl
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+#pragma unroll
+      for (int t = 0; t < NT; ++t) acc = sbk::mfma_32x32x16_bf16(operand(Ks[buf][jl][2 * t + half]), qb[t], acc);
+      float mx = -INFINITY;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int key = j0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        if (!(key >= lo && key < hi)) acc[r] = -INFINITY;
+        mx = fmaxf(mx, acc[r]);
+      }
+      mx = fmaxf(mx, sbk::shfl_xor(mx, 32));
+      const float m_new = fmaxf(m_run, mx);
+      // base-2 softmax on one v_exp_f32 per score: a masked score gives exactly 0; a query whose keys are all masked so far
+      // keeps m = -inf: guarded
+      constexpr float kL2E = 1.44269504088896340736f;
+      const bool none = m_new == -INFINITY;
+      const float nm = none ? 0.0f : -m_new * kL2E;
+      const float alpha = none ? 1.0f : sbk::exp2_raw(fmaf(m_run, kL2E, nm));
+      float sum = 0.0f;
+      bf16x8 pb[2];
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        float x[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          x[e] = none ? 0.0f : sbk::exp2_raw(fmaf(acc[8 * s + e], kL2E, nm));
+          sum += x[e];  // the normaliser sums the unrounded probabilities
+        }
+        pb[s] = sbk::cvt_bf16x8(x);
+      }
+      sum += sbk::shfl_xor(sum, 32);
+      l_run = l_run * alpha + sum;
+      m_run = m_new;
+      if (sbk::wave_any(alpha != 1.0f)) {  // (a new maximum is rare after the first tiles)
+#pragma unroll
+        for (int ct = 0; ct < NC; ++ct)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) o[ct][r] *= alpha;
+      }
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int ct = 0; ct < NC; ++ct) o[ct] = sbk::mfma_32x32x16_bf16(operand(Vs[buf][32 * ct + jl][2 * s + half]), pb[s], o[ct]);
+    }
+    if (more) commit(buf ^ 1);  // (everybody left that buffer before the previous barrier)
+    __syncthreads();
+  }
+  // O^T: column = this lane's query, row = channel (r&3) + 8(r>>2) + 4*half + 32*ct; registers 4q .. 4q+3 are four consecutive channels
+  if (i0 + jl < T) {
+    const float inv = l_run > 0.0f ? 1.0f / l_run : 0.0f;  // no allowed key at all: zero context
+    float* orow = a.out + ((size_t)b * T + i0 + jl) * d + h * DH;
+#pragma unroll
+    for (int ct = 0; ct < NC; ++ct)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        *reinterpret_cast<float4*>(orow + ct * 32 + 8 * q + 4 * half) =
+            make_float4(o[ct][4 * q] * inv, o[ct][4 * q + 1] * inv, o[ct][4 * q + 2] * inv, o[ct][4 * q + 3] * inv);
+  }
+}
+
 // RelPosMHAXL on the bf16 matrix cores (precision "bf16", head_dim 64): the walk of relpos_flash_t_kernel -- a wave owns 32
 // queries, scores transposed, online softmax over 32-key tiles, the position term through the wave's 64-row LDS ring -- with
 // all three products on v_mfma_f32_32x32x16_bf16: 4 issues for S^T = K ((q+u) s)^T, 4 for the ring block G^T = P ((q+v) s)^T
@@ -1307,15 +1521,26 @@ int rope_attention_bf16_impl(const float* qkv, const float* cosines, const float
                              int left_chunks, sbk_stream_t stream) {
   if (B == 0 || T == 0) return 0;  // empty batch: nothing to launch, the data pointers may be NULL
   SBK_REQUIRE(qkv && out && (cosines != nullptr) == (sines != nullptr), "rope_attention_bf16: null operand");
-  SBK_REQUIRE(B >= 0 && T >= 0 && H > 0 && Dh == 64, "rope_attention_bf16: head_dim 64 only (got %d)", Dh);
+  SBK_REQUIRE(B >= 0 && T >= 0 && H > 0, "rope_attention_bf16: bad shape (B %d, T %d, H %d)", B, T, H);
+  SBK_REQUIRE(!out_bf16 || Dh == 64, "rope_attention_bf16: the bf16 context output is head_dim 64 only (got %d)", Dh);
+  SBK_REQUIRE(Dh == 64 || Dh == 128, "rope_attention_bf16: head_dim 64 or 128 only (got %d)", Dh);
   SBK_REQUIRE(!cosines || table_rows >= T, "rope_attention_bf16: the sinusoid tables hold %d rows, T = %d", table_rows, T);
   SBK_REQUIRE(sbk::aligned16(qkv) && sbk::aligned16(cosines) && sbk::aligned16(sines),
               "rope_attention_bf16: operands must be 16-byte aligned");
   SBK_REQUIRE(chunk_size >= 0, "rope_attention_bf16: negative chunk size");
+  if (Dh == 128) {  // (the conditions of the fp32 head-dim-128 launcher)
+    SBK_REQUIRE((double)T * 3.0 * H * 128 < 1073741824.0,
+                "rope_attention_bf16: head_dim 128 addresses an utterance's rows with 32-bit offsets: T * 3 * d must be < 2^30");
+    SBK_REQUIRE(sbk::aligned16(out), "rope_attention_bf16: head_dim 128 writes 16-byte pieces: out must be 16-byte aligned");
+  }
   hipStream_t st = sbk::as_stream(stream);
   AttnArgs a{qkv, cosines, sines, nullptr, key_len, reinterpret_cast<float*>(out), nullptr, B, T, H, 0, scale, chunk_size, left_chunks, out_bf16};
   sbk::ProfScope prof("rope_attention_bf16", 4.0 * B * H * (double)T * T * Dh, 4.0 * B * T * (3.0 * H * Dh) + (out_bf16 ? 2.0 : 4.0) * B * T * H * Dh, st);
-  SBK_LAUNCH(rope_flash_t_bf16_kernel, dim3((T + 127) / 128, H, B), dim3(256), 0, st, a);
+  if (Dh == 128) {
+    SBK_LAUNCH(rope_flash_t128_bf16_kernel, dim3((T + 127) / 128, H, B), dim3(256), 0, st, a);
+  } else {
+    SBK_LAUNCH(rope_flash_t_bf16_kernel, dim3((T + 127) / 128, H, B), dim3(256), 0, st, a);
+  }
   return sbk::launch_status("sbk_rope_attention_bf16");
 }
 }  // namespace

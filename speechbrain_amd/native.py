@@ -467,8 +467,8 @@ _tls = threading.local()
 
 def precision() -> str:
     """"fp32" (parity path, default) or an opt-in reduced-precision operand type for the large GEMMs, all with fp32
-    accumulation: "bf16" (also the bf16 attention kernels -- rope_attention and wavlm_attention at head dim 64 -- and the
-    positional convolution w2v_posconv), "fp16", "fp8" (e4m3, per-tensor scales)."""
+    accumulation: "bf16" (also the bf16 attention kernels -- rope_attention at head dim 64 / 128, wavlm_attention at
+    head dim 64 -- and the positional convolution w2v_posconv), "fp16", "fp8" (e4m3, per-tensor scales)."""
     return getattr(_tls, "precision", "fp32")
 
 
@@ -1268,7 +1268,9 @@ def relpos_attention(qkv, pos, bias_u, bias_v, key_len, H, scale, want_attn=Fals
 def rope_attention(qkv, cosines, sines, key_len, H, scale, want_attn=False, chunk_size=0, left_chunks=-1, out=None,
                    out_dtype=torch.float32):
     """qkv [B,T,3*d] (per-head interleaved), cosines / sines [rows >= T, Dh] -> context [B,T,d].  ``cosines`` =
-    ``sines`` = None: plain scaled-dot-product attention (no rotation; no attention-weights output)."""
+    ``sines`` = None: plain scaled-dot-product attention (no rotation; no attention-weights output).  Under precision "bf16" the
+    context-only call at head dim 64 or 128 runs on the bf16 matrix cores (sbk_rope_attention_bf16; at 128 the K / V stage is
+    shared by the workgroup through LDS); ``out_dtype=torch.bfloat16`` (a bf16 context) stays head dim 64 only."""
     lib = load()
     _dev_ok(qkv, cosines, sines, key_len, out)
     _f32(qkv)
@@ -1285,7 +1287,7 @@ def rope_attention(qkv, cosines, sines, key_len, H, scale, want_attn=False, chun
         return out, None
     if out is None:
         out = torch.empty(B, T, d, dtype=torch.float32, device=qkv.device)
-    if precision() == "bf16" and not want_attn and d // H == 64:  # opt-in: bf16 operands on the matrix cores
+    if precision() == "bf16" and not want_attn and d // H in (64, 128):  # opt-in: bf16 operands on the matrix cores
         _chk(lib.sbk_rope_attention_bf16(_p(qkv), _p(cosines), _p(sines), _p(key_len), _p(out), B, T, H, d // H,
                                          rows, float(scale), int(chunk_size), int(left_chunks), _stream(qkv)),
              "sbk_rope_attention_bf16")
