@@ -544,7 +544,7 @@ int sbk_hypermix_f32(const float* h, const int32_t* key_len, const float* pe, co
  * previous step is read from `out`.  Fixed summation order: two runs give the same bits.  sbk_rnn_layer_route: the route that
  * route = 0 takes for a shape (0: the shape is refused).
  * Limits (SBK_EINVAL): 1 <= H <= 2048, D 1 or 2, B >= 1 (any remainder against the 32-row tile), T >= 1, cell SBK_RNN_LSTM. */
-enum { SBK_RNN_LSTM = 0 }; /* (room for GRU / LiGRU cells) */
+enum { SBK_RNN_LSTM = 0 }; /* (room for GRU / LiGRU cells; SLi-GRU has an entry of its own: sbk_sligru_layer_f32) */
 int sbk_rnn_layer_route(int B, int T, int H, int D);
 int sbk_rnn_layer_f32(const float* xp, const float* w_hh, const float* b_ih, const float* b_hh, const float* h0, const float* c0,
                       float* out, float* hn, float* cn, int B, int T, int H, int D, int cell, int route, sbk_stream_t stream);
@@ -568,6 +568,33 @@ size_t sbk_rnn_layer_bf16_workspace_bytes(int B, int H, int D);
 int sbk_rnn_layer_bf16(const float* xp, const void* whh_image, size_t image_bytes, const float* b_ih, const float* b_hh,
                        const float* h0, const float* c0, float* out, float* hn, float* cn, void* workspace, size_t workspace_bytes,
                        int B, int T, int H, int D, int cell, sbk_stream_t stream);
+
+/* ---- One SLi-GRU layer for every utterance and both directions (csrc/sligru.hip; additive entries, ABI 11 unchanged)
+ * The recurrent stack of a CRDNN encoder with rnn_class SLiGRU (nnet/RNN.py:1623-1804), over the PADDED length.  Per step
+ *     gates = xp[:, t] + LayerNorm_{2H}(h_{t-1} . u^T);  a, z = gates.chunk(2);  h_t = sigmoid(z) h_{t-1} + (1 - sigmoid(z)) act(a)
+ * with the LayerNorm over all 2H columns (biased variance, eps 1e-5).  A cell of its own entry, not a `cell` of sbk_rnn_layer_f32.
+ *   xp   [B,T,2H]    the normalised feed-forward term (w(x) behind its BatchNorm / LayerNorm).  ONE tensor serves both
+ *                    directions: direction 1 at scan step s reads frame T-1-s (the reference flips x before a per-frame map)
+ *   u    [2H,H]      rows 0..H-1 the a gate, rows H..2H-1 the z gate; shared by the directions
+ *   ln_gamma, ln_beta [2H]   recurrent_elementwise_affine (both or neither; NULL = none)
+ *   h0   [D,B,H]     initial state (NULL = zeros)
+ *   out  [B,T,D*H]   direction d owns columns d*H .. (d+1)*H; direction 1 scans t = T-1 .. 0 and writes at its own t
+ *   hn   [D,B,H]     final state (h0 must not be hn or out)
+ *   workspace        sbk_sligru_layer_workspace_bytes(B, H, D) bytes, 16-byte aligned, the caller's, contents undefined before
+ *                    and after: the raw recurrent product of one step, [D*B,2H]
+ *   act              SBK_SLIGRU_* below (leaky_relu: slope 0.01)
+ * Two launches per step.  The product: the D*B rows of both directions against one slice of u, a workgroup owning 8 hidden
+ * units with both gate rows and 32 rows on v_mfma_f32_16x16x4_f32, its waves splitting K and meeting in LDS in wave order.  The
+ * norm-and-cell pass: one workgroup per row, the 2H values in registers, mean then centred squares on a fixed reduction tree.  No
+ * atomics, fixed summation order: two runs, and two streams, give the same bits.
+ * Limits (SBK_EINVAL): 1 <= H <= 2048, D 1 or 2, 1 <= B <= 1048560 (any remainder against the 32-row tile; the D*B rows are
+ * at most 65535 row tiles), T >= 1, a known act, a
+ * workspace of at least the queried size.  The size query returns 0 for a shape outside the limits. */
+enum { SBK_SLIGRU_RELU = 0, SBK_SLIGRU_TANH = 1, SBK_SLIGRU_SIN = 2, SBK_SLIGRU_LEAKY_RELU = 3 };
+size_t sbk_sligru_layer_workspace_bytes(int B, int H, int D);
+int sbk_sligru_layer_f32(const float* xp, const float* u, const float* ln_gamma, const float* ln_beta, const float* h0, float* out,
+                         float* hn, void* workspace, size_t workspace_bytes, int B, int T, int H, int D, int act,
+                         sbk_stream_t stream);
 
 /* ---- The convolution blocks of a CRDNN encoder (csrc/crdnn.hip; additive entries, ABI 11 unchanged)
  * lobes/models/CRDNN.py:199-278: [reflect-pad(1) + Conv2d(3x3, stride 1, bias) (nnet/CNN.py:654-751) -> LayerNorm over (F,C)

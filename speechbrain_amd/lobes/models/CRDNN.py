@@ -12,12 +12,14 @@ On the device (csrc/crdnn.hip, csrc/rnn.hip):
               conv_2 the same contraction; norm_2 + act_2 + the frequency pooling (+ CRDNN's time pooling behind the last block)
               in ONE pass that writes only the pooled tensor (native.crdnn_norm_pool)
   RNN         per layer ONE contraction x . [W_ih | W_ih_reverse]^T for both directions, then native.rnn_layer
+              (rnn_class SLiGRU: nnet.RNN.SLiGRU_Layer per layer -- the folded contraction, then native.sligru_layer, whose
+              recurrent product stays fp32 under every precision; its stages are recorded as ``rnn_layer{i}``)
   DNN_Block   Linear with the BatchNorm1d running statistics folded in and LeakyReLU in the GEMM epilogue
 Under the ambient precision "bf16" (native.crdnn_precision) the patch-matrix contractions, the LSTM input projections and the
 DNN blocks take gemm_nt's bf16 route (fp32 activations rounded on load) and the recurrence runs sbk_rnn_layer_bf16; the first
 convolution, the patches, every LayerNorm and pooling pass and the BatchNorm fold stay fp32.  Every other precision is fp32.
 
-Not implemented (NotImplementedError when the model is constructed): rnn_class GRU / LiGRU / RNN, use_rnnp, projection_dim,
+Not implemented (NotImplementedError when the model is constructed): rnn_class GRU / LiGRU / RNN (LSTM and SLiGRU are), use_rnnp, projection_dim,
 using_2d_pooling, activations other than LeakyReLU, kernels other than 3 x 3."""
 import torch
 
@@ -28,7 +30,7 @@ from speechbrain_amd.nnet.dropout import Dropout2d
 from speechbrain_amd.nnet.linear import Linear
 from speechbrain_amd.nnet.normalization import BatchNorm1d, LayerNorm
 from speechbrain_amd.nnet.pooling import Pooling1d
-from speechbrain_amd.nnet.RNN import LSTM
+from speechbrain_amd.nnet.RNN import LSTM, SLiGRU
 
 
 def _leaky_slope(activation):
@@ -135,7 +137,7 @@ class CRDNN(Sequential):
             raise NotImplementedError("CRDNN: projection_dim != -1 is not implemented")
         if use_rnnp:
             raise NotImplementedError("CRDNN: use_rnnp=True is not implemented")
-        if rnn_layers > 0 and rnn_class is not LSTM:
+        if rnn_layers > 0 and rnn_class is not LSTM and rnn_class is not SLiGRU:
             name = getattr(rnn_class, "__name__", "LiGRU (the reference's default)" if rnn_class is None else repr(rnn_class))
             raise NotImplementedError(f"CRDNN: rnn_class {name} is not implemented (speechbrain.nnet.RNN.LSTM is)")
         if rnn_layers > 0 and rnn_neurons > native.RNN_MAX_HIDDEN:
@@ -154,8 +156,8 @@ class CRDNN(Sequential):
                         layer_name="time_pooling")
             self.time_pool = int(time_pooling_size)
         if rnn_layers > 0:
-            self.append(LSTM(hidden_size=rnn_neurons, input_shape=shape, num_layers=rnn_layers, dropout=dropout,
-                             bidirectional=rnn_bidirectional, re_init=rnn_re_init), layer_name="RNN")
+            self.append(rnn_class(hidden_size=rnn_neurons, input_shape=shape, num_layers=rnn_layers, dropout=dropout,
+                                  bidirectional=rnn_bidirectional, re_init=rnn_re_init), layer_name="RNN")
             shape = [None, None, rnn_neurons * (2 if rnn_bidirectional else 1)]
         if dnn_blocks > 0:
             self.append(Sequential(input_shape=shape), layer_name="DNN")
@@ -202,6 +204,12 @@ class CRDNN(Sequential):
         if x.dim() == 4:
             x = x.reshape(x.shape[0], x.shape[1], x.shape[2] * x.shape[3])
         outs = []
+        if isinstance(self["RNN"], SLiGRU):  # the feed-forward contraction follows crdnn_precision(); the recurrence is fp32
+            for layer in self["RNN"].rnn:
+                with native.precision_scope(native.crdnn_precision()):
+                    x = layer(x)
+                outs.append(x)
+            return (x, outs) if return_layers else x
         for w_ih, w_hh, b_ih, b_hh in self._rnn_weights():
             B, T, _ = x.shape
             D, H = w_hh.shape[0], w_hh.shape[2]
@@ -221,7 +229,8 @@ class CRDNN(Sequential):
             x = self.cnn_forward(x)
         if "RNN" in self:
             x, layers = self.rnn_forward(x, return_layers=True)
-            stages.update({f"lstm_layer{i}": y for i, y in enumerate(layers)})
+            key = "rnn_layer" if isinstance(self["RNN"], SLiGRU) else "lstm_layer"
+            stages.update({f"{key}{i}": y for i, y in enumerate(layers)})
         if "DNN" in self:
             for i, block in enumerate(self["DNN"].values()):
                 x = block(x)

@@ -225,6 +225,8 @@ def _declare(lib):
         "sbk_rnn_whh_bf16_image": ([p, p, ctypes.c_size_t, i, i, p], c_int),
         "sbk_rnn_layer_bf16_workspace_bytes": ([i, i, i], ctypes.c_size_t),
         "sbk_rnn_layer_bf16": ([p, p, ctypes.c_size_t] + [p] * 8 + [ctypes.c_size_t] + [i] * 5 + [p], c_int),
+        "sbk_sligru_layer_workspace_bytes": ([i, i, i], ctypes.c_size_t),
+        "sbk_sligru_layer_f32": ([p] * 8 + [ctypes.c_size_t] + [i] * 5 + [p], c_int),
         "sbk_crdnn_conv1_f32": ([p] * 6 + [i, i, i, i, f, f, p], c_int),
         "sbk_crdnn_im2col_f32": ([p, p, i, i, i, i, i, i, p], c_int),
         "sbk_crdnn_norm_pool_f32": ([p] * 4 + [i] * 6 + [f, f, p], c_int),
@@ -1579,6 +1581,43 @@ def rnn_layer(xp, w_hh, b_ih=None, b_hh=None, h0=None, c0=None, route=0):
     _chk(lib.sbk_rnn_layer_f32(_p(xp), _p(w_hh), _p(b_ih), _p(b_hh), _p(h0), _p(c0), _p(out), _p(hn), _p(cn), B, T, H, D,
                                RNN_LSTM, int(route), _stream(xp)), "sbk_rnn_layer_f32")
     return out, hn, cn
+
+
+SLIGRU_ACTS = {"relu": 0, "tanh": 1, "sin": 2, "leaky_relu": 3}  # SBK_SLIGRU_*
+
+
+def sligru_layer(xp, u, ln_gamma=None, ln_beta=None, h0=None, act="relu", D=None):
+    """One SLi-GRU layer for every utterance and direction (sbk_sligru_layer_f32): xp [B,T,2H] the normalised feed-forward term
+    (one tensor for both directions: the backward scan reads it from the last frame), u [2H,H], ln_gamma / ln_beta [2H] or None
+    (the recurrent LayerNorm's affine), h0 [D,B,H] or None (zeros), act one of SLIGRU_ACTS, D the number of directions (neither
+    xp nor u shows it: h0's when h0 is given, else 1) -> (out [B,T,D*H], hn [D,B,H]); direction 1 runs backwards in time and
+    writes at its own t.  The recurrent product is fp32 under every precision."""
+    lib = load()
+    if D is None:
+        D = 1 if h0 is None else h0.shape[0]
+    if xp.ndim != 3 or u.ndim != 2:
+        raise SbkError(f"sligru_layer: xp {tuple(xp.shape)} is not [B,T,2H] or u {tuple(u.shape)} is not [2H,H]")
+    B, T, G = xp.shape
+    H = u.shape[1]
+    if G != 2 * H or u.shape[0] != 2 * H:
+        raise SbkError(f"sligru_layer: xp {tuple(xp.shape)} and u {tuple(u.shape)} do not agree on H")
+    if act not in SLIGRU_ACTS:
+        raise SbkError(f"sligru_layer: act {act!r} is not one of {sorted(SLIGRU_ACTS)}")
+    for name, t, want in (("ln_gamma", ln_gamma, (2 * H,)), ("ln_beta", ln_beta, (2 * H,)), ("h0", h0, (D, B, H))):
+        if t is not None and tuple(t.shape) != want:
+            raise SbkError(f"sligru_layer: {name} {tuple(t.shape)} is not {want}")
+    _dev_ok(xp, u, ln_gamma, ln_beta, h0)
+    for t in (xp, u, ln_gamma, ln_beta, h0):
+        if t is not None:
+            _f32(t)
+    out = torch.empty(B, T, D * H, dtype=torch.float32, device=xp.device)
+    hn = torch.empty(D, B, H, dtype=torch.float32, device=xp.device)
+    nbytes = lib.sbk_sligru_layer_workspace_bytes(B, H, D)
+    st = _stream(xp)
+    with _Workspace(nbytes, xp.device, per_stream=True) as ws:  # (the raw recurrent product of one step)
+        _chk(lib.sbk_sligru_layer_f32(_p(xp), _p(u), _p(ln_gamma), _p(ln_beta), _p(h0), _p(out), _p(hn), ws.ptr, nbytes,
+                                      B, T, H, D, SLIGRU_ACTS[act], st), "sbk_sligru_layer_f32")
+    return out, hn
 
 
 # ------------------------------------------------------------------ GRU attention decoder (csrc/attn_rnn.hip)

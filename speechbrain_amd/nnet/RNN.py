@@ -7,6 +7,9 @@ the recurrent part of a CRDNN encoder: there this class holds the parameters and
 (sbk_rnn_layer_f32 through ``direction_weights``); called on its own it raises.  ``GRU``, ``RNN`` and ``LiGRU`` are not
 implemented.
 
+``SLiGRU`` / ``SLiGRU_Layer`` (nnet/RNN.py:1430-1804) are the recurrent stack of the ``train_BPE_1000_sligru.yaml`` CRDNN: a
+folded feed-forward contraction per layer, then the batched recurrence with its per-step LayerNorm (csrc/sligru.hip).
+
 ``GRUCell`` and ``AttentionalRNNDecoder`` (nnet/RNN.py:539-648, :755-1013) are the decoder of the CRDNN seq2seq recipes: GRU
 cells with location-aware or content-based attention (csrc/attn_rnn.hip)."""
 import torch
@@ -86,6 +89,107 @@ class RNN(_NotImplementedRNN):
 
 class LiGRU(_NotImplementedRNN):
     pass
+
+
+class SLiGRU_Layer(torch.nn.Module):
+    """nnet/RNN.py:1623-1804 at inference: the parameter holder of one SLi-GRU layer under the reference's names (``w.weight``,
+    ``u.weight``, ``layer_norm.*``, ``norm.*``, ``h_init``, ``drop_mask_te``) and its forward pass on the device.  The
+    feed-forward term is ONE contraction for both directions (the reference's flipped copy of x goes through the same per-frame
+    map, so the backward scan reads the same tensor from its end); an eval-mode BatchNorm1d is folded into the rows of ``w`` and
+    its shift is the contraction's bias, a LayerNorm is one pass behind it.  The recurrence is native.sligru_layer.  The
+    recurrent dropout mask is the reference's evaluation mask (ones); the 16000 pre-sampled training masks are not allocated."""
+
+    def __init__(self, input_size, hidden_size, num_layers, batch_size, dropout=0.0, nonlinearity="relu",
+                 ff_normalization="batchnorm", recurrent_elementwise_affine=False, bias=True, bidirectional=False):
+        super().__init__()
+        self.hidden_size, self.input_size = int(hidden_size), int(input_size)
+        self.bidirectional, self.dropout, self.bias = bidirectional, dropout, bias
+        if self.hidden_size > native.RNN_MAX_HIDDEN:
+            raise NotImplementedError(f"SLiGRU: hidden_size={hidden_size} exceeds the limit of {native.RNN_MAX_HIDDEN}")
+        self.w = torch.nn.Linear(self.input_size, 2 * self.hidden_size, bias=False)
+        self.u = torch.nn.Linear(self.hidden_size, 2 * self.hidden_size, bias=False)
+        self.layer_norm = torch.nn.LayerNorm(2 * self.hidden_size, elementwise_affine=recurrent_elementwise_affine)
+        if ff_normalization == "batchnorm":
+            self.norm = torch.nn.BatchNorm1d(2 * self.hidden_size, momentum=0.05)
+        else:  # "layernorm", and every other string (the reference normalises with a LayerNorm then too)
+            self.norm = torch.nn.LayerNorm(2 * self.hidden_size)
+        if not self.bias:
+            self.norm.bias.data.fill_(0)
+            self.norm.bias.requires_grad = False
+        self.register_buffer("h_init", torch.zeros(1, self.hidden_size))
+        self.register_buffer("drop_mask_te", torch.tensor([1.0]).float())
+        # the reference's rule: tanh, sin and leaky_relu by name, everything else is ReLU
+        self.act = nonlinearity if nonlinearity in ("tanh", "sin", "leaky_relu") else "relu"
+        self._folded = native.Derived()
+
+    def _fold(self):
+        """(W', b') with BatchNorm_eval(x w^T) = x W'^T + b'."""
+        n = self.norm
+        scale = n.weight.detach().float() / torch.sqrt(n.running_var.float() + n.eps)
+        return ((self.w.weight.detach().float() * scale[:, None]).contiguous(),
+                (n.bias.detach().float() - n.running_mean.float() * scale).contiguous())
+
+    @torch.no_grad()
+    def forward(self, x, hx=None):
+        """x [B,T,in] -> h [B,T,D*H]."""
+        if hx is not None:
+            raise NotImplementedError("SLiGRU: hx (a starting hidden state) is not implemented; the layers start from h_init")
+        if self.training:  # (batch statistics and sampled recurrent dropout masks are the reference's training behaviour)
+            raise NotImplementedError("SLiGRU: training mode is not implemented (inference only: call .eval() first)")
+        x = x.float().contiguous()
+        n = self.norm
+        if isinstance(n, torch.nn.BatchNorm1d):
+            wf, bf = self._folded.get([self.w.weight, n.weight, n.bias, n.running_mean, n.running_var], self._fold, extra=(n.eps,))
+            xp = native.gemm_nt(x, wf, bf)
+        else:
+            xp = native.layernorm(native.gemm_nt(x, self.w.weight.detach()), n.weight.detach(), n.bias.detach(), n.eps)
+        ln = self.layer_norm
+        affine = ln.weight is not None
+        out, _ = native.sligru_layer(xp, self.u.weight.detach(), ln.weight.detach() if affine else None,
+                                     ln.bias.detach() if affine else None, act=self.act, D=2 if self.bidirectional else 1)
+        return out
+
+
+class SLiGRU(torch.nn.Module):
+    """nnet/RNN.py:1430-1620 with the reference's constructor arguments and state-dict keys (``rnn.{i}.w.weight``, ...):
+    [B,T,in] (4-D inputs are flattened) -> (output [B,T,D*H], hh in the reference's layout).  Inference semantics only."""
+
+    def __init__(self, hidden_size, input_shape, nonlinearity="relu", ff_normalization="batchnorm",
+                 recurrent_elementwise_affine=False, num_layers=1, bias=True, dropout=0.0, re_init=True, bidirectional=False):
+        super().__init__()
+        self.hidden_size, self.nonlinearity, self.num_layers = hidden_size, nonlinearity, num_layers
+        self.ff_normalization, self.recurrent_elementwise_affine = ff_normalization, recurrent_elementwise_affine
+        self.bias, self.dropout, self.re_init, self.bidirectional = bias, dropout, re_init, bidirectional
+        self.reshape = len(input_shape) > 3
+        self.fea_dim = float(torch.prod(torch.tensor(input_shape[2:])))
+        self.batch_size = input_shape[0]
+        self.rnn = torch.nn.ModuleList([])
+        dim = self.fea_dim
+        for _ in range(num_layers):
+            self.rnn.append(SLiGRU_Layer(dim, hidden_size, num_layers, self.batch_size, dropout=dropout, nonlinearity=nonlinearity,
+                                         ff_normalization=ff_normalization,
+                                         recurrent_elementwise_affine=recurrent_elementwise_affine, bias=bias,
+                                         bidirectional=bidirectional))
+            dim = hidden_size * 2 if bidirectional else hidden_size
+        if re_init:
+            _rnn_init(self.rnn)
+
+    @torch.no_grad()
+    def forward(self, x, hx=None, return_layers=False):
+        """x [B,T,in] -> (output, hh); hh as nnet/RNN.py:1612-1618: the last FRAME of every layer's output, stacked and
+        reshaped the reference's way.  ``return_layers``: also each layer's output."""
+        if hx is not None:
+            raise NotImplementedError("SLiGRU: hx (a starting hidden state) is not implemented; the layers start from h_init")
+        if self.reshape and x.ndim == 4:
+            x = x.reshape(x.shape[0], x.shape[1], x.shape[2] * x.shape[3])
+        h, outs = [], []
+        for layer in self.rnn:
+            x = layer(x)
+            outs.append(x)
+            h.append(x[:, -1, :])
+        h = torch.stack(h, dim=1)
+        h = h.reshape(h.shape[1] * 2, h.shape[0], self.hidden_size) if self.bidirectional else h.transpose(0, 1)
+        return (x, h, outs) if return_layers else (x, h)
 
 
 class GRUCell(torch.nn.Module):

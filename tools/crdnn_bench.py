@@ -21,6 +21,9 @@ time ends the run (nothing more is started on the GPU) and is recorded.  ``--hea
 a ``bench.py`` run into the result.  One JSON line per run, also written to profiles/crdnn_bench.json.  A job for a GPU visit.
 
     python tools/crdnn_bench.py [--steps 3] [--warmup 1] [--headline this=a.json ...]
+    python tools/crdnn_bench.py --rnn sligru         # the SLi-GRU layer of train_BPE_1000_sligru.yaml: us per launch of its two
+                                                     # launches, the layer next to the LSTM step and to the torch loop of the
+                                                     # reference, the encoder with rnn_class SLiGRU; joins the file as "sligru"
     python tools/crdnn_bench.py --precision bf16     # the fp32 and bf16 forms alternating: us per recurrent step at B 32 and B 1,
                                                      # ms per batch, the recurrence's share; joins the file as "precision_bf16"
 """
@@ -288,6 +291,86 @@ def bf16_step(args):
     return res
 
 
+def sligru_step(args):
+    """``--rnn sligru``: the SLi-GRU layer of train_BPE_1000_sligru.yaml (H 1024, D 2) in ONE process -- its two launches per step
+    (us each, from the library's per-launch timing) and the layer (us per step, HIP events) next to the LSTM step of this tree
+    and to the torch composition of the reference's loop, alternating, at B 32 and B 1; then the encoder from PCM."""
+    import torch
+
+    from speechbrain_amd import native
+    from speechbrain_amd.lobes.features import Fbank
+    from speechbrain_amd.lobes.models.CRDNN import CRDNN
+    from speechbrain_amd.nnet.RNN import SLiGRU
+
+    native.load()
+    gen = torch.Generator().manual_seed(9)
+    res = {"layer": []}
+    u = (torch.nn.init.orthogonal_(torch.empty(2 * H, H), generator=gen)).cuda()
+    w_hh = (torch.randn(2, 4 * H, H, generator=gen) / H ** 0.5).cuda()
+    b_ih, b_hh = torch.randn(2, 4 * H, generator=gen).cuda(), torch.randn(2, 4 * H, generator=gen).cuda()
+
+    def torch_loop(xp):  # nnet/RNN.py:1743-1804 on the device: the flipped batch under the batch, one loop over time
+        w = torch.cat([xp, xp.flip(1)], dim=0)
+        h = torch.zeros(w.shape[0], H, device=w.device)
+        hs = []
+        for k in range(w.shape[1]):
+            a, z = (w[:, k] + torch.nn.functional.layer_norm(h @ u.t(), (2 * H,))).chunk(2, 1)
+            z = torch.sigmoid(z)
+            h = z * h + (1 - z) * torch.relu(a)
+            hs.append(h)
+        o = torch.stack(hs, dim=1)
+        return torch.cat([o[:xp.shape[0]], o[xp.shape[0]:].flip(1)], dim=2)
+
+    for B in (32, 1):
+        xp = torch.randn(B, T_RNN, 2 * H, generator=gen).cuda()
+        xp4 = torch.randn(B, T_RNN, 2, 4 * H, generator=gen).cuda()
+        fns = {"sligru": lambda: native.sligru_layer(xp, u, D=2)[0], "lstm": lambda: native.rnn_layer(xp4, w_hh, b_ih, b_hh)[0],
+               "torch_loop": lambda: torch_loop(xp)}
+        runs = {k: [] for k in fns}
+        with torch.no_grad():
+            for _ in range(3):  # alternate
+                for k, fn in fns.items():
+                    runs[k].append(med(event_ms(torch, fn, args.steps, args.warmup)))
+            diff = float((fns["sligru"]() - fns["torch_loop"]()).abs().max())
+            native.prof_reset()
+            native.prof_enable(True)
+            fns["sligru"]()
+            torch.cuda.synchronize()
+            native.prof_enable(False)
+            rep = native.prof_report()
+        us = {k: round(med(sorted(v)) * 1e3 / T_RNN, 2) for k, v in runs.items()}
+        per = {k: round(rep[k]["ms"] * 1e3 / rep[k]["count"], 2) for k in ("sligru_product", "sligru_norm_cell")}
+        res["layer"].append({
+            "B": B, "T": T_RNN, "H": H, "D": 2, "product_us_per_launch": per["sligru_product"],
+            "norm_cell_us_per_launch": per["sligru_norm_cell"], "sligru_layer_us_per_step": us["sligru"],
+            "lstm_us_per_step": us["lstm"], "torch_loop_us_per_step": us["torch_loop"],
+            "ms_repeated": {k: [round(v, 3) for v in runs[k]] for k in runs}, "max_abs_diff_vs_torch_loop": diff,
+            "expectation the product launch takes no longer than the LSTM step": "met" if per["sligru_product"] <= us["lstm"] else "missed",
+            "expectation faster than the torch loop": "met" if us["sligru"] < us["torch_loop"] else "missed"})
+    B = args.batch
+    torch.manual_seed(3)
+    m = CRDNN(input_shape=[None, None, N_MELS], cnn_blocks=2, cnn_channels=[128, 256], inter_layer_pooling_size=[2, 2],
+              time_pooling=True, time_pooling_size=4, rnn_class=SLiGRU, rnn_layers=4, rnn_neurons=H, rnn_bidirectional=True,
+              rnn_re_init=True, dnn_blocks=2, dnn_neurons=512).to("cuda:0").eval()
+    fbank = Fbank(sample_rate=16000, n_fft=400, n_mels=N_MELS).to("cuda:0")
+    wav = (0.1 * torch.randn(B, 160000, generator=torch.Generator().manual_seed(5))).cuda()
+    with torch.no_grad():
+        run = lambda: m(fbank(wav))  # noqa: E731
+        ms = event_ms(torch, run, args.steps, args.warmup)
+        native.prof_reset()
+        native.prof_enable(True)
+        run()
+        torch.cuda.synchronize()
+        native.prof_enable(False)
+        rep = native.prof_report()
+    total = sum(v["ms"] for v in rep.values())
+    res["encoder"] = {"batch": B, "seconds": 10.0, "p50_ms": round(med(ms), 2), "min_ms": round(ms[0], 2), "max_ms": round(ms[-1], 2),
+                      "kernel_ms": round(total, 2),
+                      "share_recurrence": round(sum(v["ms"] for k, v in rep.items() if k.startswith("sligru_")) / total, 4),
+                      "kernels_ms": {k: [v["count"], round(v["ms"], 3)] for k, v in sorted(rep.items(), key=lambda kv: -kv[1]["ms"])}}
+    return res
+
+
 STEPS = {"encoder": encoder_step, "convs": convs_step, "lstm": lstm_step, "torch": torch_step}
 
 
@@ -311,20 +394,30 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--precision", default="fp32", choices=("fp32", "bf16"),
                     help="bf16: only the fp32 / bf16 comparison (recurrent step, encoder), recorded under the key precision_bf16")
+    ap.add_argument("--rnn", default="lstm", choices=("lstm", "sligru"),
+                    help="sligru: only the SLi-GRU comparison (its two launches, the LSTM step, the torch loop, the encoder), "
+                         "recorded under the key sligru")
     ap.add_argument("--step", default=None, help="(internal) run one GPU step in this process: " + " | ".join(STEPS))
     ap.add_argument("--headline", action="append", default=[], metavar="NAME=FILE",
                     help="a file whose last line is a bench.py JSON result, recorded under bench_py[NAME]")
     args = ap.parse_args()
     if args.step:
-        print(json.dumps(dict(STEPS, bf16=bf16_step)[args.step](args)))
+        print(json.dumps(dict(STEPS, bf16=bf16_step, sligru=sligru_step)[args.step](args)))
         return
     path = os.path.join(ROOT, "profiles", "crdnn_bench.json")
-    if args.precision == "bf16":  # one step; its result joins the recorded fp32 run under a key of its own
-        out, err = child("bf16", args)
+    if args.precision == "bf16" or args.rnn == "sligru":  # one step; its result joins the recorded fp32 run under a key of its own
+        step, key = ("bf16", "precision_bf16") if args.precision == "bf16" else ("sligru", "sligru")
+        out, err = child(step, args)
         with open(path) as f:
             res = json.loads(f.read().strip().splitlines()[-1])
-        res["precision_bf16"] = out if err is None else {"failed": err}
-        print(json.dumps(res["precision_bf16"]))
+        res[key] = out if err is None else {"failed": err}
+        for item in args.headline if key == "sligru" else []:  # (bench.py of this tree and of the parent, as below)
+            name, file = item.split("=", 1)
+            with open(file) as f:
+                full = json.loads([ln for ln in f.read().splitlines() if ln.strip().startswith("{")][-1])
+            res[key].setdefault("bench_py", {}).setdefault(name.rstrip("0123456789_"), []).append(
+                {k: full.get(k) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step")})
+        print(json.dumps(res[key]))
         with open(path, "w") as f:
             f.write(json.dumps(res) + "\n")
         sys.exit(1 if err else 0)
