@@ -595,6 +595,29 @@ size_t sbk_sligru_layer_workspace_bytes(int B, int H, int D);
 int sbk_sligru_layer_f32(const float* xp, const float* u, const float* ln_gamma, const float* ln_beta, const float* h0, float* out,
                          float* hn, void* workspace, size_t workspace_bytes, int B, int T, int H, int D, int act,
                          sbk_stream_t stream);
+/* The same layer with the product h_{t-1} . u^T on v_mfma_f32_16x16x32_bf16 (csrc/sligru_bf16.hip; the opt-in precision "bf16";
+ * additive entries, ABI 11 unchanged).  Rounded to bf16 (nearest even): u and h_{t-1}, and only as operands of that product.
+ * fp32: the accumulators, the raw product, the LayerNorm statistics and affine, xp, the cell (its sigmoid(z) h_{t-1} term reads
+ * the fp32 h_{t-1}), and the h written to out and hn.  Operands, semantics and limits as sbk_sligru_layer_f32, except:
+ *   u_image     sbk_sligru_u_bf16_image_bytes(H) bytes, 16-byte aligned, written by sbk_sligru_u_bf16_image from u [2H,H] (once
+ *               per weight): bf16 [ceil(H/8) slices of 8 units][ceil(H/32) chunks of 32 k][64 lanes][8], lane l of a chunk holding
+ *               the 8 consecutive k of MFMA column l & 15 = gate * 8 + unit, k block l >> 4; zeros past H (units and k).
+ *   workspace   sbk_sligru_layer_bf16_workspace_bytes(B, H, D) bytes, 16-byte aligned, the caller's, contents undefined before
+ *               and after: the fp32 raw product of one step [D*B,2H] (rounded up to 16 bytes), then two bf16 copies of the state
+ *               in the operand order of the product, [2][ceil(D*B/16) row tiles][ceil(H/32) chunks][64 lanes][8] with lane =
+ *               row mod 16 + 16 * (k / 8 mod 4), written by the norm-and-cell pass beside the fp32 h and read by the next step's
+ *               product (ping-pong); the entry fills them from h0 (or zeros) first.
+ * Two launches per step, as the fp32 layer: the product (8 units x 2 gates and 32 rows per workgroup, its waves taking contiguous
+ * quarters of the chunks and meeting in LDS in wave order) and the norm-and-cell pass (one workgroup per row, a thread holding 8
+ * consecutive units).  No atomics, fixed summation order: two runs, and two streams, give the same bits.  SBK_EINVAL names a bad
+ * shape, an image whose size is not that of H, a short workspace and a pointer that is not 16-byte aligned.  The size queries
+ * return 0 for a shape outside the limits. */
+size_t sbk_sligru_u_bf16_image_bytes(int H);
+int sbk_sligru_u_bf16_image(const float* u, void* image, size_t image_bytes, int H, sbk_stream_t stream);
+size_t sbk_sligru_layer_bf16_workspace_bytes(int B, int H, int D);
+int sbk_sligru_layer_bf16(const float* xp, const void* u_image, size_t image_bytes, const float* ln_gamma, const float* ln_beta,
+                          const float* h0, float* out, float* hn, void* workspace, size_t workspace_bytes, int B, int T, int H,
+                          int D, int act, sbk_stream_t stream);
 
 /* ---- The convolution blocks of a CRDNN encoder (csrc/crdnn.hip; additive entries, ABI 11 unchanged)
  * lobes/models/CRDNN.py:199-278: [reflect-pad(1) + Conv2d(3x3, stride 1, bias) (nnet/CNN.py:654-751) -> LayerNorm over (F,C)

@@ -13,7 +13,8 @@ On the device (csrc/crdnn.hip, csrc/rnn.hip):
               in ONE pass that writes only the pooled tensor (native.crdnn_norm_pool)
   RNN         per layer ONE contraction x . [W_ih | W_ih_reverse]^T for both directions, then native.rnn_layer
               (rnn_class SLiGRU: nnet.RNN.SLiGRU_Layer per layer -- the folded contraction, then native.sligru_layer, whose
-              recurrent product stays fp32 under every precision; its stages are recorded as ``rnn_layer{i}``)
+              recurrent product runs on the bf16 matrix cores under "bf16" (sbk_sligru_layer_bf16) and in fp32 under every other
+              precision; its stages are recorded as ``rnn_layer{i}``)
   DNN_Block   Linear with the BatchNorm1d running statistics folded in and LeakyReLU in the GEMM epilogue
 Under the ambient precision "bf16" (native.crdnn_precision) the patch-matrix contractions, the LSTM input projections and the
 DNN blocks take gemm_nt's bf16 route (fp32 activations rounded on load) and the recurrence runs sbk_rnn_layer_bf16; the first

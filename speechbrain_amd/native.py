@@ -227,6 +227,10 @@ def _declare(lib):
         "sbk_rnn_layer_bf16": ([p, p, ctypes.c_size_t] + [p] * 8 + [ctypes.c_size_t] + [i] * 5 + [p], c_int),
         "sbk_sligru_layer_workspace_bytes": ([i, i, i], ctypes.c_size_t),
         "sbk_sligru_layer_f32": ([p] * 8 + [ctypes.c_size_t] + [i] * 5 + [p], c_int),
+        "sbk_sligru_u_bf16_image_bytes": ([i], ctypes.c_size_t),
+        "sbk_sligru_u_bf16_image": ([p, p, ctypes.c_size_t, i, p], c_int),
+        "sbk_sligru_layer_bf16_workspace_bytes": ([i, i, i], ctypes.c_size_t),
+        "sbk_sligru_layer_bf16": ([p, p, ctypes.c_size_t] + [p] * 6 + [ctypes.c_size_t] + [i] * 5 + [p], c_int),
         "sbk_crdnn_conv1_f32": ([p] * 6 + [i, i, i, i, f, f, p], c_int),
         "sbk_crdnn_im2col_f32": ([p, p, i, i, i, i, i, i, p], c_int),
         "sbk_crdnn_norm_pool_f32": ([p] * 4 + [i] * 6 + [f, f, p], c_int),
@@ -830,6 +834,11 @@ def _make_image(w: torch.Tensor, kind: str):
         nbytes = lib.sbk_rnn_whh_bf16_image_bytes(H, D)  # (0 for a shape outside the limits: the entry below names it)
         out = torch.empty(nbytes // 2, dtype=torch.int16, device=w.device)
         _chk(lib.sbk_rnn_whh_bf16_image(_p(w2), _p(out), nbytes, H, D, _stream(w2)), "sbk_rnn_whh_bf16_image")
+    elif kind == "sligru_u":  # u [2H,H] in the operand order of sbk_sligru_layer_bf16
+        H = w2.shape[1]
+        nbytes = lib.sbk_sligru_u_bf16_image_bytes(H)  # (0 for a width outside the limits: the entry below names it)
+        out = torch.empty(nbytes // 2, dtype=torch.int16, device=w.device)
+        _chk(lib.sbk_sligru_u_bf16_image(_p(w2), _p(out), nbytes, H, _stream(w2)), "sbk_sligru_u_bf16_image")
     elif kind == "bf16k32":  # bf16 with every row zero-padded to a multiple of 32 (sbk_w2v_posconv_bf16's K step)
         w2 = torch.nn.functional.pad(w2, (0, -w2.shape[1] % 32))
         out = torch.empty(w2.shape, dtype=torch.int16, device=w.device)
@@ -845,6 +854,7 @@ def lp_weight(w: torch.Tensor, kind: str = "bf16"):
     """The reduced-precision image of a weight matrix ("bf16" / "fp16": int16 bits; "fp8": (uint8 e4m3 bits, w_scale);
     "bf16k32": bf16 bits with every row zero-padded to a multiple of 32, the filter image of sbk_w2v_posconv_bf16;
     "rnn_whh": w_hh [D,4H,H] as bf16 bits in the operand order of sbk_rnn_layer_bf16 (sbk_rnn_whh_bf16_image);
+    "sligru_u": u [2H,H] as bf16 bits in the operand order of sbk_sligru_layer_bf16 (sbk_sligru_u_bf16_image);
     "x3": the exact three-piece bf16 split [N, K/32, 3, 32] of sbk_split_bf16x3 -- not reduced: the pieces sum to w),
     cached for the lifetime of THAT tensor object: the entry holds a weak reference to its source and is used only while
     ``ref() is w`` and the version counter is unchanged (a freed model's addresses are commonly handed to the next
@@ -1591,7 +1601,11 @@ def sligru_layer(xp, u, ln_gamma=None, ln_beta=None, h0=None, act="relu", D=None
     (one tensor for both directions: the backward scan reads it from the last frame), u [2H,H], ln_gamma / ln_beta [2H] or None
     (the recurrent LayerNorm's affine), h0 [D,B,H] or None (zeros), act one of SLIGRU_ACTS, D the number of directions (neither
     xp nor u shows it: h0's when h0 is given, else 1) -> (out [B,T,D*H], hn [D,B,H]); direction 1 runs backwards in time and
-    writes at its own t.  The recurrent product is fp32 under every precision."""
+    writes at its own t.
+    Under ``precision() == "bf16"`` the product h . u^T runs on the bf16 matrix cores (sbk_sligru_layer_bf16): u and h_{t-1} are
+    rounded to bf16 as its operands only; the raw product, the LayerNorm, xp, the cell and the h that is returned stay fp32.  u's
+    operand image is made once per weight tensor (``lp_weight(u, "sligru_u")``: pass the parameter or a view of it, not a fresh
+    copy per call).  Every other precision takes the fp32 entry."""
     lib = load()
     if D is None:
         D = 1 if h0 is None else h0.shape[0]
@@ -1612,8 +1626,15 @@ def sligru_layer(xp, u, ln_gamma=None, ln_beta=None, h0=None, act="relu", D=None
             _f32(t)
     out = torch.empty(B, T, D * H, dtype=torch.float32, device=xp.device)
     hn = torch.empty(D, B, H, dtype=torch.float32, device=xp.device)
-    nbytes = lib.sbk_sligru_layer_workspace_bytes(B, H, D)
     st = _stream(xp)
+    if precision() == "bf16":  # opt-in: the product on the bf16 matrix cores, u's image made once per weight
+        img = lp_weight(u, "sligru_u")
+        nbytes = lib.sbk_sligru_layer_bf16_workspace_bytes(B, H, D)
+        with _Workspace(nbytes, xp.device, per_stream=True) as ws:  # (the raw product of one step and the bf16 shadows of the state)
+            _chk(lib.sbk_sligru_layer_bf16(_p(xp), _p(img), img.numel() * 2, _p(ln_gamma), _p(ln_beta), _p(h0), _p(out), _p(hn),
+                                           ws.ptr, nbytes, B, T, H, D, SLIGRU_ACTS[act], st), "sbk_sligru_layer_bf16")
+        return out, hn
+    nbytes = lib.sbk_sligru_layer_workspace_bytes(B, H, D)
     with _Workspace(nbytes, xp.device, per_stream=True) as ws:  # (the raw recurrent product of one step)
         _chk(lib.sbk_sligru_layer_f32(_p(xp), _p(u), _p(ln_gamma), _p(ln_beta), _p(h0), _p(out), _p(hn), ws.ptr, nbytes,
                                       B, T, H, D, SLIGRU_ACTS[act], st), "sbk_sligru_layer_f32")

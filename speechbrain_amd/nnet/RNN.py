@@ -145,7 +145,8 @@ class SLiGRU_Layer(torch.nn.Module):
             xp = native.layernorm(native.gemm_nt(x, self.w.weight.detach()), n.weight.detach(), n.bias.detach(), n.eps)
         ln = self.layer_norm
         affine = ln.weight is not None
-        out, _ = native.sligru_layer(xp, self.u.weight.detach(), ln.weight.detach() if affine else None,
+        # (u as the Parameter itself: its bf16 operand image is cached per tensor object, and .detach() makes a new one per call)
+        out, _ = native.sligru_layer(xp, self.u.weight, ln.weight.detach() if affine else None,
                                      ln.bias.detach() if affine else None, act=self.act, D=2 if self.bidirectional else 1)
         return out
 

@@ -26,6 +26,9 @@ a ``bench.py`` run into the result.  One JSON line per run, also written to prof
                                                      # reference, the encoder with rnn_class SLiGRU; joins the file as "sligru"
     python tools/crdnn_bench.py --precision bf16     # the fp32 and bf16 forms alternating: us per recurrent step at B 32 and B 1,
                                                      # ms per batch, the recurrence's share; joins the file as "precision_bf16"
+    python tools/crdnn_bench.py --rnn sligru --precision bf16   # the fp32 and bf16 forms of the SLi-GRU layer alternating: us per
+                                                     # launch and per step at B 32 and B 1, the encoder under "bf16" with the
+                                                     # recurrence held to fp32 and with the bf16 kernel; joins as "sligru_bf16"
 """
 import argparse
 import json
@@ -371,6 +374,102 @@ def sligru_step(args):
     return res
 
 
+def sligru_bf16_step(args):
+    """``--rnn sligru --precision bf16``: the fp32 and the bf16 form of the SLi-GRU layer (H 1024, D 2, T' 250) alternating in ONE
+    process at B 32 and B 1 -- us per launch of both launches of each form (the library's per-launch timing) and us per step
+    (HIP events) -- then the encoder from PCM under "bf16", with the recurrence held to fp32 and with sbk_sligru_layer_bf16,
+    alternating: ms per batch and the recurrence's share of kernel time."""
+    import torch
+
+    from speechbrain_amd import native
+    from speechbrain_amd.lobes.features import Fbank
+    from speechbrain_amd.lobes.models.CRDNN import CRDNN
+    from speechbrain_amd.nnet.RNN import SLiGRU
+
+    native.load()
+    gen = torch.Generator().manual_seed(9)
+    precisions = ("fp32", "bf16")
+    tags = {"fp32": ("sligru_product", "sligru_norm_cell"), "bf16": ("sligru_product_bf16", "sligru_norm_cell_bf16")}
+    res = {"layer": []}
+    u = (torch.nn.init.orthogonal_(torch.empty(2 * H, H), generator=gen)).cuda()
+
+    def profiled(fn):
+        native.prof_reset()
+        native.prof_enable(True)
+        with torch.no_grad():
+            fn()
+        torch.cuda.synchronize()
+        native.prof_enable(False)
+        return native.prof_report()
+
+    for B in (32, 1):
+        xp = torch.randn(B, T_RNN, 2 * H, generator=gen).cuda()
+
+        def layer(p):
+            with native.precision_scope(p):
+                return native.sligru_layer(xp, u, D=2)[0]
+
+        runs = {p: [] for p in precisions}
+        for _ in range(3):  # alternate
+            for p in precisions:
+                runs[p].append(med(event_ms(torch, lambda: layer(p), args.steps, args.warmup)))
+        us = {p: round(med(sorted(runs[p])) * 1e3 / T_RNN, 2) for p in precisions}
+        per = {}
+        for p in precisions:
+            rep = profiled(lambda: layer(p))
+            per[p] = [round(rep[k]["ms"] * 1e3 / rep[k]["count"], 2) for k in tags[p]]
+        diff = float((layer("bf16") - layer("fp32")).abs().max())
+        res["layer"].append({
+            "B": B, "T": T_RNN, "H": H, "D": 2, "fp32_product_us_per_launch": per["fp32"][0], "fp32_norm_cell_us_per_launch": per["fp32"][1],
+            "bf16_product_us_per_launch": per["bf16"][0], "bf16_norm_cell_us_per_launch": per["bf16"][1],
+            "fp32_us_per_step": us["fp32"], "bf16_us_per_step": us["bf16"],
+            "ms_repeated": {p: [round(v, 3) for v in runs[p]] for p in precisions}, "max_abs_diff_out": diff,
+            "expectation the bf16 product launch is faster": "met" if per["bf16"][0] < per["fp32"][0] else "missed",
+            "expectation the bf16 step is faster": "met" if us["bf16"] < us["fp32"] else "missed"})
+    B = args.batch
+    torch.manual_seed(3)
+    m = CRDNN(input_shape=[None, None, N_MELS], cnn_blocks=2, cnn_channels=[128, 256], inter_layer_pooling_size=[2, 2],
+              time_pooling=True, time_pooling_size=4, rnn_class=SLiGRU, rnn_layers=4, rnn_neurons=H, rnn_bidirectional=True,
+              rnn_re_init=True, dnn_blocks=2, dnn_neurons=512).to("cuda:0").eval()
+    fbank = Fbank(sample_rate=16000, n_fft=400, n_mels=N_MELS).to("cuda:0")
+    wav = (0.1 * torch.randn(B, 160000, generator=torch.Generator().manual_seed(5))).cuda()
+    bf16_layer = native.sligru_layer
+
+    def fp32_layer(*a, **kw):  # the recurrence held to fp32 inside an encoder that is otherwise under "bf16"
+        with native.precision_scope("fp32"):
+            return bf16_layer(*a, **kw)
+
+    def encoder(held):
+        native.sligru_layer = fp32_layer if held else bf16_layer
+        try:
+            with native.precision_scope("bf16"):
+                return m(fbank(wav))
+        finally:
+            native.sligru_layer = bf16_layer
+
+    forms = {"recurrence_fp32": True, "recurrence_bf16": False}
+    enc = {"batch": B, "seconds": 10.0, "precision": "bf16"}
+    with torch.no_grad():
+        ms = {k: [] for k in forms}
+        for _ in range(2):  # alternate
+            for k, held in forms.items():
+                ms[k] += event_ms(torch, lambda: encoder(held), args.steps, args.warmup)
+        for k, held in forms.items():
+            rep = profiled(lambda: encoder(held))
+            total = sum(v["ms"] for v in rep.values())
+            enc[k + "_p50_ms"] = round(med(sorted(ms[k])), 2)
+            enc[k + "_kernel_ms"] = round(total, 2)
+            enc[k + "_share_recurrence"] = round(sum(v["ms"] for n, v in rep.items() if n.startswith("sligru_")) / total, 4)
+            enc[k + "_kernels_ms"] = {n: [v["count"], round(v["ms"], 3)] for n, v in sorted(rep.items(), key=lambda kv: -kv[1]["ms"])}
+        ref = encoder(True)
+        enc["rel_rms_recurrence_bf16_vs_fp32"] = float(((encoder(False) - ref).pow(2).mean() / ref.pow(2).mean()).sqrt())
+    enc["expectation ms per batch is lower with the bf16 recurrence"] = (
+        "met" if enc["recurrence_bf16_p50_ms"] < enc["recurrence_fp32_p50_ms"] else "missed")
+    res["encoder"] = enc
+    res["not_measured"] = "H other than 1024, D 1, B > 32"
+    return res
+
+
 STEPS = {"encoder": encoder_step, "convs": convs_step, "lstm": lstm_step, "torch": torch_step}
 
 
@@ -402,16 +501,19 @@ def main():
                     help="a file whose last line is a bench.py JSON result, recorded under bench_py[NAME]")
     args = ap.parse_args()
     if args.step:
-        print(json.dumps(dict(STEPS, bf16=bf16_step, sligru=sligru_step)[args.step](args)))
+        print(json.dumps(dict(STEPS, bf16=bf16_step, sligru=sligru_step, sligru_bf16=sligru_bf16_step)[args.step](args)))
         return
     path = os.path.join(ROOT, "profiles", "crdnn_bench.json")
     if args.precision == "bf16" or args.rnn == "sligru":  # one step; its result joins the recorded fp32 run under a key of its own
-        step, key = ("bf16", "precision_bf16") if args.precision == "bf16" else ("sligru", "sligru")
+        if args.precision == "bf16" and args.rnn == "sligru":
+            step, key = "sligru_bf16", "sligru_bf16"
+        else:
+            step, key = ("bf16", "precision_bf16") if args.precision == "bf16" else ("sligru", "sligru")
         out, err = child(step, args)
         with open(path) as f:
             res = json.loads(f.read().strip().splitlines()[-1])
         res[key] = out if err is None else {"failed": err}
-        for item in args.headline if key == "sligru" else []:  # (bench.py of this tree and of the parent, as below)
+        for item in args.headline if key.startswith("sligru") else []:  # (bench.py of this tree and of the parent, as below)
             name, file = item.split("=", 1)
             with open(file) as f:
                 full = json.loads([ln for ln in f.read().splitlines() if ln.strip().startswith("{")][-1])
